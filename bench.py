@@ -1,17 +1,27 @@
 #!/usr/bin/env python3
 """bench.py - training examples/sec of the CFFM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step is one fused forward + backward + Adagrad update (the reference's ``sess.run((loss, optimizer))``,
 CFFM.py:200) over one batch of synthetic libfm rows of the frappe shape (10 fields, dim 32, batch 256 per
-GPU, selu - README.md:28).  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON
-line; besides the contract keys it carries
+GPU, selu - README.md:28).  Inputs are resident in HBM before the timed region.  A plain run sets up, runs W
+untimed steps, times exactly K steps and prints ONE JSON line (rank 0).
 
+--dump-outputs DIR  after the timed steps, writes what the last step left to its caller as DIR/<name>.npy: the
+                    loss it returned (float64) and every trained variable after its update (float32; a table
+                    beyond 32 MB as a fixed, seeded sample of its rows, whose indices are in table_rows.npy).
+                    Inputs and initial parameters are seeded, so two builds can be compared output for output.
+
+--full adds to the line what the headline figure does not need:
+
+  value_with_host_batching  the same loop with the host-side batcher of CFFM.train in it
   roofline      the embedding-gather kernel (the kernel BASELINE.json's metric names) on the 1M-feature
                 stress shape (32 fields, dim 64, batch 8192, uniform ids: tables 516 MB > Infinity Cache),
-                algorithmic bytes F*(K+D+1)*4 + F*4 per example / HIP-event time per launch, vs 8 TB/s
+                algorithmic bytes F*(K+D+1)*4 + F*4 per example / HIP-event time per launch, vs 8 TB/s,
+                with the measured copy / MFMA peaks of the box
+  stress        a driver-timed train step at that stress shape
   stage_us      HIP-event time of every stage of the timed workload (where the step time goes)
   cpu_baseline  the numpy oracle (CPU restatement of the TF1 graph, kind "port") timed on the host cores
                 on a bounded sample of the same workload
@@ -300,6 +310,31 @@ def cpu_baseline(cfg, X, y, budget_s=9.0):
             'torch_cpu': round(torch_rate, 1), 'numpy_oracle': round(numpy_rate, 1)}
 
 
+DUMP_TABLE_BYTES = 32 << 20    # --dump-outputs: tables beyond this are written as a seeded sample of their rows
+
+
+def dump_outputs(out_dir, eng, loss):
+    """--dump-outputs: what the last timed step hands its caller - the loss it returned and every trained variable after its
+    update - as <out_dir>/<name>.npy (float64 loss, float32 variables).  The three tables go whole up to DUMP_TABLE_BYTES and
+    beyond that as one fixed, seeded sample of their rows (indices in table_rows.npy), so a dump stays well below 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': np.array([loss], dtype=np.float64)}
+    arrays.update(eng.export_params_dense())
+    M = eng.inner.shape[0]
+    row_bytes = (eng.inner.shape[1] + eng.outer.shape[1] + 1) * 4
+    idx = None
+    if M * row_bytes > DUMP_TABLE_BYTES:
+        rows = np.sort(np.random.default_rng(2021).choice(M, size=DUMP_TABLE_BYTES // row_bytes, replace=False))
+        arrays['table_rows'] = rows.astype(np.float64)
+        idx = torch.from_numpy(rows).to(eng.inner.device)
+    for name, t in (('inner_embeddings', eng.inner), ('outer_embeddings', eng.outer),
+                    ('feature_bias', eng.fbias.reshape(-1, 1))):
+        arrays[name] = (t if idx is None else t.index_select(0, idx)).cpu().numpy()
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + '.npy'), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def self_launch(n):
     """Run this same command line under torch.distributed.run with n ranks on this node (127.0.0.1 rendezvous: the
     container hostname may not resolve) and return its exit status.  Nothing here initialises the GPU."""
@@ -335,10 +370,17 @@ def main():
     ap.add_argument('--dp-mode', default='auto', choices=['auto', 'dense', 'gather'],
                     help='data-parallel exchange: dense image of the table gradients in one all-reduce (small vocabularies) or '
                          'all-gather of the row gradients; auto picks by size')
-    ap.add_argument('--blocks', type=int, default=0,
-                    help='timed blocks of --steps steps; the median block is reported (default 25, 1 for the big shapes)')
-    ap.add_argument('--quick', action='store_true', help='skip stage times, roofline, peaks and the CPU baseline')
+    ap.add_argument('--blocks', type=int, default=1,
+                    help='timed blocks of --steps steps; the median block is reported (default 1: exactly --steps timed steps)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the figure with host batching, stage times, '
+                         'roofline, stress step, peaks and the CPU baseline')
+    ap.add_argument('--quick', action='store_true', help='with --full: skip stage times, roofline, peaks and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss and the trained variables the last step left as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.blocks < 1:
+        raise SystemExit('bench.py: --steps and --blocks must be >= 1, --warmup >= 0')
 
     if (args.gpus > 1 or os.environ.get('CFFM_BENCH_SELF_LAUNCH')) and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, as children (one process per GPU over RCCL), BEFORE
@@ -416,9 +458,9 @@ def main():
         barrier = lambda: None
 
     # W untimed warm-up steps, then blocks of EXACTLY K timed steps, each bracketed by barrier + synchronize on both sides
-    # and reduced with MAX over the ranks.  A block of 20 frappe steps is 2.4 ms, so one block decides nothing: the
-    # reported figure is the MEDIAN block (all block times are in ms_per_step_blocks); the big shapes run one block.
-    n_blocks = args.blocks if args.blocks > 0 else (1 if big else 25)
+    # and reduced with MAX over the ranks.  One block by default, so that --steps is the number of timed steps; with
+    # --blocks > 1 the reported figure is the MEDIAN block (all block times are in ms_per_step_blocks).
+    n_blocks = args.blocks
     for i in range(args.warmup):
         step(i)
     block_dt = []
@@ -450,6 +492,8 @@ def main():
             raise SystemExit('bench.py: the replicas diverged (rank %d)' % rank)
     if big:
         torch.cuda.empty_cache()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)
 
     if rank == 0:
         res = {
@@ -475,7 +519,8 @@ def main():
                            'replicas_bit_identical_after_run': agree}
             if args.tables == 'sharded':
                 res['dist']['plans_built'], res['dist']['plans_reused'] = sh.plans_built, sh.plans_reused
-        if world == 1 and not args.quick and args.tables == 'replicated' and not args.force_dp:
+        extras = args.full and not args.quick
+        if world == 1 and extras and args.tables == 'replicated' and not args.force_dp:
             # the same loop with the host-side batcher of CFFM.train in it (random start on the host, slice of the
             # device-resident split): SURVEY 8d's "second figure including host batching"
             Xall, yall = X.reshape(-1, cfg.F), y.reshape(-1)
@@ -495,7 +540,7 @@ def main():
             res['roofline']['measured_peaks'] = measured_peaks(device)
             if not args.no_cpu_baseline and not big:
                 res['cpu_baseline'] = cpu_baseline(cfg, Xh, yh)
-        elif world > 1 and not args.quick and args.tables == 'replicated':
+        elif world > 1 and extras and args.tables == 'replicated':
             # N > 1: the roofline object of the dominant gather kernel again, measured on rank 0's GPU once the timed blocks are
             # over (the other ranks wait at the final barrier; cpu_baseline is an N = 1 figure by contract)
             del X, y
