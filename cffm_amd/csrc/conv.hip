@@ -170,12 +170,15 @@ __device__ __forceinline__ void gemm_tile(f32x4 (&acc)[RM][NT], int khalves, flo
 
 // -------------------------------------------------------------------------------------------------
 // The same K loop on the bf16 MFMA pipe at fp32 accuracy ("bf16x3"): every fp32 operand is split WITHOUT ERROR into three bf16
-// pieces, x = x1 + x2 + x3 (x1 = the top 8 significand bits of x, x2 those of the exact remainder x - x1, x3 those of x - x1 -
-// x2: 24 bits in all, same exponent range as fp32), and a product a*b is taken as the six cross terms of weight >= 2^-16,
+// pieces, x = x1 + x2 + x3 (x1 = x rounded to nearest bf16, x2 = the exact remainder x - x1 rounded to nearest, x3 = x - x1 - x2,
+// itself an exact bf16: |x - x1| <= 2^-8 |x| spans at most 16 significand bits; same exponent range as fp32), and a product a*b is
+// taken as the six cross terms of weight >= 2^-16,
 //     a1 b1 + (a1 b2 + a2 b1) + (a2 b2 + a1 b3 + a3 b1),
 // each term an EXACT fp32 value (8 x 8 significand bits) added into the fp32 accumulator of v_mfma_f32_16x16x32_bf16.  What is
-// dropped - a2 b3 + a3 b2 + a3 b3 - is below 2^-23 |a b|: the rounding error of ONE fp32 multiply, against an accumulation
-// over K = 496 .. 1984 terms that both forms round term by term.  Six bf16 MFMAs of 16 cycles do the work of eight fp32 MFMAs of
+// dropped - a2 b3 + a3 b2 + a3 b3 - is at most 2^-24 |a b| per term (|x2| <= 2^-8 |x|, |x3| <= 2^-16 |x|) and
+// has no preferred sign, against an accumulation over K = 496 .. 1984 terms that both forms round term by term.  (A split by
+// truncation is also exact, but its pieces x2, x3 always carry the sign of x: the dropped terms reach 2^-20 |a b| with the sign of
+// a b, a relative bias of -4e-8 in every long sum - tests/test_gpu_layers.py checks the slope.)  Six bf16 MFMAs of 16 cycles do the work of eight fp32 MFMAs of
 // 32 (16x16x4, same output layout): 2.7x on the pipe that bounds the wide shapes (CFFM.py:384-391 at F = 32: 98 % of the step).
 // CFFM_CONV_FP32=1 runs the fp32 MFMA loop above instead (A/B, and the reference the parity of this one was first checked on).
 //
@@ -186,15 +189,16 @@ __device__ __forceinline__ void gemm_tile(f32x4 (&acc)[RM][NT], int khalves, flo
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-// two floats -> their three bf16 pieces, packed (low half = first float).  Truncation splits: every remainder is exact.
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+// two floats -> their three bf16 pieces, packed (low half = first float).  Round-to-nearest pieces (v_cvt_pk_bf16_f32); every
+// remainder is exact and the last piece converts without rounding.
 __device__ __forceinline__ void split_bf16x3(float x0, float x1, unsigned& p1, unsigned& p2, unsigned& p3) {
-    const unsigned u0 = __float_as_uint(x0), u1 = __float_as_uint(x1);
-    p1 = __builtin_amdgcn_perm(u1, u0, 0x07060302u);                              // (hi16(x0), hi16(x1))
-    const float r0 = x0 - __uint_as_float(u0 & 0xffff0000u), r1 = x1 - __uint_as_float(u1 & 0xffff0000u);
-    const unsigned v0 = __float_as_uint(r0), v1 = __float_as_uint(r1);
-    p2 = __builtin_amdgcn_perm(v1, v0, 0x07060302u);
-    const float s0 = r0 - __uint_as_float(v0 & 0xffff0000u), s1 = r1 - __uint_as_float(v1 & 0xffff0000u);
-    p3 = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
+    p1 = __builtin_bit_cast(unsigned, (bf16x2_t){(__bf16)x0, (__bf16)x1});
+    const float r0 = x0 - __uint_as_float(p1 << 16), r1 = x1 - __uint_as_float(p1 & 0xffff0000u);
+    p2 = __builtin_bit_cast(unsigned, (bf16x2_t){(__bf16)r0, (__bf16)r1});
+    const float s0 = r0 - __uint_as_float(p2 << 16), s1 = r1 - __uint_as_float(p2 & 0xffff0000u);
+    p3 = __builtin_bit_cast(unsigned, (bf16x2_t){(__bf16)s0, (__bf16)s1});
 }
 __device__ __forceinline__ void split8_bf16x3(const float4& lo, const float4& hi, u32x4_t (&p)[3]) {
     unsigned q[4][3];
@@ -1181,7 +1185,7 @@ __global__ __launch_bounds__(256, 2) void wgrad2_kernel(WgradArgs a) {
 // wgrad3: the same weight gradient on the bf16 MFMA pipe at fp32 accuracy (bf16x3, see gemm_tile_b3): both operands are split
 // without error into three bf16 pieces WHILE THEY ARE STAGED, the LDS images hold [piece][m-octet][channel] records of 8 bf16
 // (8 consecutive reduction rows of one channel: one ds_read_b128 = the operand of one v_mfma_f32_16x16x32_bf16), and the six
-// cross terms of weight >= 2^-16 are accumulated in fp32.  One 32-row step per barrier pair (48 KB of LDS: three workgroups per
+// cross terms of gemm_tile_b3 are accumulated in fp32.  One 32-row step per barrier pair (48 KB of LDS: three workgroups per
 // CU cover each other's staging); waves 0-1 stage A' = act(C_{l-1}) patches, waves 2-3 stage dC and keep the bias gradient.
 template <int NT>
 __global__ __launch_bounds__(256, 3) void wgrad3_kernel(WgradArgs a) {

@@ -1,0 +1,322 @@
+"""GPU: every conv layer of the outer branch against the float64 contraction of its own device inputs (oracle/layer_check.py).
+
+Two paths on the same seeded case:
+  product   eng.forward + eng.backward (the fused kernels wherever the dispatch picks them), then each layer's outputs in the
+            workspace against the reference of that layer's inputs in the workspace, and the gradients after export_grad
+  stage     cffm_outer_conv0_fwd, cffm_conv_fwd(l), cffm_conv_bwd(l), cffm_outer_conv0_bwd and cffm_reduce_slabs one at a time on
+            the same workspace (the unfused instances), checked the same way
+Cases with a bf16x3 instance (wide filters, NT = 8: the forward / input gradient of a layer with >= 32768 rows, the weight gradient
+of every layer >= 1) run a second time in a child process with CFFM_CONV_FP32=1 (latched in a static at first use, so it cannot
+change within one process); the child returns the statistics of the fp32 loops, which the distribution and bias tiers of the
+bf16x3 tensors are held against (b3_instances() names them per case)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from cffm_amd.spec import CFFMConfig, init_params  # noqa: E402
+from oracle import layer_check as lc  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+CASES = {
+    # narrow filters (Pp <= 64): tap-split kernels with 1 and 2 row groups, the rows kernel (>= 32768 rows at layer 1)
+    'f6-d32-b16-selu': dict(F=6, K=8, D=32, act='selu', B=16),
+    'f10-d32-b256-gelu': dict(F=10, K=8, D=32, act='gelu', B=256),
+    'f10-d32-b512-elu': dict(F=10, K=8, D=32, act='elu', B=512),
+    # wide filters: NT = 6 (F = 20) with a ragged last row tile (layer 2: 33 x 16 rows), the tiled layer 0
+    'f20-d32-b33-selu': dict(F=20, K=8, D=32, act='selu', B=33),
+    # NT = 8 with ragged columns (Pp = 496) and the weight gradient on the bf16 pipe at a small row count
+    'f32-d32-b6-elu': dict(F=32, K=8, D=32, act='elu', B=6),
+    # F = 33: layer 0 forward / input gradient through the direct kernels
+    'f33-d32-b5-relu': dict(F=33, K=8, D=32, act='relu', B=5),
+    # the bf16x3 forward and input gradient: layer 1 of F16 D32 at B = 512 has exactly 32768 rows; both ACTA builds (selu, gelu)
+    'f16-d32-b512-relu': dict(F=16, K=8, D=32, act='relu', B=512),
+    'f16-d32-b512-selu': dict(F=16, K=8, D=32, act='selu', B=512),
+    'f16-d32-b512-gelu': dict(F=16, K=8, D=32, act='gelu', B=512),
+    # the cfg4 instances (F32 D64: Pp = 496, five layers) with layer 1 on the bf16x3 forward / input gradient (128 x 256 rows)
+    'f32-d64-b128-relu': dict(F=32, K=16, D=64, act='relu', B=128),
+    # cfg4 at full size (BASELINE configs[3]: F32 K = D = 64, B = 8192; C[0] holds 4.2e9 elements, past 2^31), heavy: the grid sizes
+    # and 64-bit element offsets of the stress step.  Forward, input gradient, masks and pools on 32 sampled examples - the first
+    # and last eight (first and last row tiles of every layer) and 16 spread over the batch (row tiles of every XCD's share) -,
+    # weight gradients over all rows through the chunked float64 device reference; product path only (the stage path runs the
+    # same instances at this shape).
+    'cfg4-f32-d64-b8192-relu': dict(F=32, K=64, D=64, act='relu', B=8192, M=100000, heavy=True),
+}
+HEAVY = [k for k, v in CASES.items() if v.get('heavy')]
+
+
+# Two bf16x3 contractions keep a slope with the round-to-nearest split that the CPU replay of the split does not have and the
+# fp32 loops on the identical case do not show ("Per-layer check"; cause not found): the forward (gemm_tile_b3)
+# and the weight gradient (wgrad3), both growing with the reduction length.  They are held to pinned ceilings fitted to what was
+# measured, set below what the truncating split gave on the same tensors, so that the residual cannot grow unnoticed:
+#   forward, reduction length K = 4 Pp:  |beta| <= 0.95e-3 K u.  Measured -2.2e-8 at K = 512 (F16, relu / selu / gelu) and -8.6e-8 ..
+#       -1.01e-7 at K = 1984 (F32 D64, B = 128 and 8192, layers 1-4); ceilings 2.9e-8 / 1.12e-7; truncating split -6.2e-8 / -1.29e-7.
+#   layer-1 weight gradient:  |beta| <= 3.5e-8.  Measured -1.3e-8 (F16 B512) and -2.8e-8 (F32 D64 B128), both 32768 rows; truncating
+#       split 4.2e-8 .. 5.7e-8 on the same tensors (selu / gelu corrected for the fp32 activation).
+# The weight-gradient slope grows with the row count: at F32 D64 B8192 it is -1.5e-8 (32768 rows), -4.8e-8, -1.6e-7 and -5.7e-7
+# (2097152 rows, where the 99.9th percentile of |err| / S is also 8.3 u against the fp32 loops' 3.4 u).  That is an open defect of
+# wgrad3, not a tolerance: the heavy case reports those tiers of its weight gradients as an expected failure (KNOWN_WGRAD3) and
+# asserts everything else.
+# The input gradients are held to BIAS_MAX_B3 at every size.
+def b3_residual_ceiling(inst, Pp):
+    if inst[0] == 'fwd':
+        return 0.95e-3 * (4 * Pp) * lc.U
+    if inst == ('wgrad', 1):
+        return 3.5e-8
+    return None
+
+
+def _pick_nt(tiles):
+    nb = (tiles + 7) // 8
+    need = (tiles + nb - 1) // nb
+    return next(n for n in (1, 2, 3, 4, 6, 8) if n >= need)
+
+
+def b3_instances(cfg, B):
+    """(direction, layer) pairs that run on the bf16 pipe by default (conv.hip: launch_conv_fwd / launch_dgrad NT = 8, RM = 2 at
+    >= 128 x 256 rows; launch_wgrad2<8> -> wgrad3_kernel)."""
+    Pp = (cfg.P + 15) // 16 * 16
+    out = set()
+    if Pp <= 64:
+        return out
+    for l in range(1, cfg.live_layers):
+        rows = B * (cfg.D >> (l + 1)) ** 2
+        if _pick_nt(Pp // 16) == 8:
+            out.add(('wgrad', l))
+            if rows >= 128 * 256:
+                out.add(('fwd', l))
+        if _pick_nt(4 * Pp // 16) == 8 and rows >= 128 * 256:
+            out.add(('dgrad', l))
+    return out
+
+
+def make_layer_case(name, seed=0):
+    c = CASES[name]
+    cfg = CFFMConfig(M=c.get('M', 4000), F=c['F'], K=c['K'], D=c['D'], activation=c['act'], lamda_att=1.3)
+    p32 = init_params(cfg, seed=seed, dtype=np.float32)
+    rng = np.random.default_rng(seed + 7)
+    p32['feature_bias'] = (rng.standard_normal(p32['feature_bias'].shape) * 0.3).astype(np.float32)
+    p32['outer_embeddings'] = (p32['outer_embeddings'] * 20.0).astype(np.float32)    # trained-like magnitudes (make_case)
+    p32['inner_embeddings'] = (p32['inner_embeddings'] * 4.0).astype(np.float32)
+    for l in range(cfg.live_layers):      # biases of both signs: the bias add, relu and the gate all have work to do
+        k = 'outer_layer_conv_bias_%d' % l
+        p32[k] = (rng.standard_normal(p32[k].shape) * 0.02).astype(np.float32)
+    X = rng.integers(0, cfg.M, size=(c['B'], cfg.F)).astype(np.int32)
+    y = rng.choice([-1.0, 1.0], size=(c['B'],)).astype(np.float32)
+    return cfg, p32, X, y
+
+
+def _t1_off(D, l):
+    return sum(D >> i for i in range(l))
+
+
+class _Ws(object):
+    """The device tensors of one case, read straight from the workspace (no copies to the host)."""
+
+    def __init__(self, eng, cfg, B):
+        self.eng, self.cfg, self.B = eng, cfg, B
+        self.Pp = eng.tl.Pp
+        _, self.wl = eng.workspace(B)
+
+    def C(self, l, grad=False):
+        S = self.cfg.D >> (l + 1)
+        return self.eng.ws_tensor(self.B, 'dC' if grad else 'C', (self.B, S, S, self.Pp), index=l)
+
+    def get(self, member, shape, dtype=torch.float32, index=None):
+        return self.eng.ws_tensor(self.B, member, shape, dtype=dtype, index=index)
+
+
+def check_layers(path, eng, cfg, p32, X, grads, out, fails, twin=None, bias=True, b3=frozenset(), sample=None, known=None):
+    """Every layer of the outer stack, re-anchored on the device's own inputs.  grads: name -> device gradient [2,2,P,P] / [P].
+    Fills out = {tensor name: stats}; a tensor that misses a tier appends its message to fails (the other tensors are still
+    checked and reported).  twin: the same dict from the CFFM_CONV_FP32=1 child (applied to the bf16x3 tensors).  sample: example
+    indices (a device tensor) to which everything but the weight / bias gradients is restricted."""
+    dev = eng.device
+    B, P, D, live = X.shape[0], cfg.P, cfg.D, cfg.live_layers
+    ws = _Ws(eng, cfg, B)
+    sel = (lambda t: t) if sample is None else (lambda t: t.index_select(0, sample))
+    Eo_all = torch.from_numpy(p32['outer_embeddings'][X]).to(dev)          # what the gather copied (exact; test_gpu_parity)
+    Eo = sel(Eo_all)
+    dt1 = sel(ws.get('dt1', (B, 2 * D - 2)))
+    t1 = sel(ws.get('t1', (B, 2 * D - 2)))
+    Pp = ws.Pp
+
+    def tier(name, got, ref, S, n, mask=None, inst=None):
+        split = inst in b3
+        tw = twin.get(name) if (twin is not None and split) else None
+        try:
+            lc.check_tiers(name, got, ref, S, n, bias_mask=mask, twin=tw, bias=bias, sink=out,
+                           bias_ceiling=b3_residual_ceiling(inst, Pp) if split else None)
+        except AssertionError as e:
+            msg = '%s path: %s' % (path, e)
+            if known is not None and split and inst[0] == 'wgrad' and ('slope' in msg or '99.9th' in msg):
+                known.append(msg)
+            else:
+                fails.append(msg)
+
+    for l in range(live):
+        C = sel(ws.C(l))
+        lc.exact_pads_zero('%s C[%d]' % (path, l), C, P)
+        lc.exact_relu_out('%s C[%d]' % (path, l), C)
+        if ws.wl.relu0 > 0 and l + 1 < live:
+            lc.exact_mask('%s relu mask of C[%d]' % (path, l), sel(relu_words(eng, cfg, B, l)), C)
+        prev = Eo if l == 0 else sel(ws.C(l - 1))[..., :P]
+        W, b = p32['outer_layer_conv_weight_%d' % l], p32['outer_layer_conv_bias_%d' % l]
+        z, S = lc.ref_forward(prev, W, b, l, cfg, device=dev)
+        tier('C[%d]' % l, C[..., :P], torch.clamp(z, min=0), S, 4 * P + 1, mask=z > 0, inst=('fwd', l))
+        pool, Sp = lc.ref_pool(C[..., :P], cfg, device=dev)
+        So = D >> (l + 1)
+        if path == 'product':                  # the head's t1 (the stage path does not re-run the head)
+            tier('t1 pool %d' % (l + 1), t1[:, _t1_off(D, l + 1):_t1_off(D, l + 1) + So], pool, Sp, So * P)
+        if ws.wl.pool_np[l] > 0:
+            parts = sel(ws.get('pool', (B, So, int(ws.wl.pool_np[l])), index=l)).double().sum(-1)
+            tier('pool partials %d' % (l + 1), parts, pool, Sp, So * P + int(ws.wl.pool_np[l]))
+        del z, S
+    for l in range(live - 1, -1, -1):
+        dC = sel(ws.C(l, grad=True))
+        lc.exact_pads_zero('%s dC[%d]' % (path, l), dC, P)
+        W = p32['outer_layer_conv_weight_%d' % l]
+        if l >= 1:
+            Cprev = sel(ws.C(l - 1))[..., :P]
+            got = sel(ws.C(l - 1, grad=True))[..., :P]
+            ref, S = lc.ref_dgrad(dC[..., :P], W, dt1[:, _t1_off(D, l):_t1_off(D, l) + (D >> l)], Cprev, l, cfg, device=dev)
+            lc.exact_gated_zero('%s dC[%d]' % (path, l - 1), got, Cprev)
+            tier('dC[%d]' % (l - 1), got, ref, S, P + 3, inst=('dgrad', l))
+        else:
+            ref, S = lc.ref_dgrad0(dC[..., :P], W, dt1[:, :D], Eo, cfg, device=dev)
+            tier('dEo', sel(ws.get('dEo', (B, cfg.F, D))), ref, S, P + 3 + (cfg.F - 1) * D)
+        del ref, S
+        prev = Eo_all if l == 0 else ws.C(l - 1)[..., :P]           # the weight gradient: every row
+        gw, sw, gb, sb = lc.ref_wgrad(prev, ws.C(l, grad=True)[..., :P], l, cfg, device=dev)
+        rows = B * (D >> (l + 1)) ** 2
+        tier('grad W[%d]' % l, grads['outer_layer_conv_weight_%d' % l], gw, sw, rows, inst=('wgrad', l))
+        tier('grad b[%d]' % l, grads['outer_layer_conv_bias_%d' % l], gb, sb, rows)
+
+
+def relu_words(eng, cfg, B, l):
+    """ws.relu0 words of C[l] as [B, S*S*Pp/16] int16 (common.hpp relu_mask_off: 256-byte aligned layers one after the other)."""
+    Pp = eng.tl.Pp
+    buf, wl = eng.workspace(B)
+    off = int(wl.relu0) + sum((B * (cfg.D >> (k + 1)) ** 2 * (Pp // 16) * 2 + 255) // 256 * 256 for k in range(l))
+    n = B * (cfg.D >> (l + 1)) ** 2 * (Pp // 16)
+    return buf[off:off + 2 * n].view(torch.int16).reshape(B, -1)
+
+
+def stage_grads(eng, flat):
+    tl, P, Pp = eng.tl, eng.tl.P, eng.tl.Pp
+    g = {}
+    for l in range(tl.live):
+        g['outer_layer_conv_weight_%d' % l] = flat[tl.conv_w[l]:tl.conv_w[l] + 4 * Pp * Pp].reshape(4, Pp, Pp)[:, :P, :P].reshape(2, 2, P, P)
+        g['outer_layer_conv_bias_%d' % l] = flat[tl.conv_b[l]:tl.conv_b[l] + P]
+    return g
+
+
+def run_case(name, res, fails, twin=None, bias=True, known=None):
+    """Both paths of one case: fills res = {'product': stats, 'stage': stats} and fails (see check_layers)."""
+    from cffm_amd import hip
+    from cffm_amd.engine import HipEngine
+    cfg, p32, X, y = make_layer_case(name)
+    B = X.shape[0]
+    b3 = frozenset(b3_instances(cfg, B))
+    eng = HipEngine(cfg, params=p32)
+    ids, yt = torch.from_numpy(X).cuda(), torch.from_numpy(y).cuda()
+    eng.forward(ids, yt)
+    eng.backward(yt, B)
+    torch.cuda.synchronize()
+    dev_grads = {k: torch.as_tensor(v).cuda() for k, v in eng.export_grad().items() if k.startswith('outer_layer_conv_')}
+    res['product'] = {}
+    if CASES[name].get('heavy'):
+        sample = torch.tensor(sorted(set(range(8)) | set(range(B - 8, B)) | set(np.linspace(8, B - 9, 16).astype(int).tolist())),
+                              device=eng.device)
+        chunk, lc.CHUNK = lc.CHUNK, 1 << 25
+        try:
+            check_layers('product', eng, cfg, p32, X, dev_grads, res['product'], fails, (twin or {}).get('product'), bias, b3,
+                         sample=sample, known=known)
+        finally:
+            lc.CHUNK = chunk
+        del eng
+        torch.cuda.empty_cache()
+        return
+    res['stage'] = {}
+    check_layers('product', eng, cfg, p32, X, dev_grads, res['product'], fails, (twin or {}).get('product'), bias, b3)
+    # stage path: the same workspace, one entry point at a time (dC[live-1] and dt1 stay from the product backward)
+    buf, wl = eng.workspace(B)
+    eng.ws_tensor(B, 'Eo', (B, cfg.F, cfg.D)).copy_(torch.from_numpy(p32['outer_embeddings'][X]))
+    lib, s, th, st = eng.lib, eng._s, eng.theta.data_ptr(), eng._stream()
+    P, Pp = cfg.P, eng.tl.Pp
+    for l in range(cfg.live_layers):           # every value a stage reports must have been written by that stage
+        C = eng.ws_tensor(B, 'C', (B, (cfg.D >> (l + 1)) ** 2, Pp), index=l)
+        C[..., :P].fill_(float('nan'))
+        C[..., P:].fill_(1.0)                  # pad channels: nonzero, so that only a stage that writes them passes
+        if wl.relu0 > 0 and l + 1 < cfg.live_layers:
+            relu_words(eng, cfg, B, l).fill_(0x5555)
+        if wl.pool_np[l] > 0:
+            eng.ws_tensor(B, 'pool', (B * (cfg.D >> (l + 1)) * int(wl.pool_np[l]),), index=l).fill_(float('nan'))
+    hip.check(lib.cffm_outer_conv0_fwd(s, th, buf.data_ptr(), B, st))
+    for l in range(1, cfg.live_layers):
+        hip.check(lib.cffm_conv_fwd(s, th, buf.data_ptr(), B, l, st))
+    for l in range(cfg.live_layers - 1):
+        dC = eng.ws_tensor(B, 'dC', (B, (cfg.D >> (l + 1)) ** 2, Pp), index=l)
+        dC[..., :P].fill_(float('nan'))
+        dC[..., P:].fill_(1.0)
+    eng.ws_tensor(B, 'dEo', (B * cfg.F * cfg.D,)).fill_(float('nan'))
+    for l in range(cfg.live_layers - 1, 0, -1):
+        hip.check(lib.cffm_conv_bwd(s, th, buf.data_ptr(), B, l, st))
+    hip.check(lib.cffm_outer_conv0_bwd(s, th, buf.data_ptr(), B, st))
+    flat = torch.full((int(eng.tl.n),), float('nan'), dtype=torch.float32, device=eng.device)
+    hip.check(lib.cffm_reduce_slabs(s, buf.data_ptr(), B, flat.data_ptr(), st))
+    torch.cuda.synchronize()
+    check_layers('stage', eng, cfg, p32, X, stage_grads(eng, flat), res['stage'], fails, (twin or {}).get('stage'), bias, b3)
+    del eng
+    torch.cuda.empty_cache()
+
+
+def _fp32_twin(name):
+    env = dict(os.environ, CFFM_CONV_FP32='1')
+    code = ('import json, sys; sys.path.insert(0, %r); from tests.test_gpu_layers import run_case; res, fails = {}, []; '
+            'run_case(%r, res, fails, bias=False); print("TWIN " + json.dumps(res)); sys.exit("\\n".join(fails) if fails else 0)'
+            % (ROOT, name))
+    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, 'fp32-loop twin of %s failed (%d):\n%s' % (name, r.returncode, (r.stdout + r.stderr)[-4000:])
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith('TWIN ')][-1]
+    return json.loads(line[5:])
+
+
+def _report(name, res, twin):
+    path = os.environ.get('CFFM_LAYER_STATS')
+    if not path:
+        return
+    data = {}
+    if os.path.exists(path):
+        with open(path) as fh:
+            data = json.load(fh)
+    data[name] = {'default': res, 'fp32_loops': twin}
+    with open(path, 'w') as fh:
+        json.dump(data, fh, indent=1)
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_layers(name):
+    cfg, _, X, _ = make_layer_case(name)
+    b3 = b3_instances(cfg, X.shape[0])
+    twin = _fp32_twin(name) if b3 else None
+    res, fails, known = {}, [], []
+    try:
+        run_case(name, res, fails, twin=twin, known=known if CASES[name].get('heavy') else None)
+    finally:
+        _report(name, res, twin)
+    for path, st in res.items():
+        print(path, ', '.join('%s beta %.2g p99.9 %.2fu' % (k, v['beta'], v['p999_u']) for k, v in st.items()))
+    assert not fails, '\n'.join(fails)
+    if known:
+        pytest.xfail('KNOWN_WGRAD3 (DESIGN.md 3.4): wgrad3 slope grows with the row count at full size\n' + '\n'.join(known))
+
