@@ -9,7 +9,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Iinclude -Wall -Wno-unu
 ifdef PHASE_TIMERS
 CXXFLAGS += -DCFFM_PHASE_TIMERS
 endif
-# debug build only: CFFM_DBG=<bits> skips phases of the tiled layer-0 kernels (tools/dbg_tile.py)
+# debug build only: the fused gather kernel traps if its dynamic LDS does not start at address 0 (inner.hip)
 ifdef TILE_DBG
 CXXFLAGS += -DCFFM_TILE_DBG
 endif

@@ -10,7 +10,8 @@
 //                        fused with the broadcast sum-pool gradient and the relu/act mask.
 //   dgrad<L0=true>       layer 0: the dA tile is contracted with the embedding tile straight into dEo
 //                        (per-wavefront private LDS accumulators, merged in wave order).
-//   wgrad<GEN>           weight/bias gradients: split-K over CFFM_NSLAB slabs, both operands via LDS.
+//   wgrad                weight/bias gradients of the direct layer 0: split-K over CFFM_NSLAB slabs, A operand generated
+//                        like conv_fwd<GEN=true>, B operand via LDS (the layers >= 1 run wgrad2 / wgrad3).
 //
 // Tiling: 256-thread workgroups = 4 wavefronts; a wavefront owns RM x NT tiles of 16x16 (rows = output
 // positions, cols = output channels).  The weight tile of a 32-deep K step is shared by the four
@@ -378,10 +379,10 @@ struct ConvArgs {
     int64_t Mtot;        // B*So*So
     int B, lgSo, P, Pp, F, D, act;
     int nblk;            // conv_fwd_kernel: column blocks of a row tile (the grid is 1-D, see xcd_tile)
-    int dbg;             // debug build only (make TILE_DBG=1): phase-skipping bits for tools/dbg_tile.py, 0 otherwise
+    int idxStride = 0;              // tiled layer 0 only: floats between rows of the table (0 = D), see RowSrc.  Placed in the gap
+                                    // before `idx` so that the other members keep their kernel-argument offsets
     const int32_t* idx = nullptr;   // tiled layer 0 only: non-NULL = `in` is the outer TABLE [M][D] and row (b, f) is idx[b*F+f] (RowSrc)
     int idxM = 0;
-    int idxStride = 0;              // floats between rows of the table (0 = D): see RowSrc
     float* pool = nullptr;          // wide shapes: partial sum pools of act(out), [B][So][pool_np] (pool_partials(), common.hpp)
     int pool_np = 0;
     uint16_t* relu = nullptr;       // wide shapes (tiled layer-0 forward, conv_fwd_kernel): bit mask of out > 0, [B*So*So][Pp/16] 16-bit words (ws.relu0)
@@ -883,20 +884,19 @@ struct WgradArgs {
     int idxStride = 0;              // floats between rows of the table (0 = D): see RowSrc
 };
 
-// Generic form (64 x 16*NT output tile per workgroup): the direct layer 0 (GEN, F >= 33) and column-tile counts other than
-// 6 / 8; the layers >= 1 of the wide shapes run wgrad2_kernel below.
-template <int NT, bool GEN>
+// Direct layer 0 of the wide shapes (Pp > 64; NT = 6 or 8) where the factorised tiled kernel does not apply: 64 x 16*NT output
+// tile per workgroup, the A' operand generated per lane from the embedding tile in LDS.  The layers >= 1 run wgrad2_kernel below.
+template <int NT>
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     constexpr int RI = 1;                                            // row tiles per wavefront
-    constexpr int BI = 64 * RI, LDA = BI + 16, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16), KM = WG_KM;
-    constexpr int NB = KM * BQ / 256, NA = KM * BI / 4 / 256;     // per-thread B' floats / A' float4s per step
+    constexpr int BI = 64 * RI, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16), KM = WG_KM;
+    constexpr int NB = KM * BQ / 256;                                // per-thread B' floats per step
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Bs = reinterpret_cast<float*>(smem);                       // [KM][LDB]
-    float* As = Bs + KM * LDB;                                        // [KM][LDA]      (!GEN)
-    uint32_t* lut = reinterpret_cast<uint32_t*>(As + (GEN ? 0 : KM * LDA));   // [Pp]  (GEN)
-    float* Es = reinterpret_cast<float*>(lut + (GEN ? a.Pp : 0));     // [n_ex][F][Dp] (GEN)
+    uint32_t* lut = reinterpret_cast<uint32_t*>(Bs + KM * LDB);       // [Pp]
+    float* Es = reinterpret_cast<float*>(lut + a.Pp);                 // [n_ex][F][Dp]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, kk = lane >> 4;
-    const int So = 1 << a.lgSo, Sin = 2 * So, Pp = a.Pp, P = a.P, Dp = a.D + 1, S2 = So * So;
+    const int So = 1 << a.lgSo, Pp = a.Pp, P = a.P, Dp = a.D + 1, S2 = So * So;
     const float invPp = 1.f / (float)Pp;
     // all output tiles of ONE slab read the same rows of A' and dC: they run as consecutive blocks of one XCD, which
     // then works through its slabs one after the other (the operands reach the XCD's L2 once per slab)
@@ -909,26 +909,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     const int64_t nsteps = (a.Mtot + KM - 1) / KM;
     const int64_t cps = (nsteps + a.nslab - 1) / a.nslab;
     const int64_t s_lo = slab * cps, s_hi = min(nsteps, s_lo + cps);
-    const int n_ex = GEN ? (KM > S2 ? KM / S2 : 1) : 0;
+    const int n_ex = KM > S2 ? KM / S2 : 1;
 
-    // the (tap, p) this lane's A' row belongs to (GEN only: RI == 1)
+    // the (tap, p) this lane's A' row belongs to (RI == 1)
     const int irow = i0 + wave * 16 + r;
     const int tapA = fast_div(irow, invPp), pA = irow - tapA * Pp, dhA = tapA >> 1, dwA = tapA & 1;
-    int fi = 0, fj = 0;
-    if (GEN) {
-        build_pair_lut(lut, a.F, Pp);
-        __syncthreads();
-        const uint32_t ij = lut[pA];
-        fi = ij & 0xffff; fj = ij >> 16;
-    }
-    // staging geometry of this thread (fixed over the steps): BI/4 16-byte pieces per A' row
-    int a_tap[NA], a_p[NA];
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-        const int ii = i0 + 4 * ((tid + 256 * i) % (BI / 4));
-        a_tap[i] = fast_div(ii, invPp);                          // 4 for the rows of a last, partial tile beyond 4*Pp: zeros
-        a_p[i] = ii - a_tap[i] * Pp;
-    }
+    build_pair_lut(lut, a.F, Pp);
+    __syncthreads();
+    const uint32_t ij = lut[pA];
+    const int fi = ij & 0xffff, fj = ij >> 16;
     f32x4 acc[RI][NT];
 #pragma unroll
     for (int ri = 0; ri < RI; ++ri)
@@ -937,7 +926,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
     float bsum = 0.f;
     int cur_b = -1;
     float breg[NB];
-    float4 areg[NA > 0 ? NA : 1];
 
     auto fetch = [&](int64_t st) {            // global -> registers for step st
         const int64_t mbase = st * KM;
@@ -946,19 +934,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
             const int e = tid + 256 * i, row = e / BQ, c = e % BQ;
             const int64_t m = mbase + row;
             breg[i] = (m < a.Mtot && q0 + c < Pp) ? a.dC[m * Pp + q0 + c] : 0.f;
-        }
-        if (!GEN) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int64_t m = mbase + (tid + 256 * i) / (BI / 4);
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (m < a.Mtot && a_tap[i] < 4) {
-                    const RowPos rp = row_pos(m, a.lgSo);
-                    const int64_t pos = (((int64_t)rp.b * Sin + 2 * rp.y + (a_tap[i] >> 1)) * Sin + 2 * rp.x + (a_tap[i] & 1)) * Pp + a_p[i];
-                    v = *reinterpret_cast<const float4*>(a.in + pos);
-                }
-                areg[i] = v;
-            }
         }
     };
 
@@ -971,21 +946,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
             const int e = tid + 256 * i;
             Bs[(e / BQ) * LDB + (e % BQ)] = breg[i];
         }
-        if (!GEN) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                const int u = tid + 256 * i;
-                float4 v = areg[i];
-                v.x = act_pos(v.x, a.act); v.y = act_pos(v.y, a.act);
-                v.z = act_pos(v.z, a.act); v.w = act_pos(v.w, a.act);
-                *reinterpret_cast<float4*>(&As[(u / (BI / 4)) * LDA + 4 * (u % (BI / 4))]) = v;
-            }
-        } else {
-            const int bl = (int)(mbase >> (2 * a.lgSo));
-            if (bl != cur_b) {
-                stage_examples(Es, a.in, bl, n_ex, a.B, a.F, a.D, Dp);
-                cur_b = bl;
-            }
+        const int bl = (int)(mbase >> (2 * a.lgSo));
+        if (bl != cur_b) {
+            stage_examples(Es, a.in, bl, n_ex, a.B, a.F, a.D, Dp);
+            cur_b = bl;
         }
         __syncthreads();
         if (st + 1 < s_hi) fetch(st + 1);                 // in flight while this step's MFMAs run
@@ -993,16 +957,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
 #pragma unroll 2
         for (int ks4 = 0; ks4 < KM; ks4 += 4) {
             float av[RI];
-            if (GEN) {
-                int64_t m = mbase + ks4 + kk;
-                if (m >= a.Mtot) m = a.Mtot - 1;             // B' rows beyond Mtot are zero
-                const RowPos rp = row_pos(m, a.lgSo);
-                const int eb = (rp.b - cur_b) * a.F * Dp;
-                av[0] = pA < P ? Es[eb + fi * Dp + 2 * rp.y + dhA] * Es[eb + fj * Dp + 2 * rp.x + dwA] : 0.f;
-            } else {
-#pragma unroll
-                for (int ri = 0; ri < RI; ++ri) av[ri] = As[(ks4 + kk) * LDA + (wave * RI + ri) * 16 + r];
-            }
+            int64_t m = mbase + ks4 + kk;
+            if (m >= a.Mtot) m = a.Mtot - 1;                 // B' rows beyond Mtot are zero
+            const RowPos rp = row_pos(m, a.lgSo);
+            const int eb = (rp.b - cur_b) * a.F * Dp;
+            av[0] = pA < P ? Es[eb + fi * Dp + 2 * rp.y + dhA] * Es[eb + fj * Dp + 2 * rp.x + dwA] : 0.f;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (nt >= nvalid) continue;
@@ -1034,8 +993,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
 }
 
 // wgrad2: the weight / bias gradient of a conv layer >= 1 for WIDE filters (Pp > 64), same contraction and same split-K
-// slabs as wgrad_kernel<.., GEN = false>, restructured after the rocprofv3 counters of round 2 (MFMA pipe 40 % busy, one
-// exposed LDS round trip per two MFMAs: every B fragment was a ds_read_b32 followed by its own wait and a branch):
+// slabs as wgrad_kernel with A' = act(C_{l-1}) read from global memory, restructured after the rocprofv3 counters of round 2
+// (the generic form it replaced: MFMA pipe 40 % busy, one exposed LDS round trip per two MFMAs: every B fragment was a
+// ds_read_b32 followed by its own wait and a branch):
 //   * both operands are fetched in 16-byte pieces as 4 x 4 blocks (4 consecutive reduction rows m x 4 consecutive
 //     channels), transposed in registers and staged as [m/4][channel][4 m] records - the layout gemm_tile uses - so that a
 //     lane's fragments for FOUR MFMAs come back with one ds_read_b128 (a float4 = 4 consecutive m; A' and dC use the same
@@ -2906,14 +2866,13 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-#define DISPATCH_NT(NTV, CALL)                     \
-    switch (NTV) {                                 \
-        case 1: { constexpr int NT_ = 1; CALL; } break; \
-        case 2: { constexpr int NT_ = 2; CALL; } break; \
-        case 3: { constexpr int NT_ = 3; CALL; } break; \
-        case 4: { constexpr int NT_ = 4; CALL; } break; \
+// The direct layers run for Pp > 64 only, where pick_nt(Pp / 16) returns 6 or 8 (and pick_nt(4 * Pp / 16), the column tiles
+// of the input gradient, returns 8): no other column-tile count is compiled, and meeting one is an error.
+#define DISPATCH_NT68(NTV, CALL)                        \
+    switch (NTV) {                                      \
         case 6: { constexpr int NT_ = 6; CALL; } break; \
-        default: { constexpr int NT_ = 8; CALL; } break; \
+        case 8: { constexpr int NT_ = 8; CALL; } break; \
+        default: rc = CFFM_ERR_UNSUPPORTED; break;      \
     }
 
 template <class KernelT>
@@ -2923,6 +2882,22 @@ static inline int set_lds(KernelT k, size_t lds) {
         if (e != hipSuccess) return (int)e;
     }
     return 0;
+}
+
+template <int N> using IntC = std::integral_constant<int, N>;
+
+// The fused small-shape kernels get the activation of the README commands compiled in: frappe = selu at Pp 48 (NT 3), ml-tag =
+// elu and book-crossing = relu at Pp 16 (NT 1) (README.md:20-28); every other (NT, act) reads it at run time (-1).
+// go(IntC<ACT>) launches the instance; if constexpr keeps the (NT, ACT) pairs no shape reaches out of the build.
+template <int NT, class Go>
+static int with_readme_act(int act, Go&& go) {
+    if constexpr (NT == 3) {
+        if (act == CFFM_ACT_SELU) return go(IntC<CFFM_ACT_SELU>());
+    } else if constexpr (NT == 1) {
+        if (act == CFFM_ACT_ELU) return go(IntC<CFFM_ACT_ELU>());
+        if (act == CFFM_ACT_RELU) return go(IntC<CFFM_ACT_RELU>());
+    }
+    return go(IntC<-1>());
 }
 
 // bf16x3 K loop for the 128 x 128 instance of the direct layers (the one the wide shapes run); CFFM_CONV_FP32=1: the fp32 MFMA loop
@@ -2989,19 +2964,19 @@ static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
     return 0;
 }
 
-template <int NT, bool GEN>
+template <int NT>
 static int launch_wgrad(const WgradArgs& a, hipStream_t st) {
     constexpr int BI = 64, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16);
     const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex = GEN ? (WG_KM > S2 ? WG_KM / S2 : 1) : 0;
-    const size_t lds = (size_t)(WG_KM * LDB + (GEN ? a.Pp + n_ex * a.F * (a.D + 1) : WG_KM * (BI + 16)) + 4) * 4;
-    int rc = set_lds(wgrad_kernel<NT, GEN>, lds);
+    const int n_ex = WG_KM > S2 ? WG_KM / S2 : 1;
+    const size_t lds = (size_t)(WG_KM * LDB + a.Pp + n_ex * a.F * (a.D + 1) + 4) * 4;
+    int rc = set_lds(wgrad_kernel<NT>, lds);
     if (rc) return rc;
     WgradArgs b = a;
     b.nslab = CFFM_NSLAB;                                                       // Pp > 64: conv_slabs() == CFFM_NSLAB
     b.nxy = ((4 * a.Pp + BI - 1) / BI) * a.qblocks;
     dim3 grid((unsigned)(8 * xcd_per(b.nslab) * b.nxy));
-    hipLaunchKernelGGL((wgrad_kernel<NT, GEN>), grid, dim3(256), lds, st, b);
+    hipLaunchKernelGGL((wgrad_kernel<NT>), grid, dim3(256), lds, st, b);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -3080,16 +3055,11 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_fwd_kernel(ConvArg
     int bid = blockIdx.x;
     const int b = bid % a.B; bid /= a.B;
     const int xt = bid % RT, qt = bid / RT, q0 = qt * 16, x0 = xt * 16;
-#ifdef CFFM_TILE_DBG
-    const int dbg = a.dbg;
-#else
-    constexpr int dbg = 0;
-#endif
     stage_example_rows(Es, a.in, a.idx, a.idxM, b, F, D, Dp, tid, NTH, a.idxStride);
     lds_barrier();
     // ---- step 1 -----------------------------------------------------------------------------------------------------
     // The kernel is instruction-issue-bound (with every load, MFMA and store switched off it still ran 11.6 of its 29.2 ms
-    // at F32 D64: tools/dbg_tile.py), and most of those instructions were the per-unit operand bookkeeping.  So the k index
+    // at F32 D64), and most of those instructions were the per-unit operand bookkeeping.  So the k index
     // runs over ALL fields, k = dw * F4 + j (F4 = F rounded up to 4): the E fragment of a k-step then does not depend on the
     // unit (16 LDS reads per WAVE instead of per unit), the W fragment is one load at a lane-constant offset from a
     // wave-uniform row pointer, and only the first k-quad of a unit (the one that contains j = i + 1) needs a mask.
@@ -3122,14 +3092,13 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_fwd_kernel(ConvArg
                 if (t == s0) {                                  // the quad that holds j = i + 1: lanes with j <= i are masked
                     const int j = 4 * t + kk;                   // (their address is moved onto the row of j = i + 1)
                     const float wv = wb[woff[ks] + (j > i ? 0 : (i + 1 - j) * PpT)];
-                    bw[ks] = (j > i && !(dbg & 2)) ? wv : ((dbg & 2) ? 1.f : 0.f);
+                    bw[ks] = j > i ? wv : 0.f;
                 } else {
-                    bw[ks] = (dbg & 2) ? 1.f : wb[woff[ks]];
+                    bw[ks] = wb[woff[ks]];
                 }
             }
         }
         f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (!(dbg & 4))
 #pragma unroll
         for (int ks = 0; ks < C0T_MAXKS; ++ks) {
             const int dwk = ks >= nq ? 1 : 0, t = ks - dwk * nq;
@@ -3153,7 +3122,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_fwd_kernel(ConvArg
         f32x4 acc[XQ];
 #pragma unroll
         for (int q4 = 0; q4 < XQ; ++q4) acc[q4] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int s2 = 0; s2 < ((dbg & 8) ? 0 : ks2); ++s2) {
+        for (int s2 = 0; s2 < ks2; ++s2) {
             const int k = 4 * s2 + kk;
             const bool ok = k < K2;
             const int dh = (ok && k >= F) ? 1 : 0, i = ok ? k - dh * F : 0;
@@ -3169,8 +3138,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_fwd_kernel(ConvArg
             for (int j = 0; j < 4; ++j) {
                 const int yy = rt * 16 + kk * 4 + j;
                 const float c = fmaxf(acc[q4][j] + bias, 0.f);
-                if (!(dbg & 1) || c == 12345.678f)
-                    a.out[(((int64_t)b * S + yy) * S + x0 + xg + q4) * PpT + q0 + r] = c;
+                a.out[(((int64_t)b * S + yy) * S + x0 + xg + q4) * PpT + q0 + r] = c;
                 ps[j] += act_pos(c, a.act);
             }
         if (a.pool != nullptr) {                                // pool partial of this (column tile, channel tile): over q in the DPP row
@@ -3331,8 +3299,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_wgrad_kernel(Wgrad
 // (global_load_lds: 16-byte pieces land at 16 x their index, which IS the dCt layout; one 4-byte piece per lane = one embedding
 // row per wave instruction at the padded pitch) into the other half of a double buffer while the current tile is computed: two
 // barriers per tile instead of three and no load latency in front of phase C.
-// GPW groups per workgroup (4: the tile is read once, 4 units per wavefront and 64 accumulation registers; 2: read twice, 2 units per
-// wavefront, 32 accumulation registers and nothing spilled under the 128-register budget of a 1024-thread workgroup)
+// GPW groups per workgroup: 4 (the tile is read once, 4 units per wavefront and 64 accumulation registers).  GPW = 2 (read twice,
+// 2 units per wavefront, 32 accumulation registers) was measured slower and is not built.
 template <int SMAX, int GPW>
 __global__ __launch_bounds__(1024) void conv0_fact_tile_wgrad_all_kernel(WgradArgs a, int nslab) {
     constexpr int NTH = 1024, WPG = 16 / GPW, UPW = 16 / WPG;   // wavefronts per group; units (and phase-C columns) per wavefront
@@ -3504,29 +3472,19 @@ __global__ __launch_bounds__(1024) void conv0_fact_tile_wgrad_all_kernel(WgradAr
 static int launch_conv0_fact_tile_wgrad(const WgradArgs& a, int nslab, hipStream_t st) {
     const int S = a.D / 2, G = (2 * a.F + 15) / 16;
     if (S > 32) return CFFM_ERR_UNSUPPORTED;
-    const char* ver = getenv("CFFM_TILE_WGRAD");                // debug: 1 = round-2 kernel, 2 = two groups per workgroup
-    if (G <= 4 && !(ver && ver[0] == '1')) {
-        if (!(ver && ver[0] == '2')) {
-            // all four groups in one workgroup of 16 wavefronts: the dC tile is staged ONCE per (example, column tile); 4 units per
-            // wavefront, 64 accumulation registers - 122 registers and nothing spilled since phase D stopped computing an operand
-            // address per MFMA (before: 31-49 spilled, slower than two groups)
-            const size_t lds = (size_t)(2 * ((a.F * (a.D + 1) + 3) / 4 * 4) + 2 * 32 * 256 + 4 * 16 * 256) * 4 + 16;
-            int rc = set_lds(conv0_fact_tile_wgrad_all_kernel<32, 4>, lds);
-            if (rc) return rc;
-            const int64_t grid = (int64_t)(a.Pp / 16) * nslab;
-            hipLaunchKernelGGL((conv0_fact_tile_wgrad_all_kernel<32, 4>), dim3((unsigned)grid), dim3(1024), lds, st, a, nslab);
-            CFFM_CHECK_LAUNCH();
-            return 0;
-        }
-        // two groups per workgroup: the tile is staged twice
-        const size_t lds = (size_t)(2 * ((a.F * (a.D + 1) + 3) / 4 * 4) + 2 * 32 * 256 + 2 * 16 * 256) * 4 + 16;
-        int rc = set_lds(conv0_fact_tile_wgrad_all_kernel<32, 2>, lds);
+    if (G <= 4) {
+        // all four groups in one workgroup of 16 wavefronts: the dC tile is staged ONCE per (example, column tile); 4 units per
+        // wavefront, 64 accumulation registers - 122 registers and nothing spilled since phase D stopped computing an operand
+        // address per MFMA (before: 31-49 spilled, slower than two groups)
+        const size_t lds = (size_t)(2 * ((a.F * (a.D + 1) + 3) / 4 * 4) + 2 * 32 * 256 + 4 * 16 * 256) * 4 + 16;
+        int rc = set_lds(conv0_fact_tile_wgrad_all_kernel<32, 4>, lds);
         if (rc) return rc;
-        const int64_t grid = (int64_t)(a.Pp / 16) * 2 * nslab;
-        hipLaunchKernelGGL((conv0_fact_tile_wgrad_all_kernel<32, 2>), dim3((unsigned)grid), dim3(1024), lds, st, a, nslab);
+        const int64_t grid = (int64_t)(a.Pp / 16) * nslab;
+        hipLaunchKernelGGL((conv0_fact_tile_wgrad_all_kernel<32, 4>), dim3((unsigned)grid), dim3(1024), lds, st, a, nslab);
         CFFM_CHECK_LAUNCH();
         return 0;
     }
+    // G > 4 (F = 33): one workgroup per group
     const size_t lds = (size_t)((a.F * (a.D + 1) + 3) / 4 * 4 + 32 * 256 + 16 * 256) * 4 + 16;
     constexpr int NW = 8;
     int rc = set_lds(conv0_fact_tile_wgrad_kernel<32, NW>, lds);
@@ -3544,237 +3502,9 @@ static int launch_conv0_fact_tile_wgrad(const WgradArgs& a, int nslab, hipStream
 // One workgroup per example walks (group g of 16 (dh,i) rows) x (column tile) x (channel tile); per step it stages the
 // dC tile, recomputes the 16 T planes and the 16 dT planes of the group in LDS and feeds two accumulators that live in
 // registers across the walk: dEi of the group (K split over the wavefronts, summed at the end of the group) and dEj
-// (each wavefront sums its own four units, summed at the very end).  ~325 MFLOP per example at F32 D64 against 2,015.
-template <int SMAX, int NW>
-__global__ __launch_bounds__(64 * NW) void conv0_fact_tile_dgrad_kernel(DgradArgs a) {
-    constexpr int NTH = 64 * NW, UPW = 16 / NW, KPW = 64 / NW;   // units / phase-C columns per wavefront, phase-B k-steps per wavefront
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int F = a.F, D = a.D, S = D / 2, Dp = D + 1, RT = S / 16, YT = S / 16, PpT = a.Pp, QT = PpT / 16, G = (2 * F + 15) / 16;
-    // LDS plan (74.6 KB at F32 D64: TWO workgroups per CU).  Phase B reads Tg and dCt with the LANE walking the plane /
-    // row index (m = r, y = yt*16 + r): with the natural pitch of 256 floats all sixteen lanes of a k group hit one bank
-    // (rocprofv3: SQ_LDS_BANK_CONFLICT = 82 % of SQ_LDS_IDX_ACTIVE, profiles/r02_syn1m_pmc.md).  Pitch 258 makes the Tg
-    // read conflict-free (bank = 2r + kk); dCt is staged in 16-byte pieces, so its pitch stays a multiple of 4: 260
-    // (bank = 4r + kk, 2-way).  The buffers of the epilogue (cross-wave partial sums, dEi / dEj) reuse Tg / dTg.
-    constexpr int TGP = 258, DCP = 260;
-    float* Es = reinterpret_cast<float*>(smem);                // [F][Dp]
-    float* dCt = Es + (F * Dp + 3) / 4 * 4;                    // [S][DCP]: (x, q) at x*16 + q
-    float* Tg = dCt + SMAX * DCP;                               // [16 m][TGP]
-    float* dTg = Tg + 16 * TGP;                                 // [16 m][16 x][16 q]  (16 * 258 floats keep it 16-byte aligned)
-    static_assert(NW * 4 * 256 <= 16 * TGP, "the cross-wave partial sums reuse Tg");
-    float* part = Tg;                                           // [NW waves][4 tiles][64 lanes][4]   cross-wave sums (epilogue)
-    float* dEi = dTg;                                           // [G*16][SMAX]    (n = dh*F + i, y)            (epilogue)
-    float* dEj = dEi + 64 * SMAX;                               // [64][SMAX]      (n = dw*F + j, x)            (epilogue)
-    float* rs = dTg + 4096;                                     // [F] row sums, [F] dots
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, kk = lane >> 4;
-    const int b = blockIdx.x;
-    stage_example_rows(Es, a.Cprev, a.idx, a.idxM, b, F, D, Dp, tid, NTH, a.idxStride);
-    f32x4 accE[2][4];                                          // [column tile][row tile of (dw,j)]
-#pragma unroll
-    for (int xt = 0; xt < 2; ++xt)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) accE[xt][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 accB[4][2];                                          // [row group g][y tile] x (16 rows of the group)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int yt = 0; yt < 2; ++yt) accB[g][yt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* dCb = a.dC + (int64_t)b * S * S * PpT;
-    // The dC tile of the NEXT (column tile, channel tile) is fetched into registers while the current one is worked on (two
-    // wavefronts per SIMD do not hide a global load that is issued and consumed in the same step: 4 of the 64 ms).  Measured and
-    // not kept: the filter slices of phase E requested two phases ahead as well (64 more registers: 256 with spills and
-    // scratch-resident operand arrays, 64 -> 104 ms).
-    constexpr int NX = SMAX * 64 / NTH;                        // 16-byte pieces of a tile per thread
-    static_assert(NX == 8, "the prefetch registers are eight named float4s (an array ends up in scratch memory here)");
-    float4 nx0, nx1, nx2, nx3, nx4, nx5, nx6, nx7;
-#define CFFM_TILE_FETCH(X0N, Q0N)                                                                                              \
-    do {                                                                                                                      \
-        const float* tb_ = dCb + (int64_t)(X0N) * PpT + (Q0N) + 4 * (tid & 3) + (int64_t)((tid >> 2) & 15) * PpT;              \
-        const int64_t ys_ = (int64_t)S * PpT;                  /* e4 = tid + u * 256: y = (tid >> 6) + 4u */                   \
-        const int y_ = tid >> 6;                                                                                              \
-        nx0 = *reinterpret_cast<const float4*>(tb_ + min(y_, S - 1) * ys_);                                                   \
-        nx1 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 4, S - 1) * ys_);                                               \
-        nx2 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 8, S - 1) * ys_);                                               \
-        nx3 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 12, S - 1) * ys_);                                              \
-        nx4 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 16, S - 1) * ys_);                                              \
-        nx5 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 20, S - 1) * ys_);                                              \
-        nx6 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 24, S - 1) * ys_);                                              \
-        nx7 = *reinterpret_cast<const float4*>(tb_ + min(y_ + 28, S - 1) * ys_);                                              \
-    } while (0)
-    static_assert(NTH == 256, "y = (tid >> 6) + 4u above");
-    CFFM_TILE_FETCH(0, 0);
-#pragma unroll
-    for (int xt = 0; xt < 2; ++xt) {
-        if (xt >= RT) continue;
-        const int x0 = xt * 16;
-        for (int qt = 0; qt < QT; ++qt) {
-            const int q0 = qt * 16;
-            __syncthreads();                                   // dCt / Tg / dTg of the previous step consumed
-            {                                                  // the dC tile is staged ONCE for the four row groups
-                float* tl_ = dCt + ((tid >> 2) & 15) * 16 + 4 * (tid & 3);
-                const int y_ = tid >> 6;
-                if (y_ < S) *reinterpret_cast<float4*>(tl_ + y_ * DCP) = nx0;
-                if (y_ + 4 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 4) * DCP) = nx1;
-                if (y_ + 8 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 8) * DCP) = nx2;
-                if (y_ + 12 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 12) * DCP) = nx3;
-                if (y_ + 16 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 16) * DCP) = nx4;
-                if (y_ + 20 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 20) * DCP) = nx5;
-                if (y_ + 24 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 24) * DCP) = nx6;
-                if (y_ + 28 < S) *reinterpret_cast<float4*>(tl_ + (y_ + 28) * DCP) = nx7;
-            }
-            {   // the next tile (clamped to the last one: a harmless re-read at the very end)
-                const bool nq = qt + 1 < QT, nxt = xt + 1 < RT;
-                CFFM_TILE_FETCH(nq ? x0 : (nxt ? x0 + 16 : x0), nq ? q0 + 16 : (nxt ? 0 : q0));
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (g >= G) continue;
-                const int mC = g * 16 + r;                      // phase C row of this lane
-                const bool mC_ok = mC < 2 * F;
-                const int dhC = mC_ok && mC >= F ? 1 : 0, iC = mC_ok ? mC - dhC * F : 0;
-                if (g > 0) __syncthreads();                    // Tg / dTg of the previous group consumed
-                // ---- A: T planes of this wave's four units ---------------------------------------------------------
-#pragma unroll
-                for (int u4 = 0; u4 < UPW; ++u4) {
-                    const int ml = wave * UPW + u4, m = g * 16 + ml;
-                    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    if (m < 2 * F) {
-                        const int dh = m >= F ? 1 : 0, i = m - dh * F;
-                        const int nj = F - 1 - i, K = 2 * nj, base = i * (2 * F - i - 1) / 2;
-                        float bw[C0T_MAXKS], av[C0T_MAXKS];
-#pragma unroll
-                        for (int ks = 0; ks < C0T_MAXKS; ++ks) {
-                            const int k = 4 * ks + kk;
-                            const bool ok = k < K;
-                            const int dw = (ok && k >= nj) ? 1 : 0, jj = ok ? k - dw * nj : 0;
-                            // (i = F-1 has no pairs: K = 0, base = P - keep the discarded reads inside W and Es)
-                            const float wv = a.W[((int64_t)(dh * 2 + dw) * PpT + min(base + jj, a.P - 1)) * PpT + q0 + r];
-                            const float ev = Es[min(i + 1 + jj, F - 1) * Dp + 2 * (x0 + r) + dw];
-                            bw[ks] = ok ? wv : 0.f;
-                            av[ks] = ok ? ev : 0.f;
-                        }
-                        // two straight chains instead of a test per MFMA (a branch and a full wait in front of each):
-                        // 64.2 ms against 68.7 with the tests and 67.9 with four chain lengths (F32 D64 B8192)
-                        if (K > 2 * C0T_MAXKS) {
-#pragma unroll
-                            for (int ks = 0; ks < C0T_MAXKS; ++ks) acc = mfma16(av[ks], bw[ks], acc);
-                        } else {
-#pragma unroll
-                            for (int ks = 0; ks < C0T_MAXKS / 2; ++ks) acc = mfma16(av[ks], bw[ks], acc);
-                        }
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) Tg[ml * TGP + (kk * 4 + j) * 16 + r] = acc[j];
-                }
-                if (g == 0) __syncthreads();                   // dCt staged
-                // ---- C: dT planes of the group, wave's columns 4*wave .. 4*wave+3 --------------------------------------
-                {
-                    f32x4 acc[UPW];
-#pragma unroll
-                    for (int xl = 0; xl < UPW; ++xl) acc[xl] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                    for (int s4 = 0; s4 < S / 4; ++s4) {
-                        const int y = 4 * s4 + kk;
-                        const float av = mC_ok ? Es[iC * Dp + 2 * y + dhC] : 0.f;
-#pragma unroll
-                        for (int xl = 0; xl < UPW; ++xl) acc[xl] = mfma16(av, dCt[y * DCP + (UPW * wave + xl) * 16 + r], acc[xl]);
-                    }
-#pragma unroll
-                    for (int xl = 0; xl < UPW; ++xl)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) dTg[((kk * 4 + j) * 16 + UPW * wave + xl) * 16 + r] = acc[xl][j];
-                }
-                __syncthreads();                               // Tg and dTg written
-                // ---- B: dEi of the group: rows y, K = (x,q) of this tile (64 k-steps, 16 per wave), cols m -----------------
-                for (int ks = 0; ks < KPW; ++ks) {
-                    const int kf = 4 * (wave * KPW + ks) + kk, x = kf >> 4, q = kf & 15;
-                    const float bv = Tg[r * TGP + x * 16 + q];
-#pragma unroll
-                    for (int yt = 0; yt < 2; ++yt)
-                        if (yt < YT) accB[g][yt] = mfma16(dCt[(yt * 16 + r) * DCP + x * 16 + q], bv, accB[g][yt]);
-                }
-                // ---- E: dEj rows (dw,j), K = q, cols x: this wave's four units ------------------------------------------
-#pragma unroll
-                for (int u4 = 0; u4 < UPW; ++u4) {
-                    const int ml = wave * UPW + u4, m = g * 16 + ml;
-                    if (m >= 2 * F) continue;
-                    const int dh = m >= F ? 1 : 0, i = m - dh * F, base = i * (2 * F - i - 1) / 2;
-                    const float4 bv = *reinterpret_cast<const float4*>(dTg + (ml * 16 + r) * 16 + 4 * kk);   // [k = q = 4kk+t][n = x = r]
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const int n = t * 16 + r, dw = n >= F ? 1 : 0, j = n - dw * F;
-                        // the tile is empty when none of its rows has j > i (wave-uniform test on the tile's last rows)
-                        const int jmax_lo = min(F - 1, t * 16 + 15), jmax_hi = t * 16 + 15 - F;
-                        const bool any = (t * 16 < F && jmax_lo > i) || (t * 16 + 15 >= F && jmax_hi > i && t * 16 < 2 * F);
-                        if (!any) continue;
-                        const bool ok = n < 2 * F && j > i;
-                        const int jc = ok ? j - i - 1 : 0, dwc = ok ? dw : 0;            // clamped row, zeroed by the select
-                        float4 wv = *reinterpret_cast<const float4*>(a.W + ((int64_t)(dh * 2 + dwc) * PpT + base + jc) * PpT + q0 + 4 * kk);
-                        if (!ok) wv = make_float4(0.f, 0.f, 0.f, 0.f);
-                        accE[xt][t] = mfma16(wv.x, bv.x, accE[xt][t]);
-                        accE[xt][t] = mfma16(wv.y, bv.y, accE[xt][t]);
-                        accE[xt][t] = mfma16(wv.z, bv.z, accE[xt][t]);
-                        accE[xt][t] = mfma16(wv.w, bv.w, accE[xt][t]);
-                    }
-                }
-            }
-        }
-    }
-    // ---- dEi: sum the four wavefronts' K slices, group by group -------------------------------------------------------
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        if (g >= G) continue;
-        __syncthreads();
-#pragma unroll
-        for (int yt = 0; yt < 2; ++yt)
-            *reinterpret_cast<f32x4*>(part + ((wave * 4 + yt) * 64 + lane) * 4) = accB[g][yt];
-        __syncthreads();
-        for (int e = tid; e < YT * 256; e += NTH) {              // e = (yt, lane, j)
-            const int j = e & 3, ln = (e >> 2) & 63, yt = e >> 8;
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v += part[((w * 4 + yt) * 64 + ln) * 4 + j];
-            const int y = yt * 16 + (ln >> 4) * 4 + j, mm = g * 16 + (ln & 15);          // D layout: row y, col m
-            dEi[mm * SMAX + y] = v;
-        }
-    }
-    // ---- dEj: sum the four wavefronts' unit subsets -----------------------------------------------------------------
-#pragma unroll
-    for (int xt = 0; xt < 2; ++xt) {
-        if (xt >= RT) continue;
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < 4; ++t) *reinterpret_cast<f32x4*>(part + ((wave * 4 + t) * 64 + lane) * 4) = accE[xt][t];
-        __syncthreads();
-        for (int e = tid; e < 4 * 256; e += NTH) {              // e = (t, lane, j)
-            const int j = e & 3, ln = (e >> 2) & 63, t = e >> 8;
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) v += part[((w * 4 + t) * 64 + ln) * 4 + j];
-            const int n = t * 16 + (ln >> 4) * 4 + j, x = xt * 16 + (ln & 15);           // D layout: row (dw,j), col x
-            dEj[n * SMAX + x] = v;
-        }
-    }
-    if (tid < 2 * F) {                                           // row sums and <ds0, E[f]> for the closed-form s0 terms
-        const int f = tid % F;
-        float sacc = 0.f;
-        if (tid < F) { for (int h = 0; h < D; ++h) sacc += Es[f * Dp + h]; }
-        else { for (int h = 0; h < D; ++h) sacc += Es[f * Dp + h] * a.dt1[(int64_t)b * a.t1w + h]; }
-        rs[tid] = sacc;
-    }
-    __syncthreads();
-    for (int e = tid; e < F * D; e += NTH) {
-        const int f = e / D, h = e - f * D, lo = h & 1, hh = h >> 1;
-        float R = 0.f, Q = 0.f;
-        for (int j = f + 1; j < F; ++j) R += rs[j];
-        for (int i = 0; i < f; ++i) Q += rs[F + i];
-        a.dprev[(int64_t)b * F * D + e] = (dEi[(lo * F + f) * SMAX + hh] + dEj[(lo * F + f) * SMAX + hh])
-                                          + a.dt1[(int64_t)b * a.t1w + h] * R + Q;
-    }
-}
-
-#undef CFFM_TILE_FETCH
-
-// ---- the same input gradient with the filter read as PRE-PACKED MFMA fragments ------------------------------------------
-// rocprofv3 + the ISA of the kernel above: 19.7 K instructions for 784 MFMAs - per MFMA of phases A and E a dozen integer
+// (each wavefront sums its own units, summed at the very end).  ~325 MFLOP per example at F32 D64 against 2,015.
+// The filter is read as PRE-PACKED MFMA fragments.  rocprofv3 + the ISA of round 2's kernel, which read it element by element
+// from the filter itself: 19.7 K instructions for 784 MFMAs - per MFMA of phases A and E a dozen integer
 // instructions of (pair, tap) address arithmetic, two selects and a 64-bit multiply-add, unrolled over 4 row groups x 2 column
 // tiles (an instruction stream larger than the instruction cache); MFMA pipe busy 30 %.  Here the layer-0 filter is laid out
 // ONCE per backward pass (pack_w0_tile_kernel, 16 MB written, a few us) exactly as the two phases consume it:
@@ -3810,6 +3540,10 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_dgrad2_kernel(Dgra
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int F = a.F, D = a.D, S = D / 2, Dp = D + 1, RT = S / 16, YT = S / 16, PpT = a.Pp, QT = PpT / 16, G = (2 * F + 15) / 16;
     const int CE = (F + 3) / 4, Fp = 4 * CE, NTE = (2 * F + 15) / 16;
+    // Phase B reads Tg and dCt with the LANE walking the plane / row index (m = r, y = yt*16 + r): with the natural pitch of
+    // 256 floats all sixteen lanes of a k group hit one bank (rocprofv3: SQ_LDS_BANK_CONFLICT = 82 % of SQ_LDS_IDX_ACTIVE,
+    // profiles/r02_syn1m_pmc.md).  Pitch 258 makes the Tg read conflict-free (bank = 2r + kk); dCt is staged in 16-byte
+    // pieces, so its pitch stays a multiple of 4: 260 (bank = 4r + kk, 2-way).
     constexpr int TGP = 258, DCP = 260;
     float* Es = reinterpret_cast<float*>(smem);                // [Fp + 1][Dp], rows F .. Fp zero (Fp: the row of lanes without a unit)
     float* dCt = Es + ((Fp + 1) * Dp + 3) / 4 * 4;             // [S][DCP]: (x, q) at x*16 + q
@@ -4094,8 +3828,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_dgrad2_kernel(Dgra
     }
 }
 
-template <int NW>
-static int launch_conv0_fact_tile_dgrad2(const DgradArgs& a, float* wpack, hipStream_t st) {
+static int launch_conv0_fact_tile_dgrad(const DgradArgs& a, float* wpack, hipStream_t st) {
+    constexpr int NW = 4;
+    if (wpack == nullptr || a.F > 32 || a.D / 2 > 32) return CFFM_ERR_UNSUPPORTED;   // ws.w0pack exists iff conv0_tile_dgrad2_ok
     const int QT = a.Pp / 16, CE = (a.F + 3) / 4;
     float* WA = wpack;
     float4* WE = reinterpret_cast<float4*>(wpack + (int64_t)2 * a.F * QT * 1024);
@@ -4106,25 +3841,6 @@ static int launch_conv0_fact_tile_dgrad2(const DgradArgs& a, float* wpack, hipSt
     int rc = set_lds(conv0_fact_tile_dgrad2_kernel<32, NW>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((conv0_fact_tile_dgrad2_kernel<32, NW>), dim3(a.B), dim3(64 * NW), lds, st, a, (const float*)WA, (const float4*)WE);
-    CFFM_CHECK_LAUNCH();
-    return 0;
-}
-
-static int launch_conv0_fact_tile_dgrad(const DgradArgs& a, hipStream_t st, float* wpack = nullptr) {
-    const char* ver = getenv("CFFM_TILE_DGRAD");                // debug: 1 = the round-2 kernel, 8 = packed fragments with 8 wavefronts
-    if (wpack != nullptr && a.F <= 32 && a.D / 2 <= 32 && !(ver && ver[0] == '1')) {
-        if (ver && ver[0] == '8') return launch_conv0_fact_tile_dgrad2<8>(a, wpack, st);
-        return launch_conv0_fact_tile_dgrad2<4>(a, wpack, st);
-    }
-
-    const int S = a.D / 2;
-    if (S > 32 || 2 * a.F > 64) return CFFM_ERR_UNSUPPORTED;
-    constexpr int NW = 4;                // measured at F32 D64 B8192: 118 ms with 4 wavefronts, 194 ms with 8 (register spills)
-    // Es | dCt [32][260] | Tg [16][258] | dTg [4096] | rs [2F]
-    const size_t lds = (size_t)((a.F * (a.D + 1) + 3) / 4 * 4 + 32 * 260 + 16 * 258 + 4096 + 2 * a.F) * 4 + 16;
-    int rc = set_lds(conv0_fact_tile_dgrad_kernel<32, NW>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv0_fact_tile_dgrad_kernel<32, NW>), dim3(a.B), dim3(64 * NW), lds, st, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -4309,10 +4025,7 @@ static int launch_conv0_fact_tile_fwd2(const ConvArgs& a, float* wpack, hipStrea
 }
 
 static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st, float* wpack = nullptr) {
-    {
-        const char* ver = getenv("CFFM_TILE_FWD");              // debug: 1 = the round-2 kernel (a workgroup per tile)
-        if (wpack != nullptr && a.F <= 32 && a.D / 2 <= 32 && !(ver && ver[0] == '1')) return launch_conv0_fact_tile_fwd2(a, wpack, st);
-    }
+    if (wpack != nullptr && a.F <= 32 && a.D / 2 <= 32) return launch_conv0_fact_tile_fwd2(a, wpack, st);
 
     constexpr int NW = 8;                // measured at F32 D64 B8192: 38.6 ms with 4 wavefronts, 29.2 with 8, 36.6 with 16 (one workgroup per CU)
     const int S = a.D / 2;
@@ -4321,13 +4034,7 @@ static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st, float* 
     if (rc) return rc;
     const int64_t grid = (int64_t)a.B * (a.Pp / 16) * (S / 16);
     if (grid > 0x7fffffffll) return CFFM_ERR_UNSUPPORTED;
-#ifdef CFFM_TILE_DBG
-    ConvArgs b = a;
-    b.dbg = getenv("CFFM_DBG") ? atoi(getenv("CFFM_DBG")) : 0;
-    hipLaunchKernelGGL((conv0_fact_tile_fwd_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), lds, st, b);
-#else
     hipLaunchKernelGGL((conv0_fact_tile_fwd_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), lds, st, a);
-#endif
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -4368,19 +4075,21 @@ static int launch_conv0_fact_bwd(const DgradArgs& a, float* slabW, float* slabB,
     constexpr int PP = NT * 16;
     constexpr int NW = 16;
     const size_t lds = conv0_fact_bwd_lds(PP, a.F, a.D);
-#define CFFM_C0B_LAUNCH(FV, DV)                                                                                  \
-    do {                                                                                                         \
-        int rc = set_lds(conv0_fact_bwd_kernel<NT, FV, DV, NW>, lds);                                                \
-        if (rc) return rc;                                                                                       \
-        hipLaunchKernelGGL((conv0_fact_bwd_kernel<NT, FV, DV, NW>), dim3(nsl), dim3(64 * NW), lds, st, a, slabW, slabB, stride); \
-    } while (0)
-    if (NT == 3 && a.F == 10 && a.D == 32) CFFM_C0B_LAUNCH(10, 32);          // frappe        (README.md:28)
-    else if (NT == 1 && a.F == 6 && a.D == 32) CFFM_C0B_LAUNCH(6, 32);       // book-crossing (README.md:20)
-    else if (NT == 1 && a.F == 3 && a.D == 32) CFFM_C0B_LAUNCH(3, 32);       // ml-tag        (README.md:24)
-    else CFFM_C0B_LAUNCH(0, 0);
-#undef CFFM_C0B_LAUNCH
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    auto go = [&](auto fv, auto dv) {          // (F, D) compiled in for the README shapes, (0, 0): read at run time
+        constexpr int FV = decltype(fv)::value, DV = decltype(dv)::value;
+        int rc = set_lds(conv0_fact_bwd_kernel<NT, FV, DV, NW>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((conv0_fact_bwd_kernel<NT, FV, DV, NW>), dim3(nsl), dim3(64 * NW), lds, st, a, slabW, slabB, stride);
+        CFFM_CHECK_LAUNCH();
+        return 0;
+    };
+    if constexpr (NT == 3) {
+        if (a.F == 10 && a.D == 32) return go(IntC<10>(), IntC<32>());     // frappe        (README.md:28)
+    } else if constexpr (NT == 1) {
+        if (a.F == 6 && a.D == 32) return go(IntC<6>(), IntC<32>());       // book-crossing (README.md:20)
+        if (a.F == 3 && a.D == 32) return go(IntC<3>(), IntC<32>());       // ml-tag        (README.md:24)
+    }
+    return go(IntC<0>(), IntC<0>());
 }
 
 template <int NT, int RM, bool L0, int HALVES>
@@ -4448,21 +4157,15 @@ static int launch_conv_bwd_pair(const DgradArgs& d, const WgradArgs& w, int nsl,
     const int first_w = ib ? n_i : 0, first_d = first_w + nsl + tw.n[0] + tw.n[1];
     const int xcd_align = (nsl == d.B && (int64_t)nsl * S2 == d.Mtot && S2 % BM == 0 && d.B % 8 == 0 && first_w % 8 == 0 &&
                            first_d % 8 == 0) ? 1 : 0;
-    // activation compiled in for the README commands (see launch_fwd_all)
-#define PAIR_GO(ACT_)                                                                                                          \
-    do {                                                                                                                        \
-        int rc_ = set_lds(conv_bwd_pair_kernel<NT, RM, ACT_>, lds);                                                             \
-        if (rc_) return rc_;                                                                                                    \
-        hipLaunchKernelGGL((conv_bwd_pair_kernel<NT, RM, ACT_>), dim3(n_d + nsl + (ib ? n_i : 0) + tw.n[0] + tw.n[1]), dim3(256), \
-                           lds, st, d, w, n_d, nsl, ib ? *ib : none, ib ? n_i : 0, tw, xcd_align);                              \
-    } while (0)
-    if (NT == 3 && d.act == CFFM_ACT_SELU) PAIR_GO(CFFM_ACT_SELU);
-    else if (NT == 1 && d.act == CFFM_ACT_ELU) PAIR_GO(CFFM_ACT_ELU);
-    else if (NT == 1 && d.act == CFFM_ACT_RELU) PAIR_GO(CFFM_ACT_RELU);
-    else PAIR_GO(-1);
-#undef PAIR_GO
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return with_readme_act<NT>(d.act, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        int rc = set_lds(conv_bwd_pair_kernel<NT, RM, ACT>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((conv_bwd_pair_kernel<NT, RM, ACT>), dim3(n_d + nsl + (ib ? n_i : 0) + tw.n[0] + tw.n[1]), dim3(256),
+                           lds, st, d, w, n_d, nsl, ib ? *ib : none, ib ? n_i : 0, tw, xcd_align);
+        CFFM_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 static inline int64_t layer_rows(const Geo& g, int B, int l, int* lgSo) {
@@ -4527,11 +4230,11 @@ static int conv_fwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
     pick_nt(g.Pp / 16, &nblk, &NT);
     const bool big = a.Mtot >= 128 * 256;
     if (l == 0) {
-        if (big) { DISPATCH_NT(NT, rc = (launch_conv_fwd<NT_, 2, true>(a, nblk, st))); }
-        else { DISPATCH_NT(NT, rc = (launch_conv_fwd<NT_, 1, true>(a, nblk, st))); }
+        if (big) { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 2, true>(a, nblk, st))); }
+        else { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 1, true>(a, nblk, st))); }
     } else {
-        if (big) { DISPATCH_NT(NT, rc = (launch_conv_fwd<NT_, 2, false>(a, nblk, st))); }
-        else { DISPATCH_NT(NT, rc = (launch_conv_fwd<NT_, 1, false>(a, nblk, st))); }
+        if (big) { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 2, false>(a, nblk, st))); }
+        else { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 1, false>(a, nblk, st))); }
     }
     return rc;
 }
@@ -4568,20 +4271,14 @@ static void fill_taps_bwd_args(const cffm_shape_t* s, const float* theta, void* 
 
 template <int NT>
 static int launch_bwd_top(const BwdTopArgs& a, size_t lds, hipStream_t st) {
-    const int act = a.hb.g.act;
-#define TOP_GO(ACT_)                                                                                          \
-    do {                                                                                                       \
-        int rc_ = set_lds(bwd_top_kernel<NT, ACT_>, lds);                                                      \
-        if (rc_) return rc_;                                                                                   \
-        hipLaunchKernelGGL((bwd_top_kernel<NT, ACT_>), dim3(a.n_inner + a.n_keys + 256), dim3(256), lds, st, a); \
-    } while (0)
-    if (NT == 3 && act == CFFM_ACT_SELU) TOP_GO(CFFM_ACT_SELU);
-    else if (NT == 1 && act == CFFM_ACT_ELU) TOP_GO(CFFM_ACT_ELU);
-    else if (NT == 1 && act == CFFM_ACT_RELU) TOP_GO(CFFM_ACT_RELU);
-    else TOP_GO(-1);
-#undef TOP_GO
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return with_readme_act<NT>(a.hb.g.act, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        int rc = set_lds(bwd_top_kernel<NT, ACT>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((bwd_top_kernel<NT, ACT>), dim3(a.n_inner + a.n_keys + 256), dim3(256), lds, st, a);
+        CFFM_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 // head backward + the top conv layers (+ the inner-branch backward) in one launch; *next_layer receives the highest
@@ -4710,10 +4407,10 @@ static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
             rc = launch_conv0_fact_tile_wgrad(a, sr.nslab, st);
         }
         else if (l == 0 && rs) { rc = CFFM_ERR_UNSUPPORTED; }
-        else if (l == 0) { DISPATCH_NT(NT, rc = (launch_wgrad<NT_, true>(a, st))); }
+        else if (l == 0) { DISPATCH_NT68(NT, rc = (launch_wgrad<NT_>(a, st))); }
         else if (NT == 8) { rc = launch_wgrad2<8>(a, st); }               // 128 x 128 output tile per workgroup
         else if (NT == 6) { rc = launch_wgrad2<6>(a, st); }               // 128 x 96
-        else { DISPATCH_NT(NT, rc = (launch_wgrad<NT_, false>(a, st))); }
+        else { rc = CFFM_ERR_UNSUPPORTED; }
         if (rc) return rc;
         }
     }
@@ -4725,11 +4422,8 @@ static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
         a.dt1 = (const float*)(w + wl.dt1);
         a.dprev = (float*)(w + (l == 0 ? wl.dEo : wl.dC[l - 1]));
         if (l >= 1 && wl.wb3_bytes > 0) a.wb3 = (void*)(w + wl.wb3);
-        {   // wide shapes: the relu mask the forward of layer l-1 left (1/32 of the bytes of C_{l-1})
-            const char* oldfwd = getenv("CFFM_TILE_FWD");
-            if (l >= 1 && wl.relu0 > 0 && !(l == 1 && oldfwd && oldfwd[0] == '1') && !getenv("CFFM_DGRAD_NO_MASK"))
-                a.relu = (const uint16_t*)(w + wl.relu0 + relu_mask_off(g, B, l - 1));
-        }
+        if (l >= 1 && wl.relu0 > 0)           // wide shapes: the relu mask the forward of layer l-1 left (1/32 of the bytes of C_{l-1})
+            a.relu = (const uint16_t*)(w + wl.relu0 + relu_mask_off(g, B, l - 1));
         a.Mtot = layer_rows(g, B, l, &a.lgSo);
         a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
         a.t1w = 2 * g.D - 2; a.t1off = t1_offset(g, l);
@@ -4746,20 +4440,16 @@ static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
             else { DISPATCH_NT4(nt4, rc = (launch_dgrad_taps<NT_, 1, false, 1>(a, st))); }
             return rc;
         }
-        if (l == 0 && conv0_fact_tile_ok(g) && g.D / 2 <= 32 && 2 * g.F <= 64) {
+        if (l == 0 && conv0_tile_dgrad2_ok(g)) {
             if (rs) { a.Cprev = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }
-            return launch_conv0_fact_tile_dgrad(a, st, wl.w0pack_floats > 0 ? (float*)(w + wl.w0pack) : nullptr);
+            return launch_conv0_fact_tile_dgrad(a, wl.w0pack_floats > 0 ? (float*)(w + wl.w0pack) : nullptr, st);
         }
         if (l == 0 && rs) return CFFM_ERR_UNSUPPORTED;
         pick_nt(4 * g.Pp / 16, &nblk, &NT);
+        if (NT != 8) return CFFM_ERR_UNSUPPORTED;                    // see DISPATCH_NT68
         const bool big = a.Mtot >= 128 * 256;
-        if (l == 0) {
-            if (big) { DISPATCH_NT(NT, rc = (launch_dgrad<NT_, 2, true>(a, nblk, st))); }
-            else { DISPATCH_NT(NT, rc = (launch_dgrad<NT_, 1, true>(a, nblk, st))); }
-        } else {
-            if (big) { DISPATCH_NT(NT, rc = (launch_dgrad<NT_, 2, false>(a, nblk, st))); }
-            else { DISPATCH_NT(NT, rc = (launch_dgrad<NT_, 1, false>(a, nblk, st))); }
-        }
+        if (l == 0) rc = big ? launch_dgrad<8, 2, true>(a, nblk, st) : launch_dgrad<8, 1, true>(a, nblk, st);
+        else rc = big ? launch_dgrad<8, 2, false>(a, nblk, st) : launch_dgrad<8, 1, false>(a, nblk, st);
     }
     return rc;
 }
@@ -4893,22 +4583,14 @@ bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B) {
 template <int NT>
 static int launch_fwd_all(const FwdAllArgs& fa, size_t lds, hipStream_t st) {
     constexpr int NW = 8;
-    // the three README commands get their activation compiled in: frappe = selu at Pp 48, ml-tag = elu and book-crossing =
-    // relu at Pp 16 (README.md:20-28)
-    const int act = fa.inner.g.act;
-#define FWD_ALL_GO(ACT_)                                                                                              \
-    do {                                                                                                               \
-        int rc_ = set_lds(fwd_all_kernel<NT, NW, ACT_>, lds);                                                          \
-        if (rc_) return rc_;                                                                                           \
-        hipLaunchKernelGGL((fwd_all_kernel<NT, NW, ACT_>), dim3(fa.B < 256 ? fa.B : 256), dim3(64 * NW), lds, st, fa); \
-    } while (0)
-    if (NT == 3 && act == CFFM_ACT_SELU) FWD_ALL_GO(CFFM_ACT_SELU);
-    else if (NT == 1 && act == CFFM_ACT_ELU) FWD_ALL_GO(CFFM_ACT_ELU);
-    else if (NT == 1 && act == CFFM_ACT_RELU) FWD_ALL_GO(CFFM_ACT_RELU);
-    else FWD_ALL_GO(-1);
-#undef FWD_ALL_GO
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return with_readme_act<NT>(fa.inner.g.act, [&](auto act) {
+        constexpr int ACT = decltype(act)::value;
+        int rc = set_lds(fwd_all_kernel<NT, NW, ACT>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((fwd_all_kernel<NT, NW, ACT>), dim3(fa.B < 256 ? fa.B : 256), dim3(64 * NW), lds, st, fa);
+        CFFM_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 int cffm_fwd_all_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,

@@ -61,7 +61,7 @@ int cffm_inner_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int
     int rc = check_shape(s);
     if (rc) return rc;
     if (B <= 0 || !s->inner_conv) return 0;
-    if (cffm_wide_regather_ok(s) && !getenv("CFFM_INNER_BWD_V1")) return cffm_inner_bwd_wide(s, theta, ws, B, rs, stream);
+    if (cffm_wide_regather_ok(s)) return cffm_inner_bwd_wide(s, theta, ws, B, rs, stream);
     cffm_theta_layout_t tl; cffm_ws_layout_t wl;
     cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
     const Geo g = make_geo(s);
@@ -548,11 +548,6 @@ static int launch_giw1(const GatherInnerWideArgs& a, int grid, size_t lds, hipSt
 template <int K2, int UPT>
 static int launch_giw(const GatherInnerWideArgs& a, int grid, size_t lds, hipStream_t st) {
     if (K2 == 32 && UPT == 16 && a.F == 32 && a.D == 64) {          // BASELINE configs[3] / [4]: F32 K64 D64
-        static const bool v3 = getenv("CFFM_GIW_V3") != nullptr;     // A/B runs: round 3's row-major pair assignment, 10 VALU per unit
-        if (v3) {
-            if (a.act == CFFM_ACT_RELU) return launch_giw1<32, 16, CFFM_ACT_RELU, 32>(a, grid, lds, st);
-            return launch_giw1<32, 16, -1, 32>(a, grid, lds, st);
-        }
         if (a.act == CFFM_ACT_RELU) return launch_giw1<32, 16, CFFM_ACT_RELU, 32, true>(a, grid, lds, st);
         return launch_giw1<32, 16, -1, 32, true>(a, grid, lds, st);
     }
@@ -577,7 +572,6 @@ bool cffm_giw_lds_ok() {
 #define GIW_CHK2(K2, UPT) chk((const void*)gather_inner_fwd_wide_kernel<K2, UPT, CFFM_ACT_RELU, 0>); chk((const void*)gather_inner_fwd_wide_kernel<K2, UPT, -1, 0>)
     GIW_CHK2(32, 4); GIW_CHK2(32, 8); GIW_CHK2(32, 16); GIW_CHK2(16, 4); GIW_CHK2(16, 8); GIW_CHK2(16, 16);
 #undef GIW_CHK2
-    chk((const void*)gather_inner_fwd_wide_kernel<32, 16, CFFM_ACT_RELU, 32>); chk((const void*)gather_inner_fwd_wide_kernel<32, 16, -1, 32>);
     chk((const void*)gather_inner_fwd_wide_kernel<32, 16, CFFM_ACT_RELU, 32, true>); chk((const void*)gather_inner_fwd_wide_kernel<32, 16, -1, 32, true>);
     if (asked) cached = ok ? 1 : 0;
     return ok;
