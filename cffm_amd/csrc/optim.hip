@@ -493,6 +493,7 @@ extern "C" int cffm_dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, co
                              int64_t n_rows, void* ws, int32_t B_ws, float* loss_out, int32_t n_runs, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
+    if (s->optimizer != CFFM_OPT_ADAGRAD) return CFFM_ERR_UNSUPPORTED;    // the data-parallel update is Adagrad only
     hipStream_t st = (hipStream_t)stream;
     cffm_theta_layout_t tl;
     cffm_theta_layout(s, &tl);
@@ -652,6 +653,7 @@ extern "C" int cffm_dp_apply_dense(const cffm_shape_t* s, const cffm_tables_t* t
                                    float* theta_acc, float* flat_sum, int64_t B_global, float* loss_out, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
+    if (s->optimizer != CFFM_OPT_ADAGRAD) return CFFM_ERR_UNSUPPORTED;    // as cffm_dp_apply
     if (!s->inner_conv || !s->outer_conv) return CFFM_ERR_UNSUPPORTED;
     cffm_theta_layout_t tl;
     cffm_theta_layout(s, &tl);

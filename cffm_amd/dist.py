@@ -60,6 +60,15 @@ def replicas_agree(compute, group=None, tables=False):
     return bool(torch.equal(lo, hi))
 
 
+def require_adagrad(compute, who):
+    """The data-parallel updates (cffm_dp_apply, cffm_dp_apply_dense and the CPU stand-ins) implement Adagrad only: refuse
+    any other optimizer of a compute that carries a config, before the first collective."""
+    cfg = getattr(compute, 'cfg', None)
+    opt = getattr(cfg, 'optimizer', 'AdagradOptimizer') if cfg is not None else 'AdagradOptimizer'
+    if opt != 'AdagradOptimizer':
+        raise ValueError('%s: the multi-GPU update is Adagrad only; --optimizer %s runs on one GPU' % (who, opt))
+
+
 class DataParallelStep(object):
     """Two collectives per step.  The loss normaliser 1/L (CFFM.py:493) needs the loss-term sum over the GLOBAL
     batch; instead of a separate scalar all-reduce between forward and backward, the backward pass runs with
@@ -72,6 +81,7 @@ class DataParallelStep(object):
     Every rank applies the same update to its replica, so the replicas stay bit-identical."""
 
     def __init__(self, compute, group=None, use_graph=False, mode='auto', sync=True):
+        require_adagrad(compute, 'DataParallelStep')
         self.c = compute
         self.group = group
         self.world = dist.get_world_size(group)
@@ -283,6 +293,7 @@ class ShardedStep(object):
     CPU tests."""
 
     def __init__(self, compute, group=None, dedup=True, sync=True, M_global=None):
+        require_adagrad(compute, 'ShardedStep')
         self.c = compute
         self.group = group
         self.world = dist.get_world_size(group)

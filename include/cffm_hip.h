@@ -238,7 +238,9 @@ int cffm_dp_apply_dense(const cffm_shape_t *s, const cffm_tables_t *tab, const c
  * n_runs = 0 takes rows [n_rows][1+K+D+1] in any order and sorts the keys itself; with n_runs > 0 rows is the
  * concatenation of n_runs cffm_dp_local buffers (n_rows / n_runs slots each): the sorted runs are merged by rank
  * (binary searches in LDS) instead of a radix sort of all n_rows keys.  cffm_dp_apply takes
- * the all-reduced grad and the all-gathered rows, applies 1/L and the dense + sparse Adagrad updates. */
+ * the all-reduced grad and the all-gathered rows, applies 1/L and the dense + sparse Adagrad updates.  Both data-parallel
+ * updates (cffm_dp_apply, cffm_dp_apply_dense) are Adagrad only: any other s->optimizer returns CFFM_ERR_UNSUPPORTED
+ * before a pointer is read. */
 int cffm_backward_unscaled(const cffm_shape_t *s, const float *theta, const int32_t *ids, const float *y, int32_t B,
                            int64_t B_global, void *ws, float *grad, float *rows, void *stream);
 int cffm_dp_apply(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *acc, float *theta,

@@ -408,8 +408,14 @@ def _dense_table_grad(p, name, ids, rows):
     return g
 
 
-def apply_optimizer(p, st, g, X, cfg):
+TF_CONSTS = dict(b1=0.9, b2=0.999, omb1=1 - 0.9, omb2=1 - 0.999, eps=1e-8, mom=0.95, lr_t=None)
+
+
+def apply_optimizer(p, st, g, X, cfg, consts=None):
+    """``consts`` overrides entries of TF_CONSTS (oracle/update_check.py passes the constants as the device rounds them;
+    ``lr_t``: a function of the step t in place of lr * sqrt(1 - b2^t) / (1 - b1^t))."""
     opt, lr = cfg.optimizer, cfg.lr
+    c = dict(TF_CONSTS, **(consts or {}))
     ids = np.asarray(X).reshape(-1)
     dense = {k: np.asarray(v).reshape(np.shape(p[k])) for k, v in g.items() if not k.startswith('d_') and not k.startswith('_')}
     tabs = {'inner_embeddings': g.get('d_inner_rows'), 'outer_embeddings': g.get('d_outer_rows'), 'feature_bias': g['d_bias_rows']}
@@ -423,21 +429,21 @@ def apply_optimizer(p, st, g, X, cfg):
             tabs[k] = None
     if opt == 'AdamOptimizer':
         st['t'] += 1
-        b1, b2, eps, t = 0.9, 0.999, 1e-8, st['t']
-        lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+        b1, b2, eps, t = c['b1'], c['b2'], c['eps'], st['t']
+        lr_t = c['lr_t'](t) if c['lr_t'] is not None else lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
         for k, rows in tabs.items():
             if rows is not None:
                 dense[k] = _dense_table_grad(p, k, ids, rows)          # every row takes part (zero gradient elsewhere)
         for k, gk in dense.items():
-            st['m'][k] = b1 * st['m'][k] + (1 - b1) * gk
-            st['v'][k] = b2 * st['v'][k] + (1 - b2) * gk * gk
+            st['m'][k] = b1 * st['m'][k] + c['omb1'] * gk
+            st['v'][k] = b2 * st['v'][k] + c['omb2'] * gk * gk
             p[k] = p[k] - lr_t * st['m'][k] / (np.sqrt(st['v'][k]) + eps)
         return
     for k, gk in dense.items():
         if opt == 'GradientDescentOptimizer':
             p[k] = p[k] - lr * gk
         else:                                                          # Momentum
-            st['acc'][k] = 0.95 * st['acc'][k] + gk
+            st['acc'][k] = c['mom'] * st['acc'][k] + gk
             p[k] = p[k] - lr * st['acc'][k]
     for k, rows in tabs.items():
         if rows is None:
@@ -448,7 +454,7 @@ def apply_optimizer(p, st, g, X, cfg):
         if opt == 'GradientDescentOptimizer':
             p[k][uniq] = p[k][uniq] - lr * summed
         else:
-            a = 0.95 * st['acc'][k][uniq] + summed
+            a = c['mom'] * st['acc'][k][uniq] + summed
             st['acc'][k][uniq] = a
             p[k][uniq] = p[k][uniq] - lr * a
 

@@ -91,6 +91,20 @@ def test_bad_shapes_are_rejected(lib):
     assert hip.make_shape(CFFMConfig(M=10, F=3, loss_type='hybrid')).loss == 5
 
 
+def test_data_parallel_updates_refuse_other_optimizers(lib):
+    """cffm_dp_apply and cffm_dp_apply_dense are Adagrad only: any other optimizer is refused right after the shape check,
+    before a pointer is read (every pointer here is NULL) or a kernel is launched; an Adagrad shape gets past that check
+    (and then fails on its NULL rows for want of sorted runs, still without touching memory)."""
+    base = dict(M=10, F=3, K=8, D=8, act=0, linear_att=1, inner_conv=1, outer_conv=1, loss=0, lamda_att=1.0, beta_outer=1.0,
+                lr=0.05)
+    for opt in (1, 2, 3):
+        s = hip.Shape(optimizer=opt, **base)
+        assert lib.cffm_dp_apply(C.byref(s), None, None, None, None, None, 8, None, 24, None, 8, None, 0, None) == 10002, opt
+        assert lib.cffm_dp_apply_dense(C.byref(s), None, None, None, None, None, 8, None, None) == 10002, opt
+    s = hip.Shape(optimizer=0, **base)
+    assert lib.cffm_dp_apply(C.byref(s), None, None, None, None, None, 8, None, 0, None, 8, None, 3, None) == 10001
+
+
 def test_engine_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -214,6 +214,31 @@ def _dp_worker(rank, world, dense=False):
     return float(loss[0]), {k: np.asarray(v) for k, v in comp.p.items()}
 
 
+def _refuse_worker(rank, world):
+    from cffm_amd.dist import DataParallelStep, ShardedStep, shard_params
+    cfg, p, X, y = _case()
+    cfg.optimizer = 'AdamOptimizer'
+    out = []
+    for cls, comp in ((DataParallelStep, OracleCompute(cfg, p)), (DataParallelStep, DenseOracleCompute(cfg, p)),
+                      (ShardedStep, ShardedOracleCompute(cfg, shard_params(p, rank, world)))):
+        try:
+            cls(comp)
+        except ValueError as e:
+            out.append(str(e))
+        else:
+            out.append(None)
+    return out
+
+
+def test_data_parallel_steps_refuse_other_optimizers():
+    """The multi-GPU updates are Adagrad only: both step classes refuse AdamOptimizer with a ValueError naming it, at
+    construction, before any collective (a world-2 gloo group, the oracle as compute)."""
+    res = _run(_refuse_worker, 2)
+    for rank in range(2):
+        for msg in res[rank]:
+            assert msg is not None and 'AdamOptimizer' in msg, (rank, res[rank])
+
+
 @pytest.mark.parametrize('world,dense', [(2, False), (4, False), (2, True)])
 def test_data_parallel_step_equals_single_process_step(world, dense):
     res = _run(_dp_worker, world, dense)
