@@ -30,10 +30,8 @@ inline int bits_for(int64_t n_values) {     // bits that hold 0 .. n_values - 1 
 }
 
 __global__ __launch_bounds__(256) void plan_pack_kernel(const int32_t* __restrict__ ids, int64_t n, int world, unsigned Mmax, PlanGeo g,
-                                                        unsigned long long* __restrict__ keys, int32_t* __restrict__ local_ids,
-                                                        long long* __restrict__ counts) {
+                                                        unsigned long long* __restrict__ keys, int32_t* __restrict__ local_ids) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < world) counts[i] = 0;
     if (i >= n) return;
     unsigned id = (unsigned)ids[i];
     id = id < Mmax ? id : Mmax - 1;                        // an id outside [0, M) must not index beyond counts[world) / the key bits
@@ -123,8 +121,12 @@ extern "C" int cffm_shard_plan(const int32_t* ids, int64_t n, int32_t world, int
     int32_t* head = (int32_t*)(w + s.head);
     int32_t* incl = (int32_t*)(w + s.incl);
     const unsigned blocks = (unsigned)((n + 255) / 256);
+    // every one of the world counts is cleared here: the grid below has ceil(n / 256) * 256 threads, fewer than world when a batch
+    // has fewer lookups than there are owners
+    hipError_t e0 = hipMemsetAsync(counts, 0, (size_t)world * 8, st);
+    if (e0 != hipSuccess) return (int)e0;
     hipLaunchKernelGGL(plan_pack_kernel, dim3(blocks), dim3(256), 0, st, ids, n, (int)world,
-                       (unsigned)(M < (1ll << 31) ? M : (1ll << 31) - 1), g, keys, local_ids, (long long*)counts);
+                       (unsigned)(M < (1ll << 31) ? M : (1ll << 31) - 1), g, keys, local_ids);
     CFFM_CHECK_LAUNCH();
     size_t tb = s.tmp_bytes;
     hipError_t e = rocprim::radix_sort_keys((void*)(w + s.tmp), tb, keys, sorted, (size_t)n, (unsigned)g.sb,

@@ -179,13 +179,17 @@ def test_cffm_class_trains_data_parallel_on_the_gpu(tmp_path):
 
 
 @pytest.mark.parametrize('n_rows,F,M,world,id_range', [(8192, 32, 10_000_000, 8, None), (300, 10, 5382, 2, 40), (1, 3, 17, 4, None),
-                                                      (4096, 6, 226336, 3, 500), (70, 16, 3000, 1, None)])
+                                                      (4096, 6, 226336, 3, 500), (70, 16, 3000, 1, None),
+                                                      # fewer lookups than owners: counts[n rounded up to 256 .. world) is touched by
+                                                      # no thread of the pack kernel's grid
+                                                      (1, 3, 17, 300, None), (2, 50, 5000, 1024, None), (5, 60, 5000, 1024, None)])
 def test_device_shard_plan_equals_the_torch_plan(n_rows, F, M, world, id_range):
     """cffm_shard_plan (pack -> one radix sort -> head flags -> scan -> scatter, csrc/plan.hip) against ShardedStep.plan_torch, the ~15
     torch operations it replaces and its specification: every output identical - local rows, the stable (owner, local row) order
     with slots ascending inside a run, the distinct-pair index of every sorted position and of every slot, the request list and the
     per-owner counts - at cfg5's per-GPU share (8192 x 32 lookups, 10 M features, 8 owners), with heavy duplication, with a single
-    row, with a world size that is not a power of two and at world size 1."""
+    row, with a world size that is not a power of two, at world size 1, and with fewer lookups than owners (world 300 and 1024).  The
+    counts buffer is handed in pre-filled with a non-zero pattern, so the result cannot depend on what the allocator returns."""
     from cffm_amd.dist import ShardedStep
     from cffm_amd.engine import HipEngine
     rng = np.random.default_rng(n_rows + world)
@@ -198,8 +202,10 @@ def test_device_shard_plan_equals_the_torch_plan(n_rows, F, M, world, id_range):
     st = ShardedStep.__new__(ShardedStep)
     st.world, st.dedup = world, True
     want = st.plan_torch(ids)
-    got = eng.shard_plan(ids, world, M)
+    dirty = torch.arange(world, dtype=torch.int64, device='cuda') * 7 + 3
+    got = eng.shard_plan(ids, world, M, counts=dirty)
     torch.cuda.synchronize()
+    assert got[5].data_ptr() == dirty.data_ptr()
     n_distinct = int(want[5].sum())
     names = ('local_ids', 'order', 'uniq', 'pos', 'send_rows', 'counts')
     for name, a, b in zip(names, got, want):
@@ -209,5 +215,5 @@ def test_device_shard_plan_equals_the_torch_plan(n_rows, F, M, world, id_range):
         assert torch.equal(a, b), name
     assert n_distinct == int(got[2].max()) + 1 and int(got[5].sum()) == n_distinct
     # and twice in a row on the same scratch (the counts are re-zeroed by the call itself)
-    again = eng.shard_plan(ids, world, M)
+    again = eng.shard_plan(ids, world, M, counts=got[5])
     assert torch.equal(again[5], want[5]) and torch.equal(again[3], want[3])
