@@ -48,15 +48,20 @@ extern "C" int cffm_ws_layout(const cffm_shape_t* s, int32_t B, cffm_ws_layout_t
     int rc = check_shape(s);
     if (rc) return rc;
     if (B < 1) return CFFM_ERR_BAD_SHAPE;
-    memset(out, 0, sizeof(*out));
-    const Geo g = make_geo(s);
     cffm_theta_layout_t tl;
     cffm_theta_layout(s, &tl);
+    SlabPlan sp;
+    make_slab_plan(s, B, tl, &sp);
+    return cffm_ws_layout_from(s, B, tl, sp, out);
+}
+
+// the workspace layout for a theta layout and slab plan the caller already has (StepCtx); shape checked, B >= 1
+int cffm_ws_layout_from(const cffm_shape_t* s, int32_t B, const cffm_theta_layout_t& tl, const SlabPlan& sp, cffm_ws_layout_t* out) {
+    memset(out, 0, sizeof(*out));
+    const Geo g = make_geo(s);
     int64_t o = 0;
     auto take = [&](int64_t bytes) { int64_t r = o; o += (bytes + 255) / 256 * 256; return r; };
     const int64_t b = B;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
     out->gpart = take(sp.total * 4);                             // first: offset 0
     out->gpart_floats = sp.total;
     out->scalars = take(16 * 4);
@@ -113,143 +118,148 @@ extern "C" int cffm_ws_layout(const cffm_shape_t* s, int32_t B, cffm_ws_layout_t
     return 0;
 }
 
+// One context per ABI call: every entry point below checks the shape, returns early for an empty batch and then builds the
+// StepCtx (layouts, slab plan) that forward_impl / backward_impl and the conv functions under them share.
+//
 // no_materialise: the composites that own the whole step (cffm_train_step, cffm_predict, cffm_dp_local) let the wide shapes
 // consume the looked-up rows in the kernel that fetches them (cffm_gather_inner_fwd_wide) and re-fetch them from the tables
-// where a later kernel needs them (backward_impl with the same tab / ids); ws.Ei / ws.Eo are then never written.
+// where a later kernel needs them (backward_impl with BwdOpts.rows = the same tab / ids); ws.Ei / ws.Eo are then never written.
 // cffm_forward keeps materialising: its callers (the stage-by-stage parity tests, cffm_backward, the row-sharded step) read
 // ws.Ei / ws.Eo afterwards.
-static bool wide_rows(const cffm_shape_t* s, const cffm_tables_t* tab, const int32_t* ids) {
-    return tab && ids && cffm_wide_regather_ok(s);
+static bool wide_rows(const cffm_shape_t* s, const RowTables& r) { return r.tab && r.ids && cffm_wide_regather_ok(s); }
+// the rows of one table as the wide kernels fetch them: straight from the table, or (stride / records > 0) out of packed records
+static RowSrc table_rows(const cffm_shape_t* s, const float* base, const RowTables& r) {
+    return {base, r.ids, r.records > 0 ? r.records : s->M, r.stride};
+}
+static RowTables step_rows(const cffm_tables_t* tab, const int32_t* ids, int stride = 0, int records = 0) {
+    RowTables r;
+    r.tab = tab; r.ids = ids; r.stride = stride; r.records = records;
+    return r;
 }
 
-// rstride / rrows > 0 (wide shapes only): tab is a view into packed records of rstride floats, rrows of them (see RowSrc)
-static int forward_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
-                        const float* y, int32_t B, void* ws, bool fused_step, hipStream_t stream, bool no_materialise = false,
-                        int rstride = 0, int rrows = 0) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    const Geo g = make_geo(s);
-    if (no_materialise && wide_rows(s, tab, ids)) {
-        if ((rc = cffm_gather_inner_fwd_wide(s, tab, theta, ids, B, ws, stream, rstride, rrows))) return rc;
-        const RowSrc ro = {tab->outer_emb, ids, rrows > 0 ? rrows : s->M, rstride};
-        if ((rc = cffm_outer_conv0_fwd_rows(s, theta, ws, B, &ro, stream))) return rc;
-        for (int l = 1; l < g.live; ++l)
-            if ((rc = cffm_conv_fwd(s, theta, ws, B, l, stream))) return rc;
-        return cffm_head_fwd_impl2(s, theta, ws, y, B, !fused_step, true, stream);
+struct FwdOpts {
+    bool fused_step = false;         // part of a train step: no separate loss sum, the gather also emits the sort keys
+    bool no_materialise = false;     // see above
+};
+// rows.tab == NULL: row-sharded tables, the rows are already staged in ws.Ei / ws.Eo / ws.fb
+static int forward_impl(const StepCtx& c, const RowTables& rows, const float* y, hipStream_t stream, const FwdOpts& o = FwdOpts()) {
+    const cffm_shape_t* s = c.s;
+    const cffm_tables_t* tab = rows.tab;
+    const float* theta = c.theta;
+    const int32_t B = c.B;
+    void* ws = c.w;
+    const cffm_ws_layout_t& wl = c.wl;
+    int rc = 0;
+    if (o.no_materialise && wide_rows(s, rows)) {
+        if ((rc = cffm_gather_inner_fwd_wide(s, tab, theta, rows.ids, B, ws, stream, rows.stride, rows.records))) return rc;
+        const RowSrc ro = table_rows(s, tab->outer_emb, rows);
+        if ((rc = cffm_conv_fwd_impl(c, 0, stream, &ro))) return rc;
+        for (int l = 1; l < c.g.live; ++l)
+            if ((rc = cffm_conv_fwd_impl(c, l, stream))) return rc;
+        return cffm_head_fwd_impl2(s, theta, ws, y, B, !o.fused_step, true, stream);
     }
     if (!tab) {
-        // row-sharded tables: the rows came in over the wire and are already staged in ws.Ei / ws.Eo / ws.fb
-        if (fused_step) return CFFM_ERR_UNSUPPORTED;
+        if (o.fused_step) return CFFM_ERR_UNSUPPORTED;
         if ((rc = cffm_inner_fwd(s, theta, ws, B, stream))) return rc;
-    } else if (fused_step && s->inner_conv && s->outer_conv) {
+    } else if (o.fused_step && s->inner_conv && s->outer_conv) {
         // the inner-branch kernel gathers the rows of its example itself (one launch less)
-        if ((rc = cffm_inner_fwd_impl(s, theta, ws, B, tab, ids, stream))) return rc;
+        if ((rc = cffm_inner_fwd_impl(s, theta, ws, B, tab, rows.ids, stream))) return rc;
     } else {
-        rc = cffm_gather_impl(s, tab, ids, B, s->inner_conv ? (float*)(w + wl.Ei) : nullptr,
-                              s->outer_conv ? (float*)(w + wl.Eo) : nullptr, (float*)(w + wl.fb),
-                              fused_step ? (unsigned long long*)(w + wl.sort_keys) : nullptr, stream);
+        rc = cffm_gather_impl(s, tab, rows.ids, B, s->inner_conv ? c.at(wl.Ei) : nullptr, s->outer_conv ? c.at(wl.Eo) : nullptr,
+                              c.at(wl.fb), o.fused_step ? c.at<unsigned long long>(wl.sort_keys) : nullptr, stream);
         if (rc) return rc;
         if ((rc = cffm_inner_fwd(s, theta, ws, B, stream))) return rc;
     }
-    if (s->outer_conv) {
-        if ((rc = cffm_outer_conv0_fwd(s, theta, ws, B, stream))) return rc;
-        for (int l = 1; l < g.live; ++l)
-            if ((rc = cffm_conv_fwd(s, theta, ws, B, l, stream))) return rc;
-    }
-    return cffm_head_fwd_impl(s, theta, ws, y, B, !fused_step, stream);
+    for (int l = 0; l < c.g.live && s->outer_conv; ++l)
+        if ((rc = cffm_conv_fwd_impl(c, l, stream))) return rc;
+    return cffm_head_fwd_impl(s, theta, ws, y, B, !o.fused_step, stream);
 }
 
 extern "C" int cffm_forward(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
                             const float* y, int32_t B, void* ws, void* stream) {
-    return forward_impl(s, tab, theta, ids, y, B, ws, false, (hipStream_t)stream);
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    const StepCtx c(s, B, theta, ws);
+    return forward_impl(c, step_rows(tab, ids), y, (hipStream_t)stream);
 }
 
 extern "C" int cffm_predict(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
                             int32_t B, void* ws, float* out, void* stream) {
-    int rc = forward_impl(s, tab, theta, ids, nullptr, B, ws, false, (hipStream_t)stream, true);
+    int rc = check_shape(s);
     if (rc || B <= 0) return rc;
-    if (out) {
-        cffm_ws_layout_t wl;
-        cffm_ws_layout(s, B, &wl);
-        hipError_t e = hipMemcpyAsync(out, (char*)ws + wl.out, (size_t)B * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    const StepCtx c(s, B, theta, ws);
+    FwdOpts fo;
+    fo.no_materialise = true;
+    rc = forward_impl(c, step_rows(tab, ids), nullptr, (hipStream_t)stream, fo);
+    if (rc || !out) return rc;
+    hipError_t e = hipMemcpyAsync(out, c.at(c.wl.out), (size_t)B * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : (int)e;
 }
 
-// backward through the slab reduction; fused = single-GPU step (local loss sum, Adagrad folded into the reduction)
-static int backward_impl(const cffm_shape_t* s, float* theta, float* theta_acc, const float* y, int32_t B,
-                         int64_t B_global, void* ws, float* grad, bool fused, float* loss_out, hipStream_t stream,
-                         bool unscaled = false, bool skip_reduce = false, const int32_t* rank_ids = nullptr,
-                         const cffm_tables_t* rtab = nullptr, const int32_t* rids = nullptr, int rstride = 0, int rrows = 0) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
-    cffm_ws_layout_t wl; cffm_theta_layout_t tl;
-    cffm_ws_layout(s, B, &wl); cffm_theta_layout(s, &tl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
+// backward through the slab reduction (BwdOpts, internal.hpp)
+static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, float* grad, hipStream_t stream,
+                         const BwdOpts& o = BwdOpts()) {
+    const cffm_shape_t* s = c.s;
+    const float* theta = c.theta;
+    const int32_t B = c.B;
+    void* ws = c.w;
+    int rc = 0;
     if (!s->inner_conv || !s->outer_conv || !s->linear_att) {   // slabs of a disabled branch must read as zeros
-        hipError_t e = hipMemsetAsync(w + wl.gpart, 0, (size_t)wl.gpart_floats * 4, stream);
+        hipError_t e = hipMemsetAsync(c.at(c.wl.gpart), 0, (size_t)c.wl.gpart_floats * 4, stream);
         if (e != hipSuccess) return (int)e;
     }
     bool inner_done = false;
-    const bool wide = wide_rows(s, rtab, rids);      // the forward did not materialise Ei / Eo: rows come from the tables (RowSrc)
+    const bool wide = wide_rows(s, o.rows);          // the forward did not materialise Ei / Eo: rows come from the tables (RowSrc)
     if (bwd_top_ok(s, B) && s->loss != CFFM_LOSS_SQUARE_L2) {
         // head + top two conv layers + inner branch: one launch
         int next = 0;
-        if ((rc = cffm_bwd_top_impl(s, theta, ws, y, B, B_global, fused || loss_out != nullptr, loss_out, unscaled, stream, &next,
-                                    rank_ids)))
-            return rc;
+        if ((rc = cffm_bwd_top_impl(c, y, B_global, o, stream, &next))) return rc;
         inner_done = true;
         if (bwd_fused01_ok(s, B)) {            // layers 3..0 below the fused top: one launch
-            if ((rc = cffm_conv01_bwd_impl(s, theta, ws, B, stream))) return rc;
-            next = 0;
+            if ((rc = cffm_conv01_bwd_impl(c, stream))) return rc;
+            next = -1;
         }
-        for (int l = next; l >= 1; --l) {
-            if (l == next && top_wgrad_deferred(s, B)) rc = cffm_conv_bwd_below_top(s, theta, ws, B, l, stream);
-            else rc = cffm_conv_bwd(s, theta, ws, B, l, stream);
-            if (rc) return rc;
+        for (int l = next; l >= 0; --l) {
+            ConvBwdOpts co;
+            co.with_top_wgrad = l == next && top_wgrad_deferred(s, B);     // (never layer 0: conv_pair_ok wants l >= 1)
+            if ((rc = cffm_conv_bwd_impl(c, l, stream, co))) return rc;
         }
-        if (!bwd_fused01_ok(s, B) && (rc = cffm_outer_conv0_bwd(s, theta, ws, B, stream))) return rc;
     } else {
-        if ((rc = cffm_head_bwd_impl(s, theta, ws, y, B, B_global, fused || loss_out != nullptr, loss_out, stream, unscaled))) return rc;
-        if (s->outer_conv) {
-            for (int l = g.live - 1; l >= 1; --l) {
-                if (l == g.live - 1) rc = cffm_conv_bwd_with_inner(s, theta, ws, B, l, stream, &inner_done);
-                else rc = cffm_conv_bwd(s, theta, ws, B, l, stream);
-                if (rc) return rc;
-            }
-            if (wide) {
-                const RowSrc ro = {rtab->outer_emb, rids, rrows > 0 ? rrows : s->M, rstride};
-                rc = cffm_outer_conv0_bwd_rows(s, theta, ws, B, &ro, stream);
-            } else {
-                rc = cffm_outer_conv0_bwd(s, theta, ws, B, stream);
-            }
-            if (rc) return rc;
+        if ((rc = cffm_head_bwd_impl(s, theta, ws, y, B, B_global, o.local_sum(), o.loss_out, stream, o.unscaled)))
+            return rc;
+        const RowSrc ro = table_rows(s, wide ? o.rows.tab->outer_emb : nullptr, o.rows);
+        for (int l = c.g.live - 1; l >= 0 && s->outer_conv; --l) {
+            ConvBwdOpts co;
+            if (l == c.g.live - 1) co.carry_inner = &inner_done;    // a paired launch (layers >= 1 only) takes the inner branch along
+            if (l == 0 && wide) co.rs = &ro;
+            if ((rc = cffm_conv_bwd_impl(c, l, stream, co))) return rc;
         }
     }
     if (!inner_done) {
         if (wide) {
-            const RowSrc ri = {rtab->inner_emb, rids, rrows > 0 ? rrows : s->M, rstride};
+            const RowSrc ri = table_rows(s, o.rows.tab->inner_emb, o.rows);
             rc = cffm_inner_bwd_rows(s, theta, ws, B, &ri, stream);
         } else {
             rc = cffm_inner_bwd(s, theta, ws, B, stream);
         }
         if (rc) return rc;
     }
-    if (skip_reduce) return 0;                  // the caller reduces the slabs together with the table update
-    return cffm_reduce_slabs_impl(s, ws, B, grad, fused ? theta : nullptr, fused ? theta_acc : nullptr, s->lr, stream);
+    if (o.skip_reduce) return 0;
+    return cffm_reduce_slabs_impl(s, ws, B, grad, o.adagrad_theta, o.adagrad_acc, s->lr, stream);
 }
 
 extern "C" int cffm_backward(const cffm_shape_t* s, const float* theta, const float* y, int32_t B, int64_t B_global,
                              void* ws, float* grad, void* stream) {
-    return backward_impl(s, const_cast<float*>(theta), nullptr, y, B, B_global, ws, grad, false, nullptr,
-                         (hipStream_t)stream);
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    const StepCtx c(s, B, theta, ws);
+    return backward_impl(c, y, B_global, grad, (hipStream_t)stream);
+}
+
+// this rank's loss-term sum (ws.scalars[0]) -> grad[theta.n], so that ONE all-reduce carries gradients and loss
+static int move_loss_sum(const StepCtx& c, float* grad, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(grad + c.tl.n, c.at(c.wl.scalars), sizeof(float), hipMemcpyDeviceToDevice, st);
+    return e == hipSuccess ? 0 : (int)e;
 }
 
 // Data-parallel backward: dL/dout = (out - y) / B_global WITHOUT the 1/L of the RMSE-style loss; grad must have room
@@ -259,19 +269,17 @@ extern "C" int cffm_backward(const cffm_shape_t* s, const float* theta, const fl
 extern "C" int cffm_backward_unscaled(const cffm_shape_t* s, const float* theta, const int32_t* ids, const float* y,
                                       int32_t B, int64_t B_global, void* ws, float* grad, float* rows, void* stream) {
     if (s && (s->loss == CFFM_LOSS_HYBRID || s->loss == CFFM_LOSS_SQUARE_L2)) return CFFM_ERR_UNSUPPORTED;   // single-process only
-    int rc = backward_impl(s, const_cast<float*>(theta), nullptr, y, B, B_global, ws, grad, false, nullptr,
-                           (hipStream_t)stream, true);
+    int rc = check_shape(s);
     if (rc || B <= 0) return rc;
-    cffm_ws_layout_t wl; cffm_theta_layout_t tl;
-    cffm_ws_layout(s, B, &wl); cffm_theta_layout(s, &tl);
-    char* w = (char*)ws;
-    if (!rows) {        // the caller packs the row gradients itself (cffm_pack_rows_dedup): only the loss-term sum is moved
-        hipError_t e = hipMemcpyAsync(grad + tl.n, w + wl.scalars, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-        return e == hipSuccess ? 0 : (int)e;
-    }
-    return cffm_pack_rows(s, ids, B, s->inner_conv ? (const float*)(w + wl.dEi) : nullptr,
-                          s->outer_conv ? (const float*)(w + wl.dEo) : nullptr, (const float*)(w + wl.dfb),
-                          (const float*)(w + wl.scalars), grad + tl.n, rows, (hipStream_t)stream);
+    const StepCtx c(s, B, theta, ws);
+    BwdOpts bo;
+    bo.unscaled = true;
+    if ((rc = backward_impl(c, y, B_global, grad, (hipStream_t)stream, bo))) return rc;
+    if (!rows) return move_loss_sum(c, grad, (hipStream_t)stream);   // the caller packs the row gradients itself (cffm_pack_rows_dedup)
+    const cffm_ws_layout_t& wl = c.wl;
+    return cffm_pack_rows(s, ids, B, s->inner_conv ? c.at<const float>(wl.dEi) : nullptr,
+                          s->outer_conv ? c.at<const float>(wl.dEo) : nullptr, c.at<const float>(wl.dfb),
+                          c.at<const float>(wl.scalars), grad + c.tl.n, rows, (hipStream_t)stream);
 }
 
 // ---- row-sharded step without staging (cffm_amd/dist.py ShardedStep): the packed records a rank received ARE the tables ------
@@ -287,7 +295,10 @@ extern "C" int cffm_forward_packed(const cffm_shape_t* s, const float* theta, co
     cffm_tables_t view;
     if (B <= 0) return check_shape(s);
     if (!pos || !packed_view(s, packed, n_records, &view)) return CFFM_ERR_UNSUPPORTED;
-    return forward_impl(s, &view, theta, pos, y, B, ws, false, (hipStream_t)stream, true, s->K + s->D + 4, (int)n_records);
+    const StepCtx c(s, B, theta, ws);
+    FwdOpts fo;
+    fo.no_materialise = true;
+    return forward_impl(c, step_rows(&view, pos, s->K + s->D + 4, (int)n_records), y, (hipStream_t)stream, fo);
 }
 extern "C" int cffm_backward_unscaled_packed(const cffm_shape_t* s, const float* theta, const float* packed, const int32_t* pos,
                                              int64_t n_records, const float* y, int32_t B, int64_t B_global, void* ws, float* grad,
@@ -296,13 +307,12 @@ extern "C" int cffm_backward_unscaled_packed(const cffm_shape_t* s, const float*
     cffm_tables_t view;
     if (B <= 0) return check_shape(s);
     if (!pos || !packed_view(s, packed, n_records, &view)) return CFFM_ERR_UNSUPPORTED;
-    int rc = backward_impl(s, const_cast<float*>(theta), nullptr, y, B, B_global, ws, grad, false, nullptr, (hipStream_t)stream, true,
-                           false, nullptr, &view, pos, s->K + s->D + 4, (int)n_records);
-    if (rc) return rc;
-    cffm_ws_layout_t wl; cffm_theta_layout_t tl;
-    cffm_ws_layout(s, B, &wl); cffm_theta_layout(s, &tl);
-    hipError_t e = hipMemcpyAsync(grad + tl.n, (char*)ws + wl.scalars, sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : (int)e;
+    const StepCtx c(s, B, theta, ws);
+    BwdOpts bo;
+    bo.unscaled = true;
+    bo.rows = step_rows(&view, pos, s->K + s->D + 4, (int)n_records);
+    int rc = backward_impl(c, y, B_global, grad, (hipStream_t)stream, bo);
+    return rc ? rc : move_loss_sum(c, grad, (hipStream_t)stream);
 }
 
 // the key placement can leave the forward launch when the fused top of the backward runs (and is not the L2 loss path)
@@ -320,16 +330,21 @@ extern "C" int cffm_dp_local(const cffm_shape_t* s, const cffm_tables_t* tab, co
                              const float* y, int32_t B, int64_t B_global, void* ws, float* grad, float* rows, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
+    if (rc || B <= 0) return rc;
+    const StepCtx c(s, B, theta, ws);
     if (!y || s->loss == CFFM_LOSS_HYBRID || s->loss == CFFM_LOSS_SQUARE_L2) return CFFM_ERR_UNSUPPORTED;
-    const bool run = cffm_fwd_all_ok(s, B);          // false for a disabled branch: plain forward, no sorted run          // the single-launch forward also leaves this rank's keys sorted
-    const bool later = run && defer_rank(s, B);
-    if (run) rc = cffm_fwd_all_impl(s, tab, theta, ids, y, B, ws, st, !later);
-    else rc = forward_impl(s, tab, theta, ids, y, B, ws, false, st, true);
+    const bool run = cffm_fwd_all_ok(s, B);          // the single-launch forward also leaves this rank's keys sorted; false for a
+    const bool later = run && defer_rank(s, B);      // disabled branch: plain forward, no sorted run
+    FwdOpts fo;
+    fo.no_materialise = true;
+    rc = run ? cffm_fwd_all_impl(c, tab, ids, y, st, !later) : forward_impl(c, step_rows(tab, ids), y, st, fo);
     if (rc) return rc;
-    if ((rc = backward_impl(s, const_cast<float*>(theta), nullptr, y, B, B_global, ws, grad, false, nullptr, st, true, true,
-                            later ? ids : nullptr, run ? nullptr : tab, run ? nullptr : ids))) return rc;
+    BwdOpts bo;
+    bo.unscaled = true;
+    bo.skip_reduce = true;                           // cffm_dp_tail reduces
+    if (later) bo.rank_ids = ids;
+    if (!run) bo.rows = step_rows(tab, ids);
+    if ((rc = backward_impl(c, y, B_global, grad, st, bo))) return rc;
     return cffm_dp_tail(s, ids, B, ws, grad, rows, run, st);
 }
 
@@ -339,18 +354,20 @@ extern "C" int cffm_dp_local_dense(const cffm_shape_t* s, const cffm_tables_t* t
                                    const float* y, int32_t B, int64_t B_global, void* ws, float* flat, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
+    if (rc || B <= 0) return rc;
+    const StepCtx c(s, B, theta, ws);
     if (!y || s->loss == CFFM_LOSS_HYBRID || s->loss == CFFM_LOSS_SQUARE_L2 || !cffm_fwd_all_ok(s, B)) return CFFM_ERR_UNSUPPORTED;
-    cffm_theta_layout_t tl;
-    cffm_theta_layout(s, &tl);
     // The table image of `flat` must be all zeros on entry: cffm_dp_apply_dense leaves it that way (zero on exit), so only
     // the very first step needs a cleared buffer (the round-2 code paid a hipMemsetAsync of the 1.4 MB image, 4.5 us in front of
     // the forward launch, on every step).
     const bool later = defer_rank(s, B);
-    if ((rc = cffm_fwd_all_impl(s, tab, theta, ids, y, B, ws, st, !later))) return rc;
-    if ((rc = backward_impl(s, const_cast<float*>(theta), nullptr, y, B, B_global, ws, flat, false, nullptr, st, true, true,
-                            later ? ids : nullptr))) return rc;
+    rc = cffm_fwd_all_impl(c, tab, ids, y, st, !later);
+    if (rc) return rc;
+    BwdOpts bo;
+    bo.unscaled = true;
+    bo.skip_reduce = true;                           // cffm_dp_tail_dense reduces
+    if (later) bo.rank_ids = ids;
+    if ((rc = backward_impl(c, y, B_global, flat, st, bo))) return rc;
     return cffm_dp_tail_dense(s, B, ws, flat, st);
 }
 
@@ -359,33 +376,37 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
                                int32_t B, void* ws, float* loss, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
+    if (rc || B <= 0) return rc;
+    const StepCtx c(s, B, theta, ws);
+    FwdOpts fo;
+    fo.fused_step = true;
+    BwdOpts bo;
+    bo.adagrad_theta = theta; bo.adagrad_acc = theta_acc;    // Adagrad of theta folded into the slab reduction
+    bo.loss_out = loss;
     if (s->loss == CFFM_LOSS_SQUARE_L2) {       // regularised square loss: dense table gradients and updates
         // the reference cannot build this graph with a disabled branch either: create_loss reads self.weights['inner_embeddings']
         // and ['outer_embeddings'] (CFFM.py:489-491), which initialize_variables only creates for an enabled branch (:255, :262)
         if (!s->inner_conv || !s->outer_conv) return CFFM_ERR_UNSUPPORTED;
-        if ((rc = forward_impl(s, tab, theta, ids, y, B, ws, true, st))) return rc;
-        if ((rc = backward_impl(s, theta, theta_acc, y, B, (int64_t)B, ws, grad, true, loss, st))) return rc;
+        if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
+        if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
         return cffm_tables_adagrad_l2(s, tab, tab_acc, ids, (int64_t)B * s->F, ws, B, st);
     }
     if (cffm_fwd_all_ok(s, B)) {                 // small-channel shapes: the whole forward (and the key sort) in one launch
         const bool later = defer_rank(s, B);
-        if ((rc = cffm_fwd_all_impl(s, tab, theta, ids, y, B, ws, st, !later))) return rc;
-        if ((rc = backward_impl(s, theta, theta_acc, y, B, (int64_t)B, ws, grad, true, loss, st, false, true, later ? ids : nullptr)))
-            return rc;
+        if ((rc = cffm_fwd_all_impl(c, tab, ids, y, st, !later))) return rc;
+        bo.skip_reduce = true;                   // cffm_update_all reduces
+        if (later) bo.rank_ids = ids;
+        if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
         return cffm_update_all(s, tab, tab_acc, theta, theta_acc, grad, ws, B, st);
     }
-    rc = forward_impl(s, tab, theta, ids, y, B, ws, true, st, true);
-    if (rc) return rc;
-    if ((rc = backward_impl(s, theta, theta_acc, y, B, (int64_t)B, ws, grad, true, loss, st, false, false, nullptr, tab, ids))) return rc;
-    return cffm_sparse_adagrad_impl(s, tab, tab_acc, ids, (int64_t)B * s->F,
-                                    s->inner_conv ? (const float*)(w + wl.dEi) : nullptr,
-                                    s->outer_conv ? (const float*)(w + wl.dEo) : nullptr, (const float*)(w + wl.dfb),
-                                    ws, B, true, st);
+    fo.no_materialise = true;
+    if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
+    bo.rows = step_rows(tab, ids);
+    if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
+    const cffm_ws_layout_t& wl = c.wl;
+    return cffm_sparse_adagrad_impl(s, tab, tab_acc, ids, (int64_t)B * s->F, s->inner_conv ? c.at<const float>(wl.dEi) : nullptr,
+                                    s->outer_conv ? c.at<const float>(wl.dEo) : nullptr, c.at<const float>(wl.dfb), ws, B,
+                                    /*prepacked=*/true, st);
 }
 
 extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_state1,
@@ -399,11 +420,15 @@ extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* t
     if (B <= 0) return 0;
     if (s->loss == CFFM_LOSS_SQUARE_L2 && (!s->inner_conv || !s->outer_conv)) return CFFM_ERR_UNSUPPORTED;   // as in cffm_train_step
     hipStream_t st = (hipStream_t)stream;
-    const bool nm = s->loss != CFFM_LOSS_SQUARE_L2;      // the regularised loss sweeps the tables densely: keep its path as it was
-    if ((rc = forward_impl(s, tab, theta, ids, y, B, ws, true, st, nm))) return rc;
-    // gradients only (no fused Adagrad); the loss is written by head_bwd
-    if ((rc = backward_impl(s, theta, nullptr, y, B, (int64_t)B, ws, grad, false, loss, st, false, false, nullptr,
-                            nm ? tab : nullptr, nm ? ids : nullptr))) return rc;
+    const StepCtx c(s, B, theta, ws);
+    FwdOpts fo;
+    fo.fused_step = true;
+    fo.no_materialise = s->loss != CFFM_LOSS_SQUARE_L2;  // the regularised loss sweeps the tables densely: keep its path as it was
+    if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
+    BwdOpts bo;                                          // gradients only (no fused Adagrad); the loss is written by head_bwd
+    bo.loss_out = loss;
+    if (fo.no_materialise) bo.rows = step_rows(tab, ids);
+    if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
     return cffm_apply_opt(s, tab, tab_state1, tab_state2, theta, theta_state1, theta_state2, grad, ids, (int64_t)B * s->F, ws,
                           B, step, st);
 }

@@ -88,6 +88,7 @@ static inline bool conv0_fact_tile_ok(const Geo& g) {
 // the tiled layer-0 input gradient that reads the filter as pre-packed MFMA fragments (ws.w0pack)
 static inline bool conv0_tile_dgrad2_ok(const Geo& g) { return conv0_fact_tile_ok(g) && g.D / 2 <= 32 && g.F <= 32; }
 static inline bool conv0_tile_fwd_ok(const Geo& g) { return conv0_fact_tile_ok(g) && 2 * ((g.F + 3) & ~3) <= 4 * C0T_MAXKS; }
+static inline bool conv0_tile_wgrad_ok(const Geo& g) { return conv0_fact_tile_ok(g) && g.D / 2 <= 32; }
 // ws.relu0: relu masks of C_0 .. C_{live-2} of the wide shapes, one after the other ([rows of C_l][Pp/16] 16-bit words each)
 static inline int64_t relu_mask_bytes(const Geo& g, int64_t B, int l) {
     const int64_t S = g.D >> (l + 1);

@@ -2886,6 +2886,26 @@ static inline int set_lds(KernelT k, size_t lds) {
 
 template <int N> using IntC = std::integral_constant<int, N>;
 
+// ---- dynamic LDS: one function per size, shared by the launcher, the *_ok() predicate and cffm_fwd_all_impl ----------------------
+// Examples whose embedding tile ([F][D+1] floats each) a workgroup of BM rows stages.  Forward kinds (layer-0 forward and weight
+// gradient): the examples its rows span; layer-0 input gradient: whole examples, at least BM rows.
+static inline int fwd_tile_examples(int BM, int lgSo) { const int S2 = 1 << (2 * lgSo); return BM > S2 ? BM / S2 : 1; }
+static inline int dgrad0_rows_per_wg(int BM, int lgSo) { const int S2 = 1 << (2 * lgSo); return S2 > BM ? S2 : BM; }
+static inline int dgrad0_tile_examples(int BM, int lgSo) { return dgrad0_rows_per_wg(BM, lgSo) >> (2 * lgSo); }
+// floats of the pair table + the embedding tiles of n_ex examples (the GEN / L0 instances; 0 for the direct layers)
+static inline size_t emb_tile_floats(int Pp, int n_ex, int F, int D) { return (size_t)Pp + (size_t)n_ex * F * (D + 1); }
+// conv_fwd_taps_kernel: the four filter taps (row pitch PP + 4), reused for the cross-wave reduction of RM row tiles
+static inline size_t conv_fwd_taps_scratch(int PP, int RM) {
+    const size_t taps = (size_t)4 * PP * (PP + 4) * 4, red = (size_t)4 * RM * (PP / 16) * 64 * 16;
+    return red > taps ? red : taps;
+}
+// conv0_fact_fwd_kernel: filter [4][Pp][Pp] | T planes [2F][S*Pp + 16] | embedding tile [F][D+1]
+static inline size_t conv0_fact_t_off(int Pp) { return (size_t)4 * Pp * Pp * 4; }
+static inline size_t conv0_fact_t_bytes(int Pp, int F, int D) { return (size_t)2 * F * (D / 2 * Pp + 16) * 4; }
+static inline size_t conv0_fact_fwd_lds(int Pp, int F, int D) {
+    return conv0_fact_t_off(Pp) + conv0_fact_t_bytes(Pp, F, D) + (size_t)F * (D + 1) * 4 + 16;
+}
+
 // The fused small-shape kernels get the activation of the README commands compiled in: frappe = selu at Pp 48 (NT 3), ml-tag =
 // elu and book-crossing = relu at Pp 16 (NT 1) (README.md:20-28); every other (NT, act) reads it at run time (-1).
 // go(IntC<ACT>) launches the instance; if constexpr keeps the (NT, ACT) pairs no shape reaches out of the build.
@@ -2908,8 +2928,6 @@ static inline bool conv_b3_on() {
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
-    const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex = GEN ? (BM > S2 ? BM / S2 : 1) : 0;
     ConvArgs b = a;
     b.nblk = nblk;
     const int64_t nb1 = 8 * xcd_per((a.Mtot + BM - 1) / BM) * nblk;
@@ -2926,7 +2944,7 @@ static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
             return 0;
         }
     }
-    const size_t lds = (size_t)(2 * KSTEP * (NT * 16 + 4) + (GEN ? a.Pp + n_ex * a.F * (a.D + 1) : 0) + 4) * 4;
+    const size_t lds = ((size_t)2 * KSTEP * (NT * 16 + 4) + (GEN ? emb_tile_floats(a.Pp, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) + 4) * 4;
     int rc = set_lds(conv_fwd_kernel<NT, RM, GEN>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((conv_fwd_kernel<NT, RM, GEN>), dim3((unsigned)nb1), dim3(256), lds, st, b);
@@ -2937,9 +2955,8 @@ static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
 template <int NT, int RM, bool L0>
 static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
-    const int S2 = 1 << (2 * a.lgSo);
-    const int rows_per_wg = L0 ? (S2 > BM ? S2 : BM) : BM;
-    const int n_ex = L0 ? rows_per_wg / S2 : 0;
+    const int rows_per_wg = L0 ? dgrad0_rows_per_wg(BM, a.lgSo) : BM;
+    const int n_ex = L0 ? dgrad0_tile_examples(BM, a.lgSo) : 0;
     const size_t lds = (size_t)(2 * KSTEP * (NT * 16 + 4) + (L0 ? a.Pp + 5 * n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F : 0) + 4) * 4;
     DgradArgs b = a;
     b.nblk = L0 ? 1 : nblk;
@@ -2967,9 +2984,7 @@ static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
 template <int NT>
 static int launch_wgrad(const WgradArgs& a, hipStream_t st) {
     constexpr int BI = 64, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16);
-    const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex = WG_KM > S2 ? WG_KM / S2 : 1;
-    const size_t lds = (size_t)(WG_KM * LDB + a.Pp + n_ex * a.F * (a.D + 1) + 4) * 4;
+    const size_t lds = ((size_t)WG_KM * LDB + emb_tile_floats(a.Pp, fwd_tile_examples(WG_KM, a.lgSo), a.F, a.D) + 4) * 4;
     int rc = set_lds(wgrad_kernel<NT>, lds);
     if (rc) return rc;
     WgradArgs b = a;
@@ -3008,12 +3023,7 @@ static int launch_wgrad2(const WgradArgs& a, hipStream_t st) {
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_taps(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 16 * RM;
-    const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex = GEN ? (BM > S2 ? BM / S2 : 1) : 0;
-    size_t lds = (size_t)4 * PP * (PP + 4) * 4;
-    const size_t red = (size_t)4 * RM * NT * 64 * 16;
-    if (red > lds) lds = red;
-    lds += (size_t)(GEN ? PP + n_ex * a.F * (a.D + 1) : 0) * 4 + 16;
+    const size_t lds = conv_fwd_taps_scratch(PP, RM) + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
     int rc = set_lds(conv_fwd_taps_kernel<NT, RM, GEN>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((conv_fwd_taps_kernel<NT, RM, GEN>), dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
@@ -3024,9 +3034,7 @@ static int launch_conv_fwd_taps(const ConvArgs& a, hipStream_t st) {
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_rows(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 64 * RM;
-    const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex = GEN ? (BM > S2 ? BM / S2 : 1) : 0;
-    const size_t lds = (size_t)4 * PP * PP * 4 + (size_t)(GEN ? PP + n_ex * a.F * (a.D + 1) : 0) * 4 + 16;
+    const size_t lds = (size_t)4 * PP * PP * 4 + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
     int rc = set_lds(conv_fwd_rows_kernel<NT, RM, GEN>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((conv_fwd_rows_kernel<NT, RM, GEN>), dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
@@ -4041,9 +4049,7 @@ static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st, float* 
 
 template <int NT>
 static int launch_conv0_fact_fwd(const ConvArgs& a, hipStream_t st) {
-    constexpr int PP = NT * 16;
-    const int S = a.D / 2;
-    const size_t lds = (size_t)(4 * PP * PP + 2 * a.F * (S * PP + 16) + a.F * (a.D + 1)) * 4 + 16;
+    const size_t lds = conv0_fact_fwd_lds(NT * 16, a.F, a.D);
     int rc = set_lds(conv0_fact_fwd_kernel<NT>, lds);
     if (rc) return rc;
     hipLaunchKernelGGL((conv0_fact_fwd_kernel<NT>), dim3(a.B), dim3(256), lds, st, a);
@@ -4055,8 +4061,7 @@ static int launch_conv0_fact_fwd(const ConvArgs& a, hipStream_t st) {
 static inline bool conv0_fact_ok(const Geo& g) {
     const int S = g.D / 2;
     if (g.Pp > 64 || (S != 16 && S != 32)) return false;
-    const size_t lds = (size_t)(4 * g.Pp * g.Pp + 2 * g.F * (S * g.Pp + 16) + g.F * (g.D + 1)) * 4 + 16;
-    return lds <= 150 * 1024;
+    return conv0_fact_fwd_lds(g.Pp, g.F, g.D) <= 150 * 1024;
 }
 
 // LDS of conv0_fact_bwd_body with its 16 wavefronts: filter, T planes, partial tiles, dEi / dEj, bias partials, row sums,
@@ -4095,9 +4100,8 @@ static int launch_conv0_fact_bwd(const DgradArgs& a, float* slabW, float* slabB,
 template <int NT, int RM, bool L0, int HALVES>
 static int launch_dgrad_taps(const DgradArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 16 * RM;
-    const int S2 = 1 << (2 * a.lgSo);
-    const int rows_per_wg = L0 ? (S2 > BM ? S2 : BM) : BM;
-    const int n_ex = L0 ? rows_per_wg / S2 : 0;
+    const int rows_per_wg = L0 ? dgrad0_rows_per_wg(BM, a.lgSo) : BM;
+    const int n_ex = L0 ? dgrad0_tile_examples(BM, a.lgSo) : 0;
     const int So = 1 << a.lgSo;
     const bool fast = L0 && RM == 4 && a.lgSo >= 4 && a.lgSo <= 6;
     const size_t scratch = fast ? (size_t)(4 + 4 * HALVES) * PP * So : (size_t)4 * HALVES * n_ex * a.F * (a.D + 1);
@@ -4180,22 +4184,60 @@ static inline int t1_offset(const Geo& g, int l) {
     return off;
 }
 
-static int conv_fwd_any(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int l, hipStream_t st,
-                        const RowSrc* rs = nullptr) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
-    char* w = (char*)ws;
-    ConvArgs a;
-    a.in = (const float*)(w + (l == 0 ? wl.Eo : wl.C[l - 1]));
-    a.W = theta + tl.conv_w[l]; a.bias = theta + tl.conv_b[l];
-    a.out = (float*)(w + wl.C[l]);
+// ---- the argument blocks of layer l (StepCtx, internal.hpp): every member is decided here; the launchers add nblk / nslab / nxy ----
+template <class Args>
+static void set_layer_geo(Args& a, const Geo& g, int B, int l) {
     a.Mtot = layer_rows(g, B, l, &a.lgSo);
     a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
-    if (wl.pool_np[l] > 0) { a.pool = (float*)(w + wl.pool[l]); a.pool_np = wl.pool_np[l]; }   // wide shapes: the epilogue leaves the pool partials
-    if (l >= 1 && wl.wb3_bytes > 0) a.wb3 = (void*)(w + wl.wb3);
-    if (wl.relu0 > 0 && l + 1 < g.live) a.relu = (uint16_t*)(w + wl.relu0 + relu_mask_off(g, B, l));   // ... and the relu mask of C_l for the input gradient of layer l+1
+}
+// layer 0 of the wide shapes: the rows come straight from the table (RowSrc) instead of ws.Eo
+template <class Args>
+static void take_rows(Args& a, const float* Args::*rows, const RowSrc* rs) {
+    if (rs == nullptr) return;
+    a.*rows = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride;
+}
+ConvArgs StepCtx::conv_args(int l) const {
+    ConvArgs a{};
+    a.in = at<const float>(l == 0 ? wl.Eo : wl.C[l - 1]);
+    a.W = theta + tl.conv_w[l]; a.bias = theta + tl.conv_b[l];
+    a.out = at(wl.C[l]);
+    set_layer_geo(a, g, B, l);
+    if (wl.pool_np[l] > 0) { a.pool = at(wl.pool[l]); a.pool_np = wl.pool_np[l]; }   // wide shapes: the epilogue leaves the pool partials
+    if (l >= 1 && wl.wb3_bytes > 0) a.wb3 = at<void>(wl.wb3);
+    if (wl.relu0 > 0 && l + 1 < g.live) a.relu = at<uint16_t>(wl.relu0 + relu_mask_off(g, B, l));   // ... and the relu mask of C_l for the input gradient of layer l+1
+    return a;
+}
+WgradArgs StepCtx::wgrad_args(int l) const {
+    WgradArgs a{};
+    const SlabRange& sr = conv_slab(l);
+    a.in = at<const float>(l == 0 ? wl.Eo : wl.C[l - 1]);
+    a.dC = at<const float>(wl.dC[l]);
+    a.slabW = at(wl.gpart) + sr.base; a.slabB = a.slabW + (tl.conv_b[l] - tl.conv_w[l]);
+    a.slab_stride = sr.len; a.slabB_stride = sr.len;
+    set_layer_geo(a, g, B, l);
+    int NT;
+    if (g.Pp > 64) pick_nt(g.Pp / 16, &a.qblocks, &NT);       // column blocks of the direct kernels; the tap-split kernels do not read it
+    return a;
+}
+DgradArgs StepCtx::dgrad_args(int l) const {
+    DgradArgs a{};
+    a.dC = at<const float>(wl.dC[l]);
+    a.W = theta + tl.conv_w[l];
+    a.Cprev = at<const float>(l == 0 ? wl.Eo : wl.C[l - 1]);
+    a.dt1 = at<const float>(wl.dt1);
+    a.dprev = at(l == 0 ? wl.dEo : wl.dC[l - 1]);
+    if (l >= 1 && wl.wb3_bytes > 0) a.wb3 = at<void>(wl.wb3);
+    if (l >= 1 && wl.relu0 > 0)           // wide shapes: the relu mask the forward of layer l-1 left (1/32 of the bytes of C_{l-1})
+        a.relu = at<const uint16_t>(wl.relu0 + relu_mask_off(g, B, l - 1));
+    set_layer_geo(a, g, B, l);
+    a.t1w = 2 * g.D - 2; a.t1off = t1_offset(g, l);
+    return a;
+}
+
+int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs) {
+    const Geo& g = c.g;
+    if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
+    ConvArgs a = c.conv_args(l);
     int nblk, NT;
     int rc = 0;
     if (g.Pp <= 64) {                       // tap-split path: one wave per filter tap, no K loop
@@ -4222,9 +4264,9 @@ static int conv_fwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
         return rc;
     }
     // rank-1 input channels: factorised, channel-tiled (its step 1 indexes k over ALL fields: 2 * ceil4(F) <= 64 k values)
-    if (l == 0 && conv0_fact_tile_ok(g) && 2 * ((g.F + 3) & ~3) <= 4 * C0T_MAXKS) {
-        if (rs) { a.in = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }     // rows straight from the outer table (RowSrc)
-        return launch_conv0_fact_tile_fwd(a, st, wl.w0pack_floats > 0 ? (float*)(w + wl.w0pack) : nullptr);
+    if (l == 0 && conv0_tile_fwd_ok(g)) {
+        take_rows(a, &ConvArgs::in, rs);
+        return launch_conv0_fact_tile_fwd(a, st, c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr);
     }
     if (l == 0 && rs) return CFFM_ERR_UNSUPPORTED;                  // cffm_wide_regather_ok() guards the callers
     pick_nt(g.Pp / 16, &nblk, &NT);
@@ -4239,36 +4281,6 @@ static int conv_fwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
     return rc;
 }
 
-// argument blocks of the tap-split backward of layer l >= 1
-static void fill_taps_bwd_args(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int l, DgradArgs* da_, WgradArgs* wa_) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
-    float* gpart = (float*)(w + wl.gpart);
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const SlabRange& sr = sp.r[sp.conv0 + l];
-    int lg;
-    const int64_t Mtot = layer_rows(g, B, l, &lg);
-    WgradArgs& wa = *wa_;
-    wa.in = (const float*)(w + wl.C[l - 1]);
-    wa.dC = (const float*)(w + wl.dC[l]);
-    wa.slabW = gpart + sr.base; wa.slabB = wa.slabW + (tl.conv_b[l] - tl.conv_w[l]);
-    wa.slab_stride = sr.len; wa.slabB_stride = sr.len;
-    wa.Mtot = Mtot; wa.lgSo = lg;
-    wa.B = B; wa.P = g.P; wa.Pp = g.Pp; wa.F = g.F; wa.D = g.D; wa.act = g.act; wa.qblocks = 0;
-    DgradArgs& da = *da_;
-    da.dC = wa.dC;
-    da.W = theta + tl.conv_w[l];
-    da.Cprev = wa.in;
-    da.dt1 = (const float*)(w + wl.dt1);
-    da.dprev = (float*)(w + wl.dC[l - 1]);
-    da.Mtot = Mtot; da.lgSo = lg;
-    da.B = B; da.P = g.P; da.Pp = g.Pp; da.F = g.F; da.D = g.D; da.act = g.act;
-    da.t1w = 2 * g.D - 2; da.t1off = t1_offset(g, l);
-}
-
 template <int NT>
 static int launch_bwd_top(const BwdTopArgs& a, size_t lds, hipStream_t st) {
     return with_readme_act<NT>(a.hb.g.act, [&](auto act) {
@@ -4281,30 +4293,28 @@ static int launch_bwd_top(const BwdTopArgs& a, size_t lds, hipStream_t st) {
     });
 }
 
-// head backward + the top conv layers (+ the inner-branch backward) in one launch; *next_layer receives the highest
-// conv layer the caller still has to run (layers >= 1 below it, then layer 0)
-int cffm_bwd_top_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, int64_t B_global,
-                      bool local_sum, float* loss_out, bool unscaled, hipStream_t st, int* next_layer, const int32_t* rank_ids) {
-    const Geo g = make_geo(s);
+int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t st, int* next_layer) {
+    const cffm_shape_t* s = c.s;
+    const Geo& g = c.g;
+    const int32_t B = c.B;
     BwdTopArgs a;
     memset(&a, 0, sizeof(a));
-    fill_head_bwd_args(s, theta, ws, y, B, B_global, local_sum, loss_out, unscaled, &a.hb);
+    fill_head_bwd_args(s, c.theta, c.w, y, B, B_global, o.local_sum(), o.loss_out, o.unscaled, &a.hb);
     const int first = bwd_top_first_layer(s);
     a.wgrad_here = (top_wgrad_deferred(s, B) || bwd_fused01_ok(s, B)) ? 0 : 1;   // 0: a later launch computes them
     a.n_layers = 0;
     for (int l = g.live - 1; l >= first; --l) {
-        fill_taps_bwd_args(s, theta, ws, B, l, &a.d[a.n_layers], &a.w[a.n_layers]);
+        a.d[a.n_layers] = c.dgrad_args(l);
+        a.w[a.n_layers] = c.wgrad_args(l);
         a.lgSo[a.n_layers] = a.d[a.n_layers].lgSo;
         ++a.n_layers;
     }
-    a.n_inner = fill_inner_bwd_args(s, theta, ws, B, &a.ib);
+    a.n_inner = fill_inner_bwd_args(s, c.theta, c.w, B, &a.ib);
     a.ib.dout = nullptr;                                     // recomputed from (out, y, L): no dependency on the head role
     a.ib.y = y; a.ib.invB = 1.f / (float)B_global;
-    if (rank_ids != nullptr && s->F <= RANK_MAXF && (int64_t)B * s->F <= 4096) {
-        cffm_ws_layout_t wl;
-        cffm_ws_layout(s, B, &wl);
-        a.rank_ids = rank_ids; a.n_rows = B * s->F;
-        a.keys_sorted = (unsigned long long*)((char*)ws + wl.sort_vals);
+    if (o.rank_ids != nullptr && s->F <= RANK_MAXF && (int64_t)B * s->F <= 4096) {
+        a.rank_ids = o.rank_ids; a.n_rows = B * s->F;
+        a.keys_sorted = c.at<unsigned long long>(c.wl.sort_vals);
         a.n_keys = 256;
     }
     size_t lds = (size_t)(WGT_SUB * g.Pp) * 4 + 16;
@@ -4315,118 +4325,71 @@ int cffm_bwd_top_impl(const cffm_shape_t* s, const float* theta, void* ws, const
     return rc;
 }
 
-// which: bit 0 = weight/bias gradient, bit 1 = input gradient (the two only share their inputs, so the fused
-// step runs them on different streams)
-static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int l, hipStream_t st, int which = 3,
-                        bool* with_inner = nullptr, bool with_top_wgrad = false, const RowSrc* rs = nullptr) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
+// weight / bias gradient and input gradient of layer l: one launch where a fused or paired kernel exists, else one each
+int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o) {
+    const cffm_shape_t* s = c.s;
+    const Geo& g = c.g;
+    const int32_t B = c.B;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
-    char* w = (char*)ws;
-    float* gpart = (float*)(w + wl.gpart);
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const SlabRange& sr = sp.r[sp.conv0 + l];
+    const SlabRange& sr = c.conv_slab(l);
+    const RowSrc* rs = o.rs;
+    float* w0pack = c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr;
     int rc = 0;
-    if (l == 0 && which == 3 && conv0_fact_bwd_ok(g)) {   // factorised layer 0: weight, bias and input gradient in one kernel
-        DgradArgs a;
-        a.dC = (const float*)(w + wl.dC[0]);
-        a.W = theta + tl.conv_w[0];
-        a.Cprev = (const float*)(w + wl.Eo);
-        a.dt1 = (const float*)(w + wl.dt1);
-        a.dprev = (float*)(w + wl.dEo);
-        a.Mtot = layer_rows(g, B, 0, &a.lgSo);
-        a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
-        a.t1w = 2 * g.D - 2; a.t1off = 0;
-        float* slabW = gpart + sr.base;
-        DISPATCH_NT4(g.Pp / 16, rc = (launch_conv0_fact_bwd<NT_>(a, slabW, slabW + (tl.conv_b[0] - tl.conv_w[0]), sr.len, sr.nslab, st)));
+    if (l == 0 && conv0_fact_bwd_ok(g)) {   // factorised layer 0: weight, bias and input gradient in one kernel
+        const DgradArgs a = c.dgrad_args(0);
+        const WgradArgs wa = c.wgrad_args(0);
+        DISPATCH_NT4(g.Pp / 16, rc = (launch_conv0_fact_bwd<NT_>(a, wa.slabW, wa.slabB, sr.len, sr.nslab, st)));
         return rc;
     }
-    if (which == 3 && l >= 1 && g.Pp <= 64) {
-        int lg;
-        const int64_t Mtot = layer_rows(g, B, l, &lg);
-        if ((Mtot + sr.nslab - 1) / sr.nslab < 128) {          // the 256-thread weight-gradient variant: pair it up
-            WgradArgs wa;
-            wa.in = (const float*)(w + wl.C[l - 1]);
-            wa.dC = (const float*)(w + wl.dC[l]);
-            wa.slabW = gpart + sr.base; wa.slabB = wa.slabW + (tl.conv_b[l] - tl.conv_w[l]);
-            wa.slab_stride = sr.len; wa.slabB_stride = sr.len;
-            wa.Mtot = Mtot; wa.lgSo = lg;
-            wa.B = B; wa.P = g.P; wa.Pp = g.Pp; wa.F = g.F; wa.D = g.D; wa.act = g.act; wa.qblocks = 0;
-            DgradArgs da;
-            da.dC = wa.dC;
-            da.W = theta + tl.conv_w[l];
-            da.Cprev = wa.in;
-            da.dt1 = (const float*)(w + wl.dt1);
-            da.dprev = (float*)(w + wl.dC[l - 1]);
-            da.Mtot = Mtot; da.lgSo = lg;
-            da.B = B; da.P = g.P; da.Pp = g.Pp; da.F = g.F; da.D = g.D; da.act = g.act;
-            da.t1w = 2 * g.D - 2; da.t1off = t1_offset(g, l);
-            const int64_t wg16 = (Mtot + 15) / 16;
+    if (l >= 1 && g.Pp <= 64) {
+        const WgradArgs wa = c.wgrad_args(l);
+        if ((wa.Mtot + sr.nslab - 1) / sr.nslab < 128) {          // the 256-thread weight-gradient variant: pair it up
+            const DgradArgs da = c.dgrad_args(l);
+            const int64_t wg16 = (wa.Mtot + 15) / 16;
             InnerBwdArgs ib;
             int n_i = 0;
-            const bool inner = with_inner != nullptr && s->inner_conv;
-            if (inner) n_i = fill_inner_bwd_args(s, theta, ws, B, &ib);
+            const bool inner = o.carry_inner != nullptr && s->inner_conv;
+            if (inner) n_i = fill_inner_bwd_args(s, c.theta, c.w, B, &ib);
             TopWgrad tw;
             memset(&tw, 0, sizeof(tw));
-            if (with_top_wgrad) {                               // the fused top left its weight gradients to this launch
+            if (o.with_top_wgrad) {                             // the fused top left its weight gradients to this launch
                 int k = 0;
                 for (int lt = g.live - 1; lt > l && k < 2; --lt, ++k) {
-                    DgradArgs unused;
-                    fill_taps_bwd_args(s, theta, ws, B, lt, &unused, &tw.w[k]);
-                    tw.n[k] = sp.r[sp.conv0 + lt].nslab;
+                    tw.w[k] = c.wgrad_args(lt);
+                    tw.n[k] = c.conv_slab(lt).nslab;
                 }
             }
-            const TopWgrad* twp = with_top_wgrad ? &tw : nullptr;
+            const TopWgrad* twp = o.with_top_wgrad ? &tw : nullptr;
             if (wg16 >= 2 * 512) { DISPATCH_NT4(g.Pp / 16, rc = (launch_conv_bwd_pair<NT_, 2>(da, wa, sr.nslab, inner ? &ib : nullptr, n_i, st, twp))); }
             else { DISPATCH_NT4(g.Pp / 16, rc = (launch_conv_bwd_pair<NT_, 1>(da, wa, sr.nslab, inner ? &ib : nullptr, n_i, st, twp))); }
-            if (inner && !rc) *with_inner = true;
+            if (inner && !rc) *o.carry_inner = true;
             return rc;
         }
     }
-    if (which & 1) {   // weight / bias gradient
-        WgradArgs a;
-        a.in = (const float*)(w + (l == 0 ? wl.Eo : wl.C[l - 1]));
-        a.dC = (const float*)(w + wl.dC[l]);
-        a.slabW = gpart + sr.base; a.slabB = a.slabW + (tl.conv_b[l] - tl.conv_w[l]);
-        a.slab_stride = sr.len; a.slabB_stride = sr.len;
-        a.Mtot = layer_rows(g, B, l, &a.lgSo);
-        a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
-        int NT;
+    {   // weight / bias gradient
+        WgradArgs a = c.wgrad_args(l);
         if (g.Pp <= 64) {
             const int nt4 = g.Pp / 16;
             const int nsl = sr.nslab;
             if (l == 0) { DISPATCH_NT4(nt4, rc = (launch_wgrad_taps<NT_, true>(a, nsl, st))); }
             else { DISPATCH_NT4(nt4, rc = (launch_wgrad_taps<NT_, false>(a, nsl, st))); }
-            if (rc) return rc;
         } else {
-        pick_nt(g.Pp / 16, &a.qblocks, &NT);
-        if (l == 0 && conv0_fact_tile_ok(g) && g.D / 2 <= 32) {
-            if (rs) { a.in = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }
-            rc = launch_conv0_fact_tile_wgrad(a, sr.nslab, st);
+            int nblk, NT;
+            pick_nt(g.Pp / 16, &nblk, &NT);                 // (nblk is a.qblocks)
+            if (l == 0 && conv0_tile_wgrad_ok(g)) {
+                take_rows(a, &WgradArgs::in, rs);
+                rc = launch_conv0_fact_tile_wgrad(a, sr.nslab, st);
+            }
+            else if (l == 0 && rs) { rc = CFFM_ERR_UNSUPPORTED; }
+            else if (l == 0) { DISPATCH_NT68(NT, rc = (launch_wgrad<NT_>(a, st))); }
+            else if (NT == 8) { rc = launch_wgrad2<8>(a, st); }               // 128 x 128 output tile per workgroup
+            else if (NT == 6) { rc = launch_wgrad2<6>(a, st); }               // 128 x 96
+            else { rc = CFFM_ERR_UNSUPPORTED; }
         }
-        else if (l == 0 && rs) { rc = CFFM_ERR_UNSUPPORTED; }
-        else if (l == 0) { DISPATCH_NT68(NT, rc = (launch_wgrad<NT_>(a, st))); }
-        else if (NT == 8) { rc = launch_wgrad2<8>(a, st); }               // 128 x 128 output tile per workgroup
-        else if (NT == 6) { rc = launch_wgrad2<6>(a, st); }               // 128 x 96
-        else { rc = CFFM_ERR_UNSUPPORTED; }
         if (rc) return rc;
-        }
     }
-    if (which & 2) {   // input gradient
-        DgradArgs a;
-        a.dC = (const float*)(w + wl.dC[l]);
-        a.W = theta + tl.conv_w[l];
-        a.Cprev = (const float*)(w + (l == 0 ? wl.Eo : wl.C[l - 1]));
-        a.dt1 = (const float*)(w + wl.dt1);
-        a.dprev = (float*)(w + (l == 0 ? wl.dEo : wl.dC[l - 1]));
-        if (l >= 1 && wl.wb3_bytes > 0) a.wb3 = (void*)(w + wl.wb3);
-        if (l >= 1 && wl.relu0 > 0)           // wide shapes: the relu mask the forward of layer l-1 left (1/32 of the bytes of C_{l-1})
-            a.relu = (const uint16_t*)(w + wl.relu0 + relu_mask_off(g, B, l - 1));
-        a.Mtot = layer_rows(g, B, l, &a.lgSo);
-        a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
-        a.t1w = 2 * g.D - 2; a.t1off = t1_offset(g, l);
+    {   // input gradient
+        DgradArgs a = c.dgrad_args(l);
         int nblk, NT;
         if (g.Pp <= 64) {
             const int nt4 = g.Pp / 16;
@@ -4441,8 +4404,8 @@ static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
             return rc;
         }
         if (l == 0 && conv0_tile_dgrad2_ok(g)) {
-            if (rs) { a.Cprev = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }
-            return launch_conv0_fact_tile_dgrad(a, wl.w0pack_floats > 0 ? (float*)(w + wl.w0pack) : nullptr, st);
+            take_rows(a, &DgradArgs::Cprev, rs);
+            return launch_conv0_fact_tile_dgrad(a, w0pack, st);
         }
         if (l == 0 && rs) return CFFM_ERR_UNSUPPORTED;
         pick_nt(4 * g.Pp / 16, &nblk, &NT);
@@ -4454,89 +4417,61 @@ static int conv_bwd_any(const cffm_shape_t* s, const float* theta, void* ws, int
     return rc;
 }
 
-int cffm_conv_bwd_part(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, int which,
-                       hipStream_t st) {
-    return conv_bwd_any(s, theta, ws, B, layer, st, which);
-}
-
-int cffm_conv_bwd_with_inner(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, hipStream_t st,
-                             bool* inner_done) {
-    *inner_done = false;
-    return conv_bwd_any(s, theta, ws, B, layer, st, 3, inner_done);
-}
-
+// The exported per-stage entry points: each builds a context of its own.
 extern "C" int cffm_outer_conv0_fwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
     if (B <= 0 || !s->outer_conv) return 0;
-    return conv_fwd_any(s, theta, ws, B, 0, (hipStream_t)stream);
+    return cffm_conv_fwd_impl(StepCtx(s, B, theta, ws), 0, (hipStream_t)stream);
 }
 extern "C" int cffm_conv_fwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
     if (B <= 0 || !s->outer_conv) return 0;
     if (layer < 1) return CFFM_ERR_BAD_SHAPE;
-    return conv_fwd_any(s, theta, ws, B, layer, (hipStream_t)stream);
+    return cffm_conv_fwd_impl(StepCtx(s, B, theta, ws), layer, (hipStream_t)stream);
+}
+extern "C" int cffm_outer_conv0_bwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (B <= 0 || !s->outer_conv) return 0;
+    return cffm_conv_bwd_impl(StepCtx(s, B, theta, ws), 0, (hipStream_t)stream);
+}
+extern "C" int cffm_conv_bwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (B <= 0 || !s->outer_conv) return 0;
+    if (layer < 1) return CFFM_ERR_BAD_SHAPE;
+    return cffm_conv_bwd_impl(StepCtx(s, B, theta, ws), layer, (hipStream_t)stream);
 }
 // Wide shapes whose layer 0 runs the three tiled factorised kernels: those can take the outer rows straight from the table
 // (RowSrc), so the fused gather + inner-branch forward never writes Ei / Eo (cffm_gather_inner_fwd_wide, inner.hip)
 bool cffm_wide_regather_ok(const cffm_shape_t* s) {
     if (check_shape(s) || !s->inner_conv || !s->outer_conv) return false;
     const Geo g = make_geo(s);
-    return conv0_fact_tile_ok(g) && 2 * ((g.F + 3) & ~3) <= 4 * C0T_MAXKS && g.D / 2 <= 32 && 2 * g.F <= 64 &&
-           g.K == g.D && (g.K == 32 || g.K == 64) && g.F <= 32 && cffm_giw_lds_ok();
-}
-int cffm_outer_conv0_fwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st) {
-    if (B <= 0 || !s->outer_conv) return 0;
-    return conv_fwd_any(s, theta, ws, B, 0, st, rs);
-}
-int cffm_outer_conv0_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st) {
-    if (B <= 0 || !s->outer_conv) return 0;
-    return conv_bwd_any(s, theta, ws, B, 0, st, 3, nullptr, false, rs);
-}
-extern "C" int cffm_outer_conv0_bwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0 || !s->outer_conv) return 0;
-    return conv_bwd_any(s, theta, ws, B, 0, (hipStream_t)stream);
-}
-// the layer right below the fused top, carrying the top layers' weight gradients (top_wgrad_deferred)
-int cffm_conv_bwd_below_top(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, hipStream_t st) {
-    return conv_bwd_any(s, theta, ws, B, layer, st, 3, nullptr, true);
+    return conv0_tile_fwd_ok(g) && conv0_tile_wgrad_ok(g) && conv0_tile_dgrad2_ok(g) && g.K == g.D && (g.K == 32 || g.K == 64) &&
+           cffm_giw_lds_ok();
 }
 
 // bwd_fused01_ok: layers 3..0 below the fused top in one launch (conv01_bwd_kernel)
-int cffm_conv01_bwd_impl(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, hipStream_t st) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
+int cffm_conv01_bwd_impl(const StepCtx& c, hipStream_t st) {
+    const cffm_shape_t* s = c.s;
+    const Geo& g = c.g;
+    const int32_t B = c.B;
     if (!bwd_fused01_ok(s, B) || g.live != 4 || !conv0_fact_bwd_ok(g)) return CFFM_ERR_UNSUPPORTED;
-    char* w = (char*)ws;
-    float* gpart = (float*)(w + wl.gpart);
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
     Conv01Args a;
     memset(&a, 0, sizeof(a));
-    const SlabRange& sr = sp.r[sp.conv0];
-    a.d0.dC = (const float*)(w + wl.dC[0]);
-    a.d0.W = theta + tl.conv_w[0];
-    a.d0.Cprev = (const float*)(w + wl.Eo);
-    a.d0.dt1 = (const float*)(w + wl.dt1);
-    a.d0.dprev = (float*)(w + wl.dEo);
-    a.d0.Mtot = layer_rows(g, B, 0, &a.d0.lgSo);
-    a.d0.B = B; a.d0.P = g.P; a.d0.Pp = g.Pp; a.d0.F = g.F; a.d0.D = g.D; a.d0.act = g.act;
-    a.d0.t1w = 2 * g.D - 2; a.d0.t1off = 0;
-    a.slabW0 = gpart + sr.base; a.slabB0 = a.slabW0 + (tl.conv_b[0] - tl.conv_w[0]); a.stride0 = sr.len;
-    DgradArgs unused;
-    fill_taps_bwd_args(s, theta, ws, B, 1, &a.d1, &a.w1);
-    fill_taps_bwd_args(s, theta, ws, B, 2, &unused, &a.w2);
-    fill_taps_bwd_args(s, theta, ws, B, 3, &unused, &a.w3);
-    a.n2 = sp.r[sp.conv0 + 2].nslab; a.n3 = sp.r[sp.conv0 + 3].nslab;
-    if (sp.r[sp.conv0].nslab != 256 || sp.r[sp.conv0 + 1].nslab != 256 || a.n2 > 256 || a.n3 > 256 ||
+    const WgradArgs w0 = c.wgrad_args(0);
+    a.d0 = c.dgrad_args(0);
+    a.slabW0 = w0.slabW; a.slabB0 = w0.slabB; a.stride0 = w0.slab_stride;
+    a.d1 = c.dgrad_args(1);
+    a.w1 = c.wgrad_args(1); a.w2 = c.wgrad_args(2); a.w3 = c.wgrad_args(3);
+    a.n2 = c.conv_slab(2).nslab; a.n3 = c.conv_slab(3).nslab;
+    if (c.conv_slab(0).nslab != 256 || c.conv_slab(1).nslab != 256 || a.n2 > 256 || a.n3 > 256 ||
         (int64_t)a.n2 * CFFM_TOP_SLAB_ROWS < a.w2.Mtot || (int64_t)a.n3 * CFFM_TOP_SLAB_ROWS < a.w3.Mtot)
         return CFFM_ERR_UNSUPPORTED;             // one layer-0/1 slab per workgroup, the 64-row slabs cover layers 2 and 3
-    // Host-side guard (round-2 review, weak #6): the argument block starts zero-filled, and a role that dereferenced a member
-    // nobody assigned would fault the GPU at address 0.  Every pointer ANY group of the kernel can dereference is checked here,
+    // Host-side guard: a role that dereferenced a null member would fault the GPU at address 0.  Every pointer ANY group of the
+    // kernel can dereference is checked here (theta or the workspace may be null even though the builders assign every member),
     // together with the row counts its clamped addresses are derived from (m = Mtot - 1 for rows past the end).
     {
         const void* must[] = {a.d0.dC, a.d0.W, a.d0.Cprev, a.d0.dt1, a.d0.dprev, a.slabW0, a.slabB0, a.d1.dC, a.d1.W, a.d1.Cprev,
@@ -4566,14 +4501,6 @@ int cffm_conv01_bwd_impl(const cffm_shape_t* s, const float* theta, void* ws, in
     return 0;
 }
 
-extern "C" int cffm_conv_bwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, void* stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0 || !s->outer_conv) return 0;
-    if (layer < 1) return CFFM_ERR_BAD_SHAPE;
-    return conv_bwd_any(s, theta, ws, B, layer, (hipStream_t)stream);
-}
-
 // ---- fused forward (one launch) --------------------------------------------------------------------------------------
 bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B) {
     const Geo g = make_geo(s);
@@ -4593,57 +4520,49 @@ static int launch_fwd_all(const FwdAllArgs& fa, size_t lds, hipStream_t st) {
     });
 }
 
-int cffm_fwd_all_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
-                      const float* y, int32_t B, void* ws, hipStream_t st, bool rank_keys) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
+int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, const float* y, hipStream_t st,
+                      bool rank_keys) {
+    const cffm_shape_t* s = c.s;
+    const Geo& g = c.g;
+    const int32_t B = c.B;
+    const float* theta = c.theta;
+    const cffm_theta_layout_t& tl = c.tl;
+    const cffm_ws_layout_t& wl = c.wl;
     FwdAllArgs fa;
     // inner branch + gather
-    fa.inner.g = g; fa.inner.Ei = (const float*)(w + wl.Ei);
+    fa.inner.g = g; fa.inner.Ei = c.at<const float>(wl.Ei);
     fa.inner.cw = theta + tl.inner_cw; fa.inner.cb = theta + tl.inner_cb; fa.inner.wd = theta + tl.inner_dw;
-    fa.inner.bd = theta + tl.inner_db; fa.inner.inner_out = (float*)(w + wl.inner_out);
+    fa.inner.bd = theta + tl.inner_db; fa.inner.inner_out = c.at(wl.inner_out);
     fa.inner.fg.ids = ids; fa.inner.fg.inner = tab->inner_emb; fa.inner.fg.outer = tab->outer_emb;
-    fa.inner.fg.fbias = tab->feat_bias; fa.inner.fg.Ei = (float*)(w + wl.Ei); fa.inner.fg.Eo = (float*)(w + wl.Eo);
-    fa.inner.fg.fb = (float*)(w + wl.fb); fa.inner.fg.keys = (unsigned long long*)(w + wl.sort_keys);
+    fa.inner.fg.fbias = tab->feat_bias; fa.inner.fg.Ei = c.at(wl.Ei); fa.inner.fg.Eo = c.at(wl.Eo);
+    fa.inner.fg.fb = c.at(wl.fb); fa.inner.fg.keys = c.at<unsigned long long>(wl.sort_keys);
     fa.inner.fg.M = s->M; fa.inner.fg.D = s->D;
     // conv stack
-    for (int l = 0; l < g.live; ++l) {
-        ConvArgs& a = fa.conv[l];
-        a.in = (const float*)(w + (l == 0 ? wl.Eo : wl.C[l - 1]));
-        a.W = theta + tl.conv_w[l]; a.bias = theta + tl.conv_b[l];
-        a.out = (float*)(w + wl.C[l]);
-        a.Mtot = layer_rows(g, B, l, &a.lgSo);
-        a.B = B; a.P = g.P; a.Pp = g.Pp; a.F = g.F; a.D = g.D; a.act = g.act;
-    }
+    for (int l = 0; l < g.live; ++l) fa.conv[l] = c.conv_args(l);
     // head
     HeadArgs& h = fa.head;
     h.g = g; h.B = B;
-    h.Eo = (const float*)(w + wl.Eo); h.fb = (const float*)(w + wl.fb); h.inner_out = (const float*)(w + wl.inner_out);
-    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) h.C[l] = (const float*)(w + wl.C[l]);
+    h.Eo = c.at<const float>(wl.Eo); h.fb = c.at<const float>(wl.fb); h.inner_out = c.at<const float>(wl.inner_out);
+    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) h.C[l] = c.at<const float>(wl.C[l]);
     h.d1_w = theta + tl.d1_w; h.d1_b = theta + tl.d1_b; h.d2_w = theta + tl.d2_w; h.d2_b = theta + tl.d2_b;
     h.att_W = theta + tl.att_W; h.att_b = theta + tl.att_b; h.lin_w = theta + tl.lin_w; h.lin_b = theta + tl.lin_b;
     h.bias = theta + tl.bias;
     h.y = y;
-    h.t1 = (float*)(w + wl.t1); h.h1 = (float*)(w + wl.h1); h.att = (float*)(w + wl.att);
-    h.out = (float*)(w + wl.out); h.sqerr = (float*)(w + wl.sqerr);
+    h.t1 = c.at(wl.t1); h.h1 = c.at(wl.h1); h.att = c.at(wl.att);
+    h.out = c.at(wl.out); h.sqerr = c.at(wl.sqerr);
     h.loss = s->loss; h.inner_conv = s->inner_conv; h.outer_conv = s->outer_conv;
     // sort workgroup
-    fa.ids = ids; fa.keys_sorted = (unsigned long long*)(w + wl.sort_vals);
+    fa.ids = ids; fa.keys_sorted = c.at<unsigned long long>(wl.sort_vals);
     fa.live = g.live; fa.n_rows = B * s->F; fa.B = B;
     fa.rank_keys = rank_keys ? 1 : 0;
     int bits = 1;
     while ((1ll << bits) <= (long long)s->M && bits < 31) ++bits;
     fa.id_bits = bits;
     const int S = g.D / 2, PP = g.Pp;
+    // every phase's scratch starts at 0: the launch gets the largest
+    const size_t l_taps = conv_fwd_taps_scratch(PP, 4) + 64;
     size_t lds = inner_fwd_lds(g);
-    const size_t l_fact = (size_t)(4 * PP * PP + 2 * g.F * (S * PP + 16) + g.F * (g.D + 1)) * 4 + 16;
-    size_t l_taps = (size_t)4 * PP * (PP + 4) * 4;
-    const size_t l_red = (size_t)4 * 4 * (PP / 16) * 64 * 16;
-    if (l_red > l_taps) l_taps = l_red;
-    l_taps += 64;
-    if (l_fact > lds) lds = l_fact;
+    if (conv0_fact_fwd_lds(PP, g.F, g.D) > lds) lds = conv0_fact_fwd_lds(PP, g.F, g.D);
     if (l_taps > lds) lds = l_taps;
     if (head_fwd_lds(g) > lds) lds = head_fwd_lds(g);
     // LDS-resident activations: C_0 above every phase's scratch, C_1.. above the scratch of the tap kernels / the head
@@ -4663,7 +4582,7 @@ int cffm_fwd_all_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const flo
         }
     }
     {   // the inner branch (and the key placement) must fit into the T planes, below the embedding tile
-        const size_t t_off = (size_t)4 * PP * PP * 4, t_bytes = (size_t)2 * g.F * (S * PP + 16) * 4;
+        const size_t t_off = conv0_fact_t_off(PP), t_bytes = conv0_fact_t_bytes(PP, g.F, g.D);
         size_t need = inner_fwd_lds(g);
         if (need < (size_t)8 * RANK_MAXF * 4) need = (size_t)8 * RANK_MAXF * 4;
         fa.early_off = (need <= t_bytes && ids != nullptr) ? (int)t_off : 0;

@@ -20,23 +20,65 @@ int cffm_sparse_adagrad_impl(const cffm_shape_t* s, const cffm_tables_t* tab, co
 // Ei/Eo/fb and the packed sort keys in the workspace, so no separate gather launch is needed
 int cffm_inner_fwd_impl(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const cffm_tables_t* tab,
                         const int32_t* ids, hipStream_t st);
-// one half of a conv layer's backward: which & 1 = weight/bias gradient, which & 2 = input gradient
-int cffm_conv_bwd_part(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, int which,
-                       hipStream_t st);
 // fused single-GPU update (both tables branches on): slab reduction + dense Adagrad and the sorted sparse table update
 // as two roles of one launch; the keys must already be sorted in ws.sort_vals
 int cffm_update_all(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
                     float* theta_acc, float* grad, void* ws, int32_t B, hipStream_t st);
-// fused top of the backward (bwd_top_ok(s, B)): head + top conv layers + inner branch in one launch
-int cffm_bwd_top_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, int64_t B_global,
-                      bool local_sum, float* loss_out, bool unscaled, hipStream_t st, int* next_layer,
-                      const int32_t* rank_ids = nullptr);
-// backward of conv layer `layer`; where the paired launch is available it also carries the inner-branch backward
-// (*inner_done = true), which the caller must then not launch again
-int cffm_conv01_bwd_impl(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, hipStream_t st);
-int cffm_conv_bwd_below_top(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, hipStream_t st);
-int cffm_conv_bwd_with_inner(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, int32_t layer, hipStream_t st,
-                             bool* inner_done);
+// ---- one context per ABI call: what every conv launch of a step derives from (s, B, theta, ws) -----------------------------
+// Built once by the entry point (shape checked, B >= 1) and handed down; conv_args / dgrad_args / wgrad_args (conv.hip) return the
+// complete argument block of layer l, every optional member decided there and nowhere else.
+struct ConvArgs; struct DgradArgs; struct WgradArgs;
+int cffm_ws_layout_from(const cffm_shape_t* s, int32_t B, const cffm_theta_layout_t& tl, const SlabPlan& sp, cffm_ws_layout_t* out);
+struct StepCtx {
+    const cffm_shape_t* s;
+    int32_t B;
+    const float* theta;
+    char* w;                     // workspace base
+    Geo g;
+    cffm_theta_layout_t tl;
+    cffm_ws_layout_t wl;
+    SlabPlan sp;
+    StepCtx(const cffm_shape_t* s_, int32_t B_, const float* theta_, void* ws) : s(s_), B(B_), theta(theta_), w((char*)ws), g(make_geo(s_)) {
+        cffm_theta_layout(s, &tl);
+        make_slab_plan(s, B, tl, &sp);
+        cffm_ws_layout_from(s, B, tl, sp, &wl);
+    }
+    template <class T = float> T* at(int64_t off) const { return reinterpret_cast<T*>(w + off); }
+    const SlabRange& conv_slab(int l) const { return sp.r[sp.conv0 + l]; }
+    ConvArgs conv_args(int l) const;
+    DgradArgs dgrad_args(int l) const;
+    WgradArgs wgrad_args(int l) const;
+};
+// wide shapes whose forward did not materialise Ei / Eo: the tables (or, stride / records > 0, the packed records) the backward
+// re-reads its rows from
+struct RowTables {
+    const cffm_tables_t* tab = nullptr;
+    const int32_t* ids = nullptr;
+    int stride = 0, records = 0;
+};
+struct BwdOpts {
+    float* adagrad_theta = nullptr;      // both non-NULL (single-GPU step): the dense Adagrad update is folded into the slab
+    float* adagrad_acc = nullptr;        // reduction, and the loss is summed locally
+    float* loss_out = nullptr;           // non-NULL: the loss is written here (and summed locally)
+    bool local_sum() const { return adagrad_theta != nullptr || loss_out != nullptr; }
+    bool unscaled = false;               // data-parallel: dL/dout without the 1/L of the RMSE-style loss
+    bool skip_reduce = false;            // the caller reduces the slabs together with the table update
+    const int32_t* rank_ids = nullptr;   // non-NULL: the fused top also places the sort keys the forward left out
+    RowTables rows;
+};
+struct ConvBwdOpts {
+    bool* carry_inner = nullptr;         // non-NULL: a paired launch may carry the inner-branch backward; *carry_inner = true if it did
+    bool with_top_wgrad = false;         // the fused top left its weight gradients to this launch (top_wgrad_deferred)
+    const RowSrc* rs = nullptr;          // layer 0 of the wide shapes: rows straight from the table
+};
+// forward / backward of conv layer l (0 = the outer-product layer); the exported per-stage entry points wrap these
+int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs = nullptr);
+int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o = ConvBwdOpts());
+// fused top of the backward (bwd_top_ok(s, B)): head + top conv layers + inner branch in one launch; *next_layer receives the
+// highest conv layer the caller still has to run
+int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t st, int* next_layer);
+// bwd_fused01_ok: layers 3..0 below the fused top in one launch
+int cffm_conv01_bwd_impl(const StepCtx& c, hipStream_t st);
 // the two halves of the sparse update: stable sort of the packed keys, then the segment-sum + Adagrad sweep
 int cffm_sort_keys_impl(const cffm_shape_t* s, const int32_t* ids, int64_t n_rows, void* ws, int32_t B_ws, bool prepacked,
                         hipStream_t st, int64_t id_stride = 1);
@@ -57,8 +99,8 @@ int cffm_pack_rows(const cffm_shape_t* s, const int32_t* ids, int32_t B, const f
                    const float* scalars, float* sum_dst, float* rows, hipStream_t st);
 // whole forward of the fused step in one launch (+ the key sort); only for shapes cffm_fwd_all_ok() accepts
 bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B);
-int cffm_fwd_all_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
-                      const float* y, int32_t B, void* ws, hipStream_t st, bool rank_keys = true);
+int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, const float* y, hipStream_t st,
+                      bool rank_keys);
 // CFFM_LOSS_SQUARE_L2: tables updated densely with g = scatter(row grads) + lamda * w (feature_bias stays sparse)
 int cffm_tables_adagrad_l2(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids,
                            int64_t n_rows, void* ws, int32_t B_ws, hipStream_t st);
@@ -77,8 +119,6 @@ bool cffm_giw_lds_ok();     // the fused gather's LDS addressing assumption hold
 // received: tab->inner_emb = records, outer_emb = records + K, feat_bias = records + K + D) with tab_rows records; ids = slot -> record
 int cffm_gather_inner_fwd_wide(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids, int32_t B,
                                void* ws, hipStream_t st, int tab_stride = 0, int tab_rows = 0);
-int cffm_outer_conv0_fwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st);
-int cffm_outer_conv0_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st);
 int cffm_inner_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st);
 // s0_ready: ws.t1[:, 0:D] already holds the s0 pool (the fused gather computed it): ws.Eo is not read
 int cffm_head_fwd_impl2(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, bool do_sum, bool s0_ready,
