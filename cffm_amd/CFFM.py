@@ -131,7 +131,8 @@ class CFFM(object):
         self.batch_rng = np.random if batch_rng is None else batch_rng
         self.batch_starts = []
         # multi-GPU (set by build_graph under torch.distributed): one process per GPU, data parallel over the batch
-        self.world, self.rank, self._dp = 1, 0, None
+        # _sh: CFFM_TABLES=sharded at world size > 1 - cffm_amd.dist.ShardedStep over this rank's rows of the tables
+        self.world, self.rank, self._dp, self._sh = 1, 0, None, None
 
     # ---- engine / data residency -----------------------------------------------------------------------
     def build_graph(self):
@@ -142,6 +143,8 @@ class CFFM(object):
         dev = int(os.environ.get('LOCAL_RANK', torch.cuda.current_device() if torch.cuda.is_available() else 0))
         if torch.cuda.is_available():
             torch.cuda.set_device(dev)
+        if os.environ.get('CFFM_TABLES', 'replicated') == 'sharded':
+            return self._build_sharded(dev)
         self.engine = self._make_engine(dev)
         if self.pretrain_flag > 0:
             self.load(self.save_file)
@@ -156,28 +159,75 @@ class CFFM(object):
         from .engine import HipEngine
         return HipEngine(self.config, seed=self.random_seed, device='cuda:%d' % dev)
 
+    # CFFM_TABLES=sharded: (local config, seed, rank, world, global rows) -> the engine over THIS rank's rows of the tables
+    # (global rows rank, rank + world, ...), drawn by global row; the CPU tests plug an oracle stand-in built from
+    # spec.table_rows in here, the product path is HipEngine(params='device_rows')
+    sharded_engine_factory = None
+
+    def _join_group(self, device):
+        """(world, rank) of the process group: the one the caller initialised, or the launcher's (RANK / WORLD_SIZE in the
+        environment, torch.distributed.run); (1, 0) without either."""
+        import torch
+        import torch.distributed as dist
+        if not dist.is_available():
+            return 1, 0
+        if not dist.is_initialized():
+            if int(os.environ.get('WORLD_SIZE', '1')) <= 1:
+                return 1, 0
+            on_gpu = torch.cuda.is_available()
+            dist.init_process_group('nccl' if on_gpu else 'gloo', device_id=device if on_gpu else None)
+        return dist.get_world_size(), dist.get_rank()
+
+    def _build_sharded(self, dev):
+        """CFFM_TABLES=sharded: row r of the three tables and of their Adagrad slots lives on rank r % world at local row
+        r // world (vocabularies beyond one GPU's HBM), the dense parameters are replicated (rank 0's are broadcast), and the
+        tables are drawn BY GLOBAL ROW from --random_seed, so every world size trains the same model: at world size 1 this is a
+        plain engine whose tables are drawn the same way, the single-process twin of every multi-rank run.  train() steps
+        through cffm_amd.dist.ShardedStep with the routing plan one step ahead; evaluate() / predict_split() sweep a
+        contiguous share of the rows per rank through its forward-only path."""
+        import copy
+        import torch
+        from .dist import ShardedStep, local_rows_count
+        self.world, self.rank = self._join_group(torch.device('cuda', dev) if torch.cuda.is_available() else None)
+        if self.world > 1:
+            # what the row-sharded step does not implement is refused here, by name, before the first collective
+            if self.optimizer_type != 'AdagradOptimizer':
+                raise ValueError('CFFM_TABLES=sharded: the multi-GPU update is Adagrad only; --optimizer %s runs on one GPU'
+                                 % self.optimizer_type)
+            if self.loss_type == 'hybrid':
+                raise ValueError('CFFM_TABLES=sharded: --loss_type hybrid runs on one GPU only')
+            if self.loss_type == 'square_loss' and self.lamda_bilinear > 0:
+                raise ValueError('CFFM_TABLES=sharded: --lamda > 0 (a regulariser over whole tables) runs on one GPU only')
+            if self.batch_size % self.world:
+                raise ValueError('--batch_size %d is not a multiple of the %d ranks' % (self.batch_size, self.world))
+            if self.features_M < self.world:
+                raise ValueError('CFFM_TABLES=sharded: %d features over %d ranks leaves a rank without rows' % (self.features_M, self.world))
+        cfg = copy.copy(self.config)
+        cfg.M = local_rows_count(self.features_M, self.rank, self.world)
+        if self.sharded_engine_factory is not None:
+            self.engine = type(self).sharded_engine_factory(cfg, self.random_seed, self.rank, self.world, self.features_M)
+        else:
+            from .engine import HipEngine
+            self.engine = HipEngine(cfg, params='device_rows', seed=self.random_seed, table_seed=self.random_seed,
+                                    table_rows=(self.rank, self.world), device='cuda:%d' % dev)
+        if self.world > 1:
+            self._sh = ShardedStep(self.engine, M_global=self.features_M)
+        if self.pretrain_flag > 0:
+            self.load(self.save_file)
+        return self.engine
+
     def _setup_dist(self):
         """One process per GPU under torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK in the environment), or a process
         group the caller initialised: the train step becomes cffm_amd.dist.DataParallelStep - every rank its slice of the
         SAME global batch, two collectives per step, replicas bit-identical (rank 0's parameters are broadcast at
         construction) - and evaluate() splits the rows over the ranks and all-reduces the three metric sums.  The reference
         is single-device (CFFM.py:19 pins one GPU), so this replaces nothing in it; at world size 1 nothing changes."""
-        import torch
-        import torch.distributed as dist
-        if not dist.is_available():
-            return
-        if not dist.is_initialized():
-            if int(os.environ.get('WORLD_SIZE', '1')) <= 1:
-                return
-            on_gpu = torch.cuda.is_available()
-            dist.init_process_group('nccl' if on_gpu else 'gloo',
-                                    device_id=self.engine.device if on_gpu else None)
-        self.world, self.rank = dist.get_world_size(), dist.get_rank()
+        self.world, self.rank = self._join_group(self.engine.device)
         if self.world == 1:
             return
-        if os.environ.get('CFFM_TABLES', 'replicated') != 'replicated':
-            raise NotImplementedError('CFFM.train() runs replicated tables (DataParallelStep); row-sharded tables are driven '
-                                      'through cffm_amd.dist.ShardedStep (bench.py --tables sharded)')
+        tables = os.environ.get('CFFM_TABLES', 'replicated')
+        if tables != 'replicated':                     # 'sharded' went through _build_sharded
+            raise ValueError("CFFM_TABLES=%r: the accepted values are 'replicated' (default) and 'sharded'" % (tables,))
         if self.batch_size % self.world:
             raise ValueError('--batch_size %d is not a multiple of the %d ranks' % (self.batch_size, self.world))
         from .dist import DataParallelStep
@@ -258,9 +308,18 @@ class CFFM(object):
                     starts = st.cpu().numpy()
                 self.batch_starts.append(np.asarray(starts, dtype=np.int64))
                 per = self.batch_size // self.world
-                for start in starts:
+                for i, start in enumerate(starts):
                     start = int(start)
-                    if self._dp is not None:
+                    if self._sh is not None:
+                        # this rank's slice of the batch, and of the NEXT one: its routing plan (and the read of the
+                        # per-owner counts) is issued before this step's kernels
+                        lo = start + self.rank * per
+                        nxt = None
+                        if i + 1 < len(starts):
+                            nlo = int(starts[i + 1]) + self.rank * per
+                            nxt = ids[nlo:nlo + per]
+                        self._sh.train_step(ids[lo:lo + per], y[lo:lo + per], next_ids=nxt)
+                    elif self._dp is not None:
                         lo = start + self.rank * per
                         self._dp.train_step(ids[lo:lo + per], y[lo:lo + per])
                     else:
@@ -288,9 +347,13 @@ class CFFM(object):
                         epoch + 1, self.examples_per_sec[-1], ' (%d ranks)' % self.world if self.world > 1 else ''))
                 if self.eva_termination(self.valid_rmse):
                     break
-                if self.pretrain_flag < 0 and self.rank == 0:        # the replicas are identical: rank 0 writes
-                    logging.info("Save model to file as pretrain.")
+                if self.pretrain_flag < 0 and (self.rank == 0 or self._sh is not None):
+                    # replicated tables: the replicas are identical, rank 0 writes; row-sharded: every rank writes its shard
+                    self._info("Save model to file as pretrain.")
                     self.save(self.save_file)
+            if self._sh is not None and self.verbose > 0:
+                self._info("Row-sharded tables over %d ranks: %d train steps ran on a routing plan issued one step ahead (plans_reused)"
+                           % (self.world, self._sh.plans_reused))
         finally:
             # the reference re-binds data.Train_data['X'] / ['Y'] to the shuffled lists every epoch (CFFM.py:183); the device
             # copy is what the loop trains on, so the caller's lists are brought to the same (composed) order once, here
@@ -312,10 +375,14 @@ class CFFM(object):
         num_example = int(ids.shape[0])
         if num_example == 0:
             raise ValueError('evaluate() needs at least one example')
-        if self.world > 1:
+        if self._sh is not None:
+            # row-sharded tables: a forward needs the owners of its rows, so every rank runs the SAME number of rounds of
+            # collectives - what the largest share (rank 0's) needs; a rank whose rows have run out joins with empty blocks
+            r0, r1, block, n_blocks = self._share(num_example)
+            sums = self._all_reduce_sum(self._sh.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block, n_blocks))
+        elif self.world > 1:
             # the forward is per example: every rank sweeps its contiguous share of the rows, the three sums are added up
-            share = -(-num_example // self.world)
-            r0, r1 = min(self.rank * share, num_example), min((self.rank + 1) * share, num_example)
+            r0, r1, _, _ = self._share(num_example)
             sums = self._all_reduce_sum(self.engine.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block=max(int(self.batch_size), 8192)))
         else:
             sums = self.engine.eval_sums(ids, y, lo, hi, block=max(int(self.batch_size), 8192))
@@ -329,10 +396,36 @@ class CFFM(object):
         R2 = 1.0 - ss_res / ss_tot if ss_tot > 0 else (1.0 if ss_res == 0 else 0.0)    # sklearn r2_score, CFFM.py:614
         return RMSE, R2
 
+    def _share(self, num_example):
+        """This rank's contiguous share [r0, r1) of a split's rows, the block size of the sweep and the number of blocks the
+        LARGEST share takes (shares only get shorter with the rank, so that is rank 0's)."""
+        share = -(-num_example // self.world)
+        r0, r1 = min(self.rank * share, num_example), min((self.rank + 1) * share, num_example)
+        block = max(int(self.batch_size), 8192)
+        return r0, r1, block, -(-share // block)
+
     def predict_split(self, data):
         """Raw (unclipped) predictions of a split as a host float64 array, in the split's current order."""
         import torch
         ids, _, _ = self._device_split(data)
+        if self._sh is not None:
+            # every rank predicts its share (in matched rounds, as evaluate() does) and gets the whole split back
+            import torch.distributed as dist
+            n = int(ids.shape[0])
+            r0, r1, block, n_blocks = self._share(n)
+            share = -(-n // self.world)
+            mine = None
+            for b in range(n_blocks):
+                s0, s1 = min(r0 + b * block, r1), min(r0 + (b + 1) * block, r1)
+                out = self._sh.predict(ids[s0:s1])
+                if mine is None:
+                    mine = out.new_zeros(share)
+                mine[s0 - r0:s1 - r0] = out
+            if mine is None:
+                return np.zeros((0,))
+            full = mine.new_empty(share * self.world)
+            dist.all_gather_into_tensor(full, mine)
+            return full[:n].cpu().numpy().astype(np.float64)
         block = max(int(self.batch_size), 8192)
         outs = [self.engine.predict(ids[s:s + block]) for s in range(0, ids.shape[0], block)]
         return torch.cat(outs).cpu().numpy().astype(np.float64) if outs else np.zeros((0,))
@@ -379,13 +472,18 @@ class CFFM(object):
         return total_parameters
 
     def create_save_folder(self, save_file):
-        if not os.path.exists(save_file):
-            os.makedirs(save_file)
+        os.makedirs(save_file, exist_ok=True)          # every rank of a job names the same folder: no exists-then-create race
 
     # ---- checkpoint: this model's tensors AND the optimizer slots (the reference restore is broken, Q7) ---------------
     # A plain dict of tensors and scalars: loads with torch.load(weights_only=True), no pickled code.
     def save(self, save_file):
         import torch
+        if self._sh is not None:                       # row-sharded: one file per rank (cffm_amd.dist.save_sharded)
+            import torch.distributed as dist
+            from .dist import save_sharded
+            save_sharded(self.engine, save_file, self.rank, self.world, opt_step=int(getattr(self.engine, 'opt_step', 0)))
+            dist.barrier()                             # on return every shard is on disk (a restore reads shard 0 on every rank)
+            return
         t = lambda d: None if d is None else {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in d.items()}
         cfg = {k: (v if isinstance(v, (int, float, str)) else float(v)) for k, v in self.config.__dict__.items()}
         torch.save({'format': 2, 'config': cfg, 'params': t(self.engine.export_params()),
@@ -395,6 +493,10 @@ class CFFM(object):
 
     def load(self, save_file):
         import torch
+        if self._sh is not None:                       # the shards a run at THIS world size wrote; dist.merge_shards for world 1
+            from .dist import load_sharded
+            self.engine.opt_step = load_sharded(self.engine, save_file, self.rank, self.world)
+            return
         blob = torch.load(save_file + '.pt', weights_only=True)
         n = lambda d: None if d is None else {k: (v.numpy() if hasattr(v, 'numpy') else np.asarray(v)) for k, v in d.items()}
         saved = blob.get('config', {})

@@ -350,7 +350,7 @@ class ShardedStep(object):
         G = self.world
         B, F = ids.shape
         dev = ids.device
-        if self.dedup and hasattr(self.c, 'shard_plan') and self.M_global is not None:
+        if B > 0 and self.dedup and hasattr(self.c, 'shard_plan') and self.M_global is not None:
             # the product path: five small launches in the library instead of ~15 torch operations with int64 temporaries
             local_ids, order, uniq, pos, send_rows, counts = self.c.shard_plan(ids, G, self.M_global)
         else:
@@ -402,6 +402,45 @@ class ShardedStep(object):
         recv = self._a2a(rows[:u], sc, rc)
         return c.dp_apply(grad, recv, Bg)
 
+    # ---- forward only: what evaluate() / predict_split() of a row-sharded model run ------------------------------------------
+    def predict(self, ids):
+        """Predictions [B] of THIS rank's rows ids [B,F]: plan -> all-to-all of the distinct rows -> gather_packed on the owner ->
+        all-to-all back -> the forward on the received records (in place on the wide shapes, staged otherwise).  A collective
+        call: every rank of the group calls it the same number of times, a rank with nothing to predict with an EMPTY batch
+        ([0,F]) - it still answers the lookups of the others.  The plan prefetched for the next train step is left alone."""
+        c = self.c
+        plan = self.plan(ids)
+        B = plan.B
+        sc, rc = plan.counts()
+        u = sum(sc)
+        asked = self._a2a(plan.send_rows[:u], sc, rc)
+        got = self._a2a(c.gather_packed(asked), rc, sc)                  # [u, K+D+4] in distinct-id order
+        if B == 0:
+            return got.new_empty(0)
+        if hasattr(c, 'packed_ok') and c.packed_ok():
+            c.forward_packed(got, plan.pos, None, B)
+        else:
+            c.stage_packed(got, plan.pos, B)
+            c.forward_staged(None, B)
+        return c.predictions(B)
+
+    def eval_sums(self, ids, y, lo, hi, block, n_blocks):
+        """evaluate()'s sweep over this rank's rows: blocks of ``block`` rows through predict() and the clip + float64 metric sums
+        of cffm_eval_sums.  Runs EXACTLY n_blocks rounds of collectives - the caller passes the maximum over the ranks; a rank
+        whose rows run out takes part with empty blocks, so the all-to-alls stay matched.  Returns this rank's
+        [sum (y - p)^2, sum y, sum y^2] (float64, on the device); the caller adds the ranks up."""
+        n = int(ids.shape[0])
+        if n > int(block) * int(n_blocks):
+            raise ValueError('eval_sums: %d rows do not fit %d blocks of %d' % (n, n_blocks, block))
+        y = y.reshape(-1)
+        sums = torch.zeros(3, dtype=torch.float64, device=ids.device)
+        for b in range(int(n_blocks)):
+            s0, s1 = min(b * block, n), min((b + 1) * block, n)
+            out = self.predict(ids[s0:s1])
+            if s1 > s0:
+                self.c.eval_sums_add(out, y[s0:s1], lo, hi, sums)
+        return sums
+
 
 # ---- checkpoint of a row-sharded model (SURVEY 8f N3: "sharded-table aware") ----------------------------------------------
 # Every rank writes its own shard of the three tables and of their optimizer slots (local rows rank, rank + G, ...); the
@@ -423,7 +462,8 @@ def save_sharded(engine, path, rank, world, opt_step=0):
 
 
 def load_sharded(engine, path, rank, world):
-    """Restores what save_sharded wrote at the SAME world size (a shard holds rows r with r % world == rank)."""
+    """Restores what save_sharded wrote at the SAME world size (a shard holds rows r with r % world == rank); merge_shards
+    turns the shards into a single-process checkpoint."""
     own = torch.load('%s.shard%d-of-%d.pt' % (path, rank, world), weights_only=True)
     if own['world'] != world or own['rank'] != rank:
         raise ValueError('shard file written for rank %d of %d' % (own['rank'], own['world']))
@@ -443,3 +483,38 @@ def load_sharded(engine, path, rank, world):
         accs.setdefault(k, np.zeros_like(v))
     engine.load_params(params, accs, second)
     return int(own.get('opt_step', 0))
+
+
+def merge_shards(path, world, out_file):
+    """Train on N, load on one: reads the ``world`` files save_sharded wrote under ``path`` and writes ONE checkpoint
+    ``out_file + '.pt'`` in the format of cffm_amd.CFFM.save, which CFFM.load restores at world size 1.  Tables and their
+    optimizer slots are interleaved back to global row order (row r <- shard r % world, local row r // world); the dense
+    parameters and their slots come from shard 0.  Host work on plain tensors; the result loads with weights_only=True."""
+    shards = [torch.load('%s.shard%d-of-%d.pt' % (path, r, world), weights_only=True) for r in range(world)]
+    for r, sh in enumerate(shards):
+        if sh['world'] != world or sh['rank'] != r:
+            raise ValueError('shard file %d written for rank %d of %d' % (r, sh['rank'], sh['world']))
+    M = sum(int(sh['local_rows']) for sh in shards)
+
+    def interleave(key):
+        if shards[0].get(key) is None:
+            return None
+        out = {}
+        for name, first in shards[0][key].items():
+            full = torch.empty((M,) + tuple(first.shape[1:]), dtype=first.dtype)
+            for r, sh in enumerate(shards):
+                full[r::world] = sh[key][name]
+            out[name] = full
+        return out
+
+    root = shards[0]
+    params, accs, second = interleave('tables'), interleave('table_slots'), interleave('table_slots2')
+    params.update(root['dense'])
+    accs.update(root['dense_slots'])
+    if second is not None:
+        second.update(root['dense_slots2'])
+    config = {'M': M, 'F': int(root['dense']['bias_W'].shape[0]), 'K': int(params['inner_embeddings'].shape[1]),
+              'D': int(params['outer_embeddings'].shape[1])}
+    torch.save({'format': 2, 'config': config, 'params': params, 'accumulators': accs, 'second_moments': second,
+                'opt_step': int(root.get('opt_step', 0))}, out_file + '.pt')
+    return out_file + '.pt'

@@ -73,7 +73,7 @@ class WorkspacePool(object):
 
 
 class HipEngine(object):
-    def __init__(self, cfg, params=None, seed=2021, device='cuda:0', table_seed=None):
+    def __init__(self, cfg, params=None, seed=2021, device='cuda:0', table_seed=None, table_rows=(0, 1)):
         if not torch.cuda.is_available():
             raise RuntimeError('cffm_amd.HipEngine needs an MI355X (torch.cuda.is_available() is False); '
                                'there is no CPU fallback')
@@ -93,7 +93,14 @@ class HipEngine(object):
         # would dominate start-up (10 M features: 5 GB).  Dense parameters still come from init_params(seed); the device
         # draw of the tables uses table_seed (default: seed).  Row-sharded ranks pass ONE seed for the replicated dense
         # parameters and table_seed = seed + rank for their own shard of the tables.
-        device_tables = isinstance(params, str) and params == 'device'
+        # params == 'device_rows': the tables are drawn on the GPU BY GLOBAL ROW (cffm_init_table_rows; spec.table_rows is its
+        # numpy twin): local row l holds global row row0 + l * row_step with table_rows = (row0, row_step), and a value depends
+        # on (table_seed, global row, table, column) alone.  Rank r of G passes (r, G) and ONE table_seed on every rank, a single
+        # process (0, 1): the model no longer depends on the world size.  'device' above is left as it is.
+        by_row = isinstance(params, str) and params == 'device_rows'
+        device_tables = (isinstance(params, str) and params == 'device') or by_row
+        if isinstance(params, str) and not device_tables:
+            raise ValueError("params must be a dict, None, 'device' or 'device_rows', not %r" % (params,))
         if params is None or device_tables:
             params = init_params(cfg, seed=seed, tables=not device_tables)
         n = int(self.tl.n)
@@ -128,10 +135,18 @@ class HipEngine(object):
         self._ta = C.addressof(self.tables_acc)
         self._ta2 = C.addressof(self.tables_acc2) if self.tables_acc2 is not None else 0
         self.load_params(params)
-        if device_tables:
+        if by_row:
+            self.init_table_rows(int(seed if table_seed is None else table_seed), int(table_rows[0]), int(table_rows[1]))
+        elif device_tables:
             gen = torch.Generator(device=dev).manual_seed(int(seed if table_seed is None else table_seed))
             self.inner.normal_(0.0, 0.1, generator=gen)
             self.outer.normal_(0.0, 0.01, generator=gen)
+
+    def init_table_rows(self, table_seed, row0=0, row_step=1):
+        """(Re)draw the three tables by global row: local row l <- global row row0 + l * row_step (cffm_init_table_rows).  The
+        optimizer slots are not touched."""
+        hip.check(self.lib.cffm_init_table_rows(self._s, self._t, int(table_seed) & 0xffffffffffffffff, int(row0), int(row_step),
+                                                int(self.cfg.M), self._stream()))
 
     def replicated_state(self, tables=True):
         """Tensors that must be bit-identical on every rank of a multi-GPU job (cffm_amd.dist.sync_replicas): the dense
@@ -338,6 +353,24 @@ class HipEngine(object):
             hip.check(self.lib.cffm_eval_sums(_ptr(out), _ptr(y[s0:s0 + m]), m, float(lo), float(hi),
                                               _ptr(self._eval_scratch), _ptr(sums), self._stream()))
         return sums
+
+    def eval_sums_add(self, pred, y, lo, hi, sums):
+        """One block of that sweep for predictions that are already there (the row-sharded forward, ShardedStep.eval_sums):
+        clip pred [m] to [lo, hi] and ADD the three float64 sums over (pred, y) onto sums [3]."""
+        m = int(pred.shape[0])
+        if self._eval_scratch is None:
+            self._eval_scratch = torch.empty(int(self.lib.cffm_eval_scratch_bytes()), dtype=torch.uint8, device=self.device)
+        y = y.reshape(-1)
+        if y.dtype != torch.float32 or not y.is_contiguous():
+            y = y.to(torch.float32).contiguous()
+        hip.check(self.lib.cffm_eval_sums(_ptr(pred), _ptr(y), m, float(lo), float(hi), _ptr(self._eval_scratch), _ptr(sums),
+                                          self._stream()))
+        return sums
+
+    def predictions(self, B):
+        """The [B] outputs the last forward (forward / forward_staged / forward_packed) left in the workspace, as a tensor of
+        their own."""
+        return self.ws_tensor(B, 'out', (B,)).clone()
 
     def train_step(self, ids, y):
         """sess.run((self.loss, self.optimizer)) (CFFM.py:200).  Returns the loss as a device scalar

@@ -103,6 +103,7 @@ PROTOTYPES = {
     'cffm_pack_rows_dedup': (C.c_int, [_SH, _P, _P, _P, C.c_int32, _P, _P, _P]),
     'cffm_shard_plan_scratch_bytes': (C.c_int64, [C.c_int64]),
     'cffm_shard_plan': (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'cffm_init_table_rows': (C.c_int, [_SH, _TB, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, _P]),
     'cffm_eval_scratch_bytes': (C.c_int64, []),
     'cffm_eval_sums': (C.c_int, [_P, _P, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     'cffm_probe_copy': (C.c_int, [_P, _P, C.c_int64, _P]),

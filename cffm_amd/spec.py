@@ -141,3 +141,67 @@ def init_params(cfg, seed=2021, dtype=np.float32, tables=True):
             v = _trunc_normal(rng, shp)
         p[name] = np.ascontiguousarray(v, dtype=dtype)
     return p
+
+
+# ---- tables drawn by GLOBAL row: the numpy twin (and the specification) of cffm_init_table_rows, include/cffm_hip.h -------------
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+TABLE_STD = {'inner_embeddings': 0.1, 'outer_embeddings': 0.01}      # CFFM.py:257, :264
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on arrays: counter = four, key = two arrays (or scalars) of 32-bit words, broadcast against each other.
+    Returns the four output words as uint32 arrays.  The words are carried in uint64 so that the 32 x 32 -> 64 bit products
+    are exact."""
+    mask = np.uint64(0xffffffff)
+    c0, c1, c2, c3 = (np.asarray(c).astype(np.uint64) & mask for c in counter)
+    k0, k1 = (np.asarray(k).astype(np.uint64) & mask for k in key)
+    m0, m1 = np.uint64(PHILOX_M[0]), np.uint64(PHILOX_M[1])
+    w0, w1 = np.uint64(PHILOX_W[0]), np.uint64(PHILOX_W[1])
+    sh = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = c0 * m0, c2 * m1
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & mask, (p0 >> sh) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + w0) & mask, (k1 + w1) & mask
+    return tuple(np.asarray(c).astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
+def table_words(seed, rows, table, width):
+    """The integer half of the draw: Philox words of global ``rows`` for the ceil(width / 4) column groups of ``table``
+    (0 inner, 1 outer), four uint32 arrays [n, groups].  Exact, so one call serves every floating-point evaluation."""
+    seed = int(seed) & 0xffffffffffffffff
+    g = np.asarray(rows).astype(np.uint64).reshape(-1, 1)
+    q = np.arange((int(width) + 3) // 4, dtype=np.uint64).reshape(1, -1)
+    return philox4x32_10((g & np.uint64(0xffffffff), g >> np.uint64(32), q, np.uint64(table)), (seed & 0xffffffff, seed >> 32))
+
+
+def unit_normals(words, width, dtype=np.float64):
+    """Box-Muller of table_words() in ``dtype``: [n, width] unit normals (the 24-bit uniforms are exact in float32, so only
+    log, sqrt and sin / cos are evaluated in ``dtype``)."""
+    dt = np.dtype(dtype).type
+    x0, x1, x2, x3 = words
+    out = np.empty(x0.shape + (4,), dtype=dtype)
+    for a, b, c in ((x0, x1, 0), (x2, x3, 2)):
+        u1 = ((a >> np.uint32(8)).astype(dtype) + dt(1)) * dt(2.0 ** -24)
+        u2 = (b >> np.uint32(8)).astype(dtype) * dt(2.0 ** -24)
+        r = np.sqrt(dt(-2) * np.log(u1))
+        ang = dt(2 * math.pi) * u2
+        out[..., c] = r * np.cos(ang)
+        out[..., c + 1] = r * np.sin(ang)
+    return out.reshape(x0.shape[0], -1)[:, :int(width)]
+
+
+def table_rows(cfg, seed, rows, dtype=np.float64):
+    """The three tables at an arbitrary array of GLOBAL rows, as cffm_init_table_rows draws them: a value depends on
+    (seed, global row, table, column) alone, so table_rows(rows)[i] is row rows[i] of the one model that ``seed`` names, for
+    every sharding.  N(0, 0.1) / N(0, 0.01) / exact zeros (CFFM.py:257-277); the table of a disabled branch stays zero."""
+    rows = np.asarray(rows).reshape(-1)
+    dt = np.dtype(dtype).type
+    out = {}
+    for t, (name, width, on) in enumerate((('inner_embeddings', cfg.K, cfg.inner_conv), ('outer_embeddings', cfg.D, cfg.outer_conv))):
+        if on:
+            out[name] = np.ascontiguousarray(unit_normals(table_words(seed, rows, t, width), width, dtype) * dt(TABLE_STD[name]))
+        else:
+            out[name] = np.zeros((rows.shape[0], width), dtype=dtype)
+    out['feature_bias'] = np.zeros((rows.shape[0], 1), dtype=dtype)
+    return out

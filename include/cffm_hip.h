@@ -290,6 +290,24 @@ int64_t cffm_shard_plan_scratch_bytes(int64_t n);
 int cffm_shard_plan(const int32_t *ids, int64_t n, int32_t world, int64_t M, void *scratch, int32_t *local_ids, int32_t *order,
                     int32_t *uniq, int32_t *pos, int32_t *send_rows, int64_t *counts, void *stream);
 
+/* ---- tables drawn by GLOBAL row (HipEngine(params='device_rows'); cffm_amd/spec.py table_rows is the numpy twin) ---
+ * Additive entry point: CFFM_ABI_VERSION stays 9, no existing signature or struct changes.
+ * Local row l (0 <= l < n_rows <= s->M) of the tables holds GLOBAL row g = row0 + l * row_step, and a value depends on
+ * (seed, g, table, column) alone: rank r of G draws its shard with (row0, row_step) = (r, G), one process with (0, 1), and
+ * the shards of any world size are rows of the same model.  The generator:
+ *   block cipher  Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85
+ *   key           (seed & 0xffffffff, seed >> 32)
+ *   counter       (g & 0xffffffff, g >> 32, q, t): q = index of a group of four columns, t = 0 inner_embeddings, 1 outer_embeddings
+ *   uniforms      output words x0..x3 -> columns 4q..4q+3:  u1 = ((x0 >> 8) + 1) * 2^-24, u2 = (x1 >> 8) * 2^-24,
+ *                 r = sqrt(-2 ln u1), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2); z2, z3 likewise from x2, x3
+ *   stored value  0.1 * z (inner, CFFM.py:257), 0.01 * z (outer, CFFM.py:264), feat_bias exact 0 (CFFM.py:276)
+ * Columns >= K or >= D are dropped (K and D only have to be even here); the table of a disabled branch is not written; a NULL
+ * feat_bias is skipped.  CFFM_ERR_BAD_SHAPE for row0 < 0, row_step < 1, n_rows < 0, n_rows > s->M, a last global row beyond
+ * int64, a NULL (or not 8-byte aligned) table of an enabled branch - before anything is launched; n_rows == 0 returns 0
+ * without a launch.  Optimizer slots are the caller's business. */
+int cffm_init_table_rows(const cffm_shape_t *s, const cffm_tables_t *tab, uint64_t seed, int64_t row0, int64_t row_step,
+                         int64_t n_rows, void *stream);
+
 /* ---- evaluate() (CFFM.py:583-615) without a device-to-host copy of the predictions ------------------------------- */
 /* clip + metric sums of CFFM.py:607-614 over n rows: p = min(max(pred, lo), hi) with lo/hi = min/max of the split's labels;
  * sums[0] += sum (y - p)^2, sums[1] += sum y, sums[2] += sum y^2, all float64, in a fixed order (bitwise reproducible).
