@@ -1774,8 +1774,11 @@ struct FwdAllArgs {
 // is the number of keys below it.  The workgroup of example b places its own F keys - n*F/256 compares per thread,
 // every workgroup in parallel, no extra launch and no serial tail.
 #define RANK_MAXF 12
+// An id outside [0, M) is keyed as M, like every other producer of these keys (gather.hip, inner_body.hpp, pack_keys_kernel): all
+// bad ids form one segment behind the valid ones, which every update kernel skips.
+__device__ __forceinline__ unsigned rank_key_id(int raw, int M) { return min((unsigned)raw, (unsigned)M); }   // raw < 0 wraps above M
 template <int NW>
-__device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, int n, int b, int F,
+__device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, int n, int b, int F, int M,
                                                unsigned long long* __restrict__ out, char* smem) {
     float* cnt = reinterpret_cast<float*>(smem);              // [NW waves][RANK_MAXF]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1783,7 +1786,7 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
 #pragma unroll
     for (int f = 0; f < RANK_MAXF; ++f) {
         const int slot = b * F + (f < F ? f : 0);
-        mine[f] = f < F ? (((unsigned long long)(unsigned)ids[slot] << 32) | (unsigned)slot) : 0ull;
+        mine[f] = f < F ? (((unsigned long long)rank_key_id(ids[slot], M) << 32) | (unsigned)slot) : 0ull;
     }
     int c[RANK_MAXF];
 #pragma unroll
@@ -1796,7 +1799,7 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
 #pragma unroll
         for (int u = 0; u < GRP; ++u) {
             const int j = j0 + 64 * NW * u;
-            idj[u] = (unsigned)ids[j < n ? j : n - 1];
+            idj[u] = rank_key_id(ids[j < n ? j : n - 1], M);
         }
 #pragma unroll
         for (int u = 0; u < GRP; ++u) {
@@ -1818,7 +1821,7 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
         for (int w = 1; w < NW; ++w) c += cnt[w * RANK_MAXF + tid];
         const int rank = (int)c;
         const int slot = b * F + tid;
-        out[rank] = ((unsigned long long)(unsigned)ids[slot] << 32) | (unsigned)slot;
+        out[rank] = ((unsigned long long)rank_key_id(ids[slot], M) << 32) | (unsigned)slot;
     }
     __syncthreads();
 }
@@ -1873,7 +1876,7 @@ __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
         const bool early = fa.early_off > 0;
         park.fetch(early ? reinterpret_cast<const float4*>(fa.conv[0].W) : nullptr, reinterpret_cast<float4*>(smem), 4 * PP * PP / 4);
         char* smem_i = smem + fa.early_off;
-        if (fa.rank_keys) rank_keys_body<NW>(fa.ids, fa.n_rows, b, fa.inner.g.F, fa.keys_sorted, smem_i);
+        if (fa.rank_keys) rank_keys_body<NW>(fa.ids, fa.n_rows, b, fa.inner.g.F, fa.inner.g.M, fa.keys_sorted, smem_i);
         PHASE_MARK(0);
         // gathers Ei/Eo/fb of example b (full barrier inside), inner_out[b]
         inner_fwd_body<ACT>(fa.inner, b, smem_i, early ? reinterpret_cast<float*>(smem + fa.es_off) : nullptr, fa.inner.g.D + 1, park);
@@ -2820,7 +2823,7 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
         __syncthreads();
         PHASE_MARKB(37, bid);
         if (a.rank_ids != nullptr && a.n_keys == 0) {
-            for (int b = bid; b < a.hb.B; b += a.n_inner) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.keys_sorted, smem);
+            for (int b = bid; b < a.hb.B; b += a.n_inner) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.hb.g.M, a.keys_sorted, smem);
         }
         PHASE_MARKB(38, bid);
         inner_bwd_body<ACT>(a.ib, bid, a.n_inner, smem, L);
@@ -2831,7 +2834,7 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
         return;
     }
     if (bid < a.n_inner + a.n_keys) {                        // ---- role 3 (n_keys > 0): the key placement as workgroups of its own
-        for (int b = bid - a.n_inner; b < a.hb.B; b += a.n_keys) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.keys_sorted, smem);
+        for (int b = bid - a.n_inner; b < a.hb.B; b += a.n_keys) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.hb.g.M, a.keys_sorted, smem);
 #ifdef CFFM_PHASE_TIMERS
         if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x + 1] = wall_clock64();
 #endif

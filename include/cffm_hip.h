@@ -212,8 +212,8 @@ int cffm_backward(const cffm_shape_t *s, const float *theta, const float *y, int
                   void *ws, float *grad, void *stream);
 /* cffm_forward + cffm_backward_unscaled in one call (what one rank runs before the two collectives of a
  * data-parallel step); uses the single-launch forward where the shape allows.  rows must hold B*F*(1+K+D+1 + 2) floats:
- * the packed rows [B*F][1+K+D+1] followed by this rank's B*F update keys (id << 32 | slot, 64-bit) in sorted order
- * (a "run"; valid when the single-launch forward ran, i.e. Pp <= 64 and B*F <= 4096) */
+ * the packed rows [B*F][1+K+D+1] followed by this rank's B*F update keys (id << 32 | slot, 64-bit; an id outside [0, M) is
+ * keyed as M, while column 0 of its row keeps the raw bits) in sorted order (a "run"; valid when the single-launch forward ran, i.e. Pp <= 64 and B*F <= 4096) */
 /* 1 if cffm_dp_local with this per-rank batch leaves a valid sorted run behind its rows (else pass n_runs = 0 rows) */
 int cffm_dp_runs_ok(const cffm_shape_t *s, int32_t B);
 int cffm_dp_local(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ids, const float *y,
