@@ -119,7 +119,7 @@ int cffm_ws_layout_from(const cffm_shape_t* s, int32_t B, const cffm_theta_layou
 }
 
 // One context per ABI call: every entry point below checks the shape, returns early for an empty batch and then builds the
-// StepCtx (layouts, slab plan) that forward_impl / backward_impl and the conv functions under them share.
+// StepCtx (layouts, slab plan) that forward_impl / backward_impl and every launcher under them share.
 //
 // no_materialise: the composites that own the whole step (cffm_train_step, cffm_predict, cffm_dp_local) let the wide shapes
 // consume the looked-up rows in the kernel that fetches them (cffm_gather_inner_fwd_wide) and re-fetch them from the tables
@@ -145,34 +145,34 @@ struct FwdOpts {
 static int forward_impl(const StepCtx& c, const RowTables& rows, const float* y, hipStream_t stream, const FwdOpts& o = FwdOpts()) {
     const cffm_shape_t* s = c.s;
     const cffm_tables_t* tab = rows.tab;
-    const float* theta = c.theta;
-    const int32_t B = c.B;
-    void* ws = c.w;
     const cffm_ws_layout_t& wl = c.wl;
+    HeadFwdOpts ho;
+    ho.sum_loss = !o.fused_step;
     int rc = 0;
     if (o.no_materialise && wide_rows(s, rows)) {
-        if ((rc = cffm_gather_inner_fwd_wide(s, tab, theta, rows.ids, B, ws, stream, rows.stride, rows.records))) return rc;
+        if ((rc = cffm_gather_inner_fwd_wide(c, rows, stream))) return rc;
         const RowSrc ro = table_rows(s, tab->outer_emb, rows);
         if ((rc = cffm_conv_fwd_impl(c, 0, stream, &ro))) return rc;
         for (int l = 1; l < c.g.live; ++l)
             if ((rc = cffm_conv_fwd_impl(c, l, stream))) return rc;
-        return cffm_head_fwd_impl2(s, theta, ws, y, B, !o.fused_step, true, stream);
+        ho.s0_ready = true;
+        return cffm_head_fwd_impl(c, y, ho, stream);
     }
     if (!tab) {
         if (o.fused_step) return CFFM_ERR_UNSUPPORTED;
-        if ((rc = cffm_inner_fwd(s, theta, ws, B, stream))) return rc;
+        if ((rc = cffm_inner_fwd_impl(c, nullptr, nullptr, stream))) return rc;
     } else if (o.fused_step && s->inner_conv && s->outer_conv) {
         // the inner-branch kernel gathers the rows of its example itself (one launch less)
-        if ((rc = cffm_inner_fwd_impl(s, theta, ws, B, tab, rows.ids, stream))) return rc;
+        if ((rc = cffm_inner_fwd_impl(c, tab, rows.ids, stream))) return rc;
     } else {
-        rc = cffm_gather_impl(s, tab, rows.ids, B, s->inner_conv ? c.at(wl.Ei) : nullptr, s->outer_conv ? c.at(wl.Eo) : nullptr,
+        rc = cffm_gather_impl(s, tab, rows.ids, c.B, s->inner_conv ? c.at(wl.Ei) : nullptr, s->outer_conv ? c.at(wl.Eo) : nullptr,
                               c.at(wl.fb), o.fused_step ? c.at<unsigned long long>(wl.sort_keys) : nullptr, stream);
         if (rc) return rc;
-        if ((rc = cffm_inner_fwd(s, theta, ws, B, stream))) return rc;
+        if ((rc = cffm_inner_fwd_impl(c, nullptr, nullptr, stream))) return rc;
     }
     for (int l = 0; l < c.g.live && s->outer_conv; ++l)
         if ((rc = cffm_conv_fwd_impl(c, l, stream))) return rc;
-    return cffm_head_fwd_impl(s, theta, ws, y, B, !o.fused_step, stream);
+    return cffm_head_fwd_impl(c, y, ho, stream);
 }
 
 extern "C" int cffm_forward(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids,
@@ -200,9 +200,7 @@ extern "C" int cffm_predict(const cffm_shape_t* s, const cffm_tables_t* tab, con
 static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, float* grad, hipStream_t stream,
                          const BwdOpts& o = BwdOpts()) {
     const cffm_shape_t* s = c.s;
-    const float* theta = c.theta;
     const int32_t B = c.B;
-    void* ws = c.w;
     int rc = 0;
     if (!s->inner_conv || !s->outer_conv || !s->linear_att) {   // slabs of a disabled branch must read as zeros
         hipError_t e = hipMemsetAsync(c.at(c.wl.gpart), 0, (size_t)c.wl.gpart_floats * 4, stream);
@@ -225,8 +223,7 @@ static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, flo
             if ((rc = cffm_conv_bwd_impl(c, l, stream, co))) return rc;
         }
     } else {
-        if ((rc = cffm_head_bwd_impl(s, theta, ws, y, B, B_global, o.local_sum(), o.loss_out, stream, o.unscaled)))
-            return rc;
+        if ((rc = cffm_head_bwd_impl(c, y, B_global, o, stream))) return rc;
         const RowSrc ro = table_rows(s, wide ? o.rows.tab->outer_emb : nullptr, o.rows);
         for (int l = c.g.live - 1; l >= 0 && s->outer_conv; --l) {
             ConvBwdOpts co;
@@ -236,16 +233,11 @@ static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, flo
         }
     }
     if (!inner_done) {
-        if (wide) {
-            const RowSrc ri = table_rows(s, o.rows.tab->inner_emb, o.rows);
-            rc = cffm_inner_bwd_rows(s, theta, ws, B, &ri, stream);
-        } else {
-            rc = cffm_inner_bwd(s, theta, ws, B, stream);
-        }
-        if (rc) return rc;
+        const RowSrc ri = table_rows(s, wide ? o.rows.tab->inner_emb : nullptr, o.rows);
+        if ((rc = cffm_inner_bwd_rows(c, wide ? &ri : nullptr, stream))) return rc;
     }
     if (o.skip_reduce) return 0;
-    return cffm_reduce_slabs_impl(s, ws, B, grad, o.adagrad_theta, o.adagrad_acc, s->lr, stream);
+    return cffm_reduce_slabs_impl(c, grad, o.adagrad_theta, o.adagrad_acc, s->lr, stream);
 }
 
 extern "C" int cffm_backward(const cffm_shape_t* s, const float* theta, const float* y, int32_t B, int64_t B_global,
@@ -276,10 +268,7 @@ extern "C" int cffm_backward_unscaled(const cffm_shape_t* s, const float* theta,
     bo.unscaled = true;
     if ((rc = backward_impl(c, y, B_global, grad, (hipStream_t)stream, bo))) return rc;
     if (!rows) return move_loss_sum(c, grad, (hipStream_t)stream);   // the caller packs the row gradients itself (cffm_pack_rows_dedup)
-    const cffm_ws_layout_t& wl = c.wl;
-    return cffm_pack_rows(s, ids, B, s->inner_conv ? c.at<const float>(wl.dEi) : nullptr,
-                          s->outer_conv ? c.at<const float>(wl.dEo) : nullptr, c.at<const float>(wl.dfb),
-                          c.at<const float>(wl.scalars), grad + c.tl.n, rows, (hipStream_t)stream);
+    return cffm_pack_rows(c, ids, grad + c.tl.n, rows, (hipStream_t)stream);
 }
 
 // ---- row-sharded step without staging (cffm_amd/dist.py ShardedStep): the packed records a rank received ARE the tables ------
@@ -345,7 +334,7 @@ extern "C" int cffm_dp_local(const cffm_shape_t* s, const cffm_tables_t* tab, co
     if (later) bo.rank_ids = ids;
     if (!run) bo.rows = step_rows(tab, ids);
     if ((rc = backward_impl(c, y, B_global, grad, st, bo))) return rc;
-    return cffm_dp_tail(s, ids, B, ws, grad, rows, run, st);
+    return cffm_dp_tail(c, ids, grad, rows, run, st);
 }
 
 // Same local half for the dense-table exchange (small vocabularies): flat = [theta gradients | loss sum | table gradient
@@ -368,7 +357,7 @@ extern "C" int cffm_dp_local_dense(const cffm_shape_t* s, const cffm_tables_t* t
     bo.skip_reduce = true;                           // cffm_dp_tail_dense reduces
     if (later) bo.rank_ids = ids;
     if ((rc = backward_impl(c, y, B_global, flat, st, bo))) return rc;
-    return cffm_dp_tail_dense(s, B, ws, flat, st);
+    return cffm_dp_tail_dense(c, flat, st);
 }
 
 extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc,
@@ -389,7 +378,7 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
         if (!s->inner_conv || !s->outer_conv) return CFFM_ERR_UNSUPPORTED;
         if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
         if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-        return cffm_tables_adagrad_l2(s, tab, tab_acc, ids, (int64_t)B * s->F, ws, B, st);
+        return cffm_tables_adagrad_l2(c, tab, tab_acc, ids, (int64_t)B * s->F, st);
     }
     if (cffm_fwd_all_ok(s, B)) {                 // small-channel shapes: the whole forward (and the key sort) in one launch
         const bool later = defer_rank(s, B);
@@ -397,16 +386,16 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
         bo.skip_reduce = true;                   // cffm_update_all reduces
         if (later) bo.rank_ids = ids;
         if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-        return cffm_update_all(s, tab, tab_acc, theta, theta_acc, grad, ws, B, st);
+        return cffm_update_all(c, tab, tab_acc, theta, theta_acc, grad, st);
     }
     fo.no_materialise = true;
     if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
     bo.rows = step_rows(tab, ids);
     if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-    const cffm_ws_layout_t& wl = c.wl;
-    return cffm_sparse_adagrad_impl(s, tab, tab_acc, ids, (int64_t)B * s->F, s->inner_conv ? c.at<const float>(wl.dEi) : nullptr,
-                                    s->outer_conv ? c.at<const float>(wl.dEo) : nullptr, c.at<const float>(wl.dfb), ws, B,
-                                    /*prepacked=*/true, st);
+    SortOpts so;
+    so.prepacked = true;                         // the gather left the packed keys in ws.sort_keys
+    if ((rc = cffm_sort_keys_impl(c, ids, (int64_t)B * s->F, so, st))) return rc;
+    return cffm_sparse_apply(c, tab, tab_acc, (int64_t)B * s->F, RowGrads::of_ws(c), LateScale{nullptr, 0.f, 0}, st);
 }
 
 extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_state1,
@@ -429,6 +418,5 @@ extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* t
     bo.loss_out = loss;
     if (fo.no_materialise) bo.rows = step_rows(tab, ids);
     if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-    return cffm_apply_opt(s, tab, tab_state1, tab_state2, theta, theta_state1, theta_state2, grad, ids, (int64_t)B * s->F, ws,
-                          B, step, st);
+    return cffm_apply_opt(c, tab, tab_state1, tab_state2, theta, theta_state1, theta_state2, grad, ids, (int64_t)B * s->F, step, st);
 }

@@ -44,6 +44,26 @@ __device__ __forceinline__ int fused_c_off(int l, int c0, int c1, int D, int Pp)
 
 static inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int ilog2_i(int v) { int r = 0; while ((1 << (r + 1)) <= v) ++r; return r; }
+// id bits of a sparse-update key (id << 32 | slot): ids 0 .. M, M being the key of every out-of-range id
+static inline int id_key_bits(int M) {
+    int bits = 1;
+    while ((1ll << bits) <= (long long)M && bits < 31) ++bits;
+    return bits;
+}
+
+// Dynamic-LDS ceilings of a workgroup (160 KB per CU): what a kernel that leaves room for a second, small workgroup may ask for,
+// and everything but the 512 bytes kept back for static __shared__ variables
+static constexpr int CFFM_LDS_SHARED_CU = 150 * 1024;
+static constexpr int CFFM_LDS_WHOLE_CU = 160 * 1024 - 512;
+// more than the default 64 KB of dynamic LDS has to be asked for, per kernel
+template <class KernelT>
+static inline int set_lds(KernelT k, size_t lds) {
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
 
 // Geometry derived from the shape; passed to kernels by value.
 struct Geo {

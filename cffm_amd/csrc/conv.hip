@@ -2878,15 +2878,6 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
         default: rc = CFFM_ERR_UNSUPPORTED; break;      \
     }
 
-template <class KernelT>
-static inline int set_lds(KernelT k, size_t lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 template <int N> using IntC = std::integral_constant<int, N>;
 
 // ---- dynamic LDS: one function per size, shared by the launcher, the *_ok() predicate and cffm_fwd_all_impl ----------------------
@@ -4064,7 +4055,7 @@ static int launch_conv0_fact_fwd(const ConvArgs& a, hipStream_t st) {
 static inline bool conv0_fact_ok(const Geo& g) {
     const int S = g.D / 2;
     if (g.Pp > 64 || (S != 16 && S != 32)) return false;
-    return conv0_fact_fwd_lds(g.Pp, g.F, g.D) <= 150 * 1024;
+    return conv0_fact_fwd_lds(g.Pp, g.F, g.D) <= CFFM_LDS_SHARED_CU;
 }
 
 // LDS of conv0_fact_bwd_body with its 16 wavefronts: filter, T planes, partial tiles, dEi / dEj, bias partials, row sums,
@@ -4075,7 +4066,7 @@ static inline size_t conv0_fact_bwd_lds(int Pp, int F, int D) {
 }
 static inline bool conv0_fact_bwd_ok(const Geo& g) {
     if (g.Pp > 64 || g.D != 32) return false;
-    return conv0_fact_bwd_lds(g.Pp, g.F, g.D) <= 160 * 1024 - 512;
+    return conv0_fact_bwd_lds(g.Pp, g.F, g.D) <= CFFM_LDS_WHOLE_CU;
 }
 
 template <int NT>
@@ -4302,7 +4293,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
     const int32_t B = c.B;
     BwdTopArgs a;
     memset(&a, 0, sizeof(a));
-    fill_head_bwd_args(s, c.theta, c.w, y, B, B_global, o.local_sum(), o.loss_out, o.unscaled, &a.hb);
+    a.hb = c.head_bwd_args(y, B_global, o);
     const int first = bwd_top_first_layer(s);
     a.wgrad_here = (top_wgrad_deferred(s, B) || bwd_fused01_ok(s, B)) ? 0 : 1;   // 0: a later launch computes them
     a.n_layers = 0;
@@ -4312,7 +4303,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
         a.lgSo[a.n_layers] = a.d[a.n_layers].lgSo;
         ++a.n_layers;
     }
-    a.n_inner = fill_inner_bwd_args(s, c.theta, c.w, B, &a.ib);
+    a.ib = c.inner_bwd_args(&a.n_inner);
     a.ib.dout = nullptr;                                     // recomputed from (out, y, L): no dependency on the head role
     a.ib.y = y; a.ib.invB = 1.f / (float)B_global;
     if (o.rank_ids != nullptr && s->F <= RANK_MAXF && (int64_t)B * s->F <= 4096) {
@@ -4332,7 +4323,6 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
 int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o) {
     const cffm_shape_t* s = c.s;
     const Geo& g = c.g;
-    const int32_t B = c.B;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
     const SlabRange& sr = c.conv_slab(l);
     const RowSrc* rs = o.rs;
@@ -4349,10 +4339,10 @@ int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpt
         if ((wa.Mtot + sr.nslab - 1) / sr.nslab < 128) {          // the 256-thread weight-gradient variant: pair it up
             const DgradArgs da = c.dgrad_args(l);
             const int64_t wg16 = (wa.Mtot + 15) / 16;
-            InnerBwdArgs ib;
+            InnerBwdArgs ib{};
             int n_i = 0;
             const bool inner = o.carry_inner != nullptr && s->inner_conv;
-            if (inner) n_i = fill_inner_bwd_args(s, c.theta, c.w, B, &ib);
+            if (inner) ib = c.inner_bwd_args(&n_i);
             TopWgrad tw;
             memset(&tw, 0, sizeof(tw));
             if (o.with_top_wgrad) {                             // the fused top left its weight gradients to this launch
@@ -4528,39 +4518,16 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
     const cffm_shape_t* s = c.s;
     const Geo& g = c.g;
     const int32_t B = c.B;
-    const float* theta = c.theta;
-    const cffm_theta_layout_t& tl = c.tl;
     const cffm_ws_layout_t& wl = c.wl;
-    FwdAllArgs fa;
-    // inner branch + gather
-    fa.inner.g = g; fa.inner.Ei = c.at<const float>(wl.Ei);
-    fa.inner.cw = theta + tl.inner_cw; fa.inner.cb = theta + tl.inner_cb; fa.inner.wd = theta + tl.inner_dw;
-    fa.inner.bd = theta + tl.inner_db; fa.inner.inner_out = c.at(wl.inner_out);
-    fa.inner.fg.ids = ids; fa.inner.fg.inner = tab->inner_emb; fa.inner.fg.outer = tab->outer_emb;
-    fa.inner.fg.fbias = tab->feat_bias; fa.inner.fg.Ei = c.at(wl.Ei); fa.inner.fg.Eo = c.at(wl.Eo);
-    fa.inner.fg.fb = c.at(wl.fb); fa.inner.fg.keys = c.at<unsigned long long>(wl.sort_keys);
-    fa.inner.fg.M = s->M; fa.inner.fg.D = s->D;
-    // conv stack
+    FwdAllArgs fa{};
+    fa.inner = c.inner_fwd_args(tab, ids);
     for (int l = 0; l < g.live; ++l) fa.conv[l] = c.conv_args(l);
-    // head
-    HeadArgs& h = fa.head;
-    h.g = g; h.B = B;
-    h.Eo = c.at<const float>(wl.Eo); h.fb = c.at<const float>(wl.fb); h.inner_out = c.at<const float>(wl.inner_out);
-    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) h.C[l] = c.at<const float>(wl.C[l]);
-    h.d1_w = theta + tl.d1_w; h.d1_b = theta + tl.d1_b; h.d2_w = theta + tl.d2_w; h.d2_b = theta + tl.d2_b;
-    h.att_W = theta + tl.att_W; h.att_b = theta + tl.att_b; h.lin_w = theta + tl.lin_w; h.lin_b = theta + tl.lin_b;
-    h.bias = theta + tl.bias;
-    h.y = y;
-    h.t1 = c.at(wl.t1); h.h1 = c.at(wl.h1); h.att = c.at(wl.att);
-    h.out = c.at(wl.out); h.sqerr = c.at(wl.sqerr);
-    h.loss = s->loss; h.inner_conv = s->inner_conv; h.outer_conv = s->outer_conv;
+    fa.head = c.head_args(y);
     // sort workgroup
     fa.ids = ids; fa.keys_sorted = c.at<unsigned long long>(wl.sort_vals);
     fa.live = g.live; fa.n_rows = B * s->F; fa.B = B;
     fa.rank_keys = rank_keys ? 1 : 0;
-    int bits = 1;
-    while ((1ll << bits) <= (long long)s->M && bits < 31) ++bits;
-    fa.id_bits = bits;
+    fa.id_bits = id_key_bits(s->M);
     const int S = g.D / 2, PP = g.Pp;
     // every phase's scratch starts at 0: the launch gets the largest
     const size_t l_taps = conv_fwd_taps_scratch(PP, 4) + 64;
@@ -4578,7 +4545,7 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
         size_t base0 = lds > low + small ? lds : low + small;
         base0 = (base0 + 255) / 256 * 256;
         fa.c0_off = -1; fa.c1_off = 0;
-        if (base0 + c0 <= 160 * 1024 - 512) {
+        if (base0 + c0 <= CFFM_LDS_WHOLE_CU) {
             fa.c0_off = (int)base0;
             fa.c1_off = (int)low;
             lds = base0 + c0;

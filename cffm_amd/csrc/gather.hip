@@ -107,14 +107,15 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const int32_t* __restric
     }
 }
 
-int cffm_pack_rows(const cffm_shape_t* s, const int32_t* ids, int32_t B, const float* dEi, const float* dEo, const float* dfb,
-                   const float* scalars, float* sum_dst, float* rows, hipStream_t st) {
-    const int64_t n_slots = (int64_t)B * s->F;
+int cffm_pack_rows(const StepCtx& c, const int32_t* ids, float* sum_dst, float* rows, hipStream_t st) {
+    const cffm_shape_t* s = c.s;
+    const RowGrads r = RowGrads::of_ws(c);
+    const int64_t n_slots = (int64_t)c.B * s->F;
     const int64_t total = n_slots * (1 + s->K + s->D + 1);
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pack_rows_kernel, dim3(blocks), dim3(256), 0, st, ids, n_slots, s->K, s->D, dEi, dEo, dfb, scalars,
-                       sum_dst, rows);
+    hipLaunchKernelGGL(pack_rows_kernel, dim3(blocks), dim3(256), 0, st, ids, n_slots, s->K, s->D, r.dEi, r.dEo, r.dfb,
+                       c.at<const float>(c.wl.scalars), sum_dst, rows);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -210,17 +211,14 @@ extern "C" int cffm_stage_packed(const cffm_shape_t* s, const float* packed, con
     if (rc) return rc;
     if (B <= 0) return 0;
     if (!packed || !ws || n_records <= 0 || (s->D & 3) || (s->K & 3)) return CFFM_ERR_BAD_SHAPE;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
+    const StepCtx c(s, B, nullptr, ws);
     const int K4 = s->K / 4, D4 = s->D / 4;
     const int64_t n_slots = (int64_t)B * s->F, total = n_slots * (K4 + D4 + 1);
     if (total >= (1ll << 31)) return CFFM_ERR_BAD_SHAPE;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(stage_packed_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, packed, pos, n_slots, n_records, K4,
-                       D4, s->inner_conv ? (float*)(w + wl.Ei) : nullptr, s->outer_conv ? (float*)(w + wl.Eo) : nullptr,
-                       (float*)(w + wl.fb));
+                       D4, s->inner_conv ? c.at(c.wl.Ei) : nullptr, s->outer_conv ? c.at(c.wl.Eo) : nullptr, c.at(c.wl.fb));
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -259,13 +257,10 @@ extern "C" int cffm_pack_rows_dedup(const cffm_shape_t* s, const int32_t* local_
     if (rc) return rc;
     if (B <= 0) return 0;
     if (!local_ids || !order || !uniq || !ws || !out) return CFFM_ERR_BAD_SHAPE;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
+    const RowGrads r = RowGrads::of_ws(StepCtx(s, B, nullptr, ws));
     const int64_t n = (int64_t)B * s->F;
     hipLaunchKernelGGL(pack_rows_dedup_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, local_ids, order,
-                       uniq, n, s->K, s->D, s->inner_conv ? (const float*)(w + wl.dEi) : nullptr,
-                       s->outer_conv ? (const float*)(w + wl.dEo) : nullptr, (const float*)(w + wl.dfb), out);
+                       uniq, n, s->K, s->D, r.dEi, r.dEo, r.dfb, out);
     CFFM_CHECK_LAUNCH();
     return 0;
 }

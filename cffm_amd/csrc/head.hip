@@ -38,46 +38,63 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
     head_bwd_end(a, blockIdx.x, st);
 }
 
-extern "C" int cffm_head_fwd(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, void* stream) {
-    return cffm_head_fwd_impl(s, theta, ws, y, B, true, (hipStream_t)stream);
-}
-
-int cffm_head_fwd_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, bool do_sum,
-                       hipStream_t stream) {
-    return cffm_head_fwd_impl2(s, theta, ws, y, B, do_sum, false, stream);
-}
-
-int cffm_head_fwd_impl2(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, bool do_sum, bool s0_ready,
-                        hipStream_t stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
-    if (2 * s->D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    HeadArgs a;
-    a.g = make_geo(s); a.B = B;
-    a.Eo = (const float*)(w + wl.Eo); a.fb = (const float*)(w + wl.fb);
-    a.inner_out = (const float*)(w + wl.inner_out);
-    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) a.C[l] = (const float*)(w + wl.C[l]);
+HeadArgs StepCtx::head_args(const float* y, bool s0_ready) const {
+    HeadArgs a{};
+    a.g = g; a.B = B;
+    a.Eo = at<const float>(wl.Eo); a.fb = at<const float>(wl.fb); a.inner_out = at<const float>(wl.inner_out);
+    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) a.C[l] = at<const float>(wl.C[l]);
     a.d1_w = theta + tl.d1_w; a.d1_b = theta + tl.d1_b; a.d2_w = theta + tl.d2_w; a.d2_b = theta + tl.d2_b;
     a.att_W = theta + tl.att_W; a.att_b = theta + tl.att_b; a.lin_w = theta + tl.lin_w; a.lin_b = theta + tl.lin_b;
     a.bias = theta + tl.bias;
     a.y = y;
-    a.t1 = (float*)(w + wl.t1); a.h1 = (float*)(w + wl.h1); a.att = (float*)(w + wl.att);
-    a.out = (float*)(w + wl.out); a.sqerr = (float*)(w + wl.sqerr);
+    a.t1 = at(wl.t1); a.h1 = at(wl.h1); a.att = at(wl.att); a.out = at(wl.out); a.sqerr = at(wl.sqerr);
     a.loss = s->loss; a.inner_conv = s->inner_conv; a.outer_conv = s->outer_conv;
     a.s0_ready = (s0_ready && s->outer_conv && s->D <= 256) ? 1 : 0;
-    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) {
+    for (int l = 0; l < CFFM_MAX_LAYERS; ++l) {       // wide shapes only (pool_partials); the fused forward reads neither
         a.pool_np[l] = wl.pool_np[l];
-        a.pool[l] = wl.pool_np[l] > 0 ? (const float*)(w + wl.pool[l]) : nullptr;
+        a.pool[l] = wl.pool_np[l] > 0 ? at<const float>(wl.pool[l]) : nullptr;
     }
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(B), dim3(256), head_fwd_lds(a.g), (hipStream_t)stream, a);
+    return a;
+}
+
+HeadBwdArgs StepCtx::head_bwd_args(const float* y, int64_t B_global, const BwdOpts& o) const {
+    const SlabRange& rf = sp.r[sp.head_front];
+    const SlabRange& rb = sp.r[sp.head_back];
+    float* gf = at(wl.gpart) + rf.base - rf.off;        // slab 0 of theta offset x lives at gf + x
+    float* gb = at(wl.gpart) + rb.base - rb.off;
+    HeadBwdArgs a{};
+    a.g = g; a.B = B; a.Bg = B_global;
+    a.fb = at<const float>(wl.fb); a.t1 = at<const float>(wl.t1); a.h1 = at<const float>(wl.h1);
+    a.att = at<const float>(wl.att); a.out = at<const float>(wl.out); a.y = y;
+    const int top = g.live - 1;
+    a.Ctop = at<const float>(wl.C[top]); a.dCtop = at(wl.dC[top]);
+    a.d1_w = theta + tl.d1_w; a.d2_w = theta + tl.d2_w; a.att_W = theta + tl.att_W; a.lin_w = theta + tl.lin_w;
+    a.scalars = at(wl.scalars);
+    a.sqerr = o.local_sum() ? at<const float>(wl.sqerr) : nullptr;
+    a.loss_out = o.loss_out;
+    a.dout = at(wl.dout); a.dt1 = at(wl.dt1); a.dfb = at(wl.dfb);
+    a.s_attW = gf + tl.att_W; a.s_attb = gf + tl.att_b; a.s_bias = gf + tl.bias;
+    a.s_d1w = gb + tl.d1_w; a.s_d1b = gb + tl.d1_b; a.s_d2w = gb + tl.d2_w; a.s_d2b = gb + tl.d2_b;
+    a.s_linw = gb + tl.lin_w; a.s_linb = gb + tl.lin_b;
+    a.stride_front = rf.len; a.stride_back = rb.len; a.front_len = rf.len; a.back_len = rb.len;
+    a.loss = s->loss; a.outer_conv = s->outer_conv; a.unscaled = o.unscaled ? 1 : 0;
+    return a;
+}
+
+extern "C" int cffm_head_fwd(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, void* stream) {
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    return cffm_head_fwd_impl(StepCtx(s, B, theta, ws), y, HeadFwdOpts(), (hipStream_t)stream);
+}
+
+int cffm_head_fwd_impl(const StepCtx& c, const float* y, const HeadFwdOpts& o, hipStream_t stream) {
+    if (2 * c.g.D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
+    const HeadArgs a = c.head_args(y, o.s0_ready);
+    hipLaunchKernelGGL(head_fwd_kernel, dim3(c.B), dim3(256), head_fwd_lds(c.g), stream, a);
     CFFM_CHECK_LAUNCH();
-    if (y && do_sum) {
-        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const float*)(w + wl.sqerr),
-                           (int64_t)B, (float*)(w + wl.scalars), 1);
+    if (y && o.sum_loss) {
+        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, stream, c.at<const float>(c.wl.sqerr), (int64_t)c.B,
+                           c.at(c.wl.scalars), 1);
         CFFM_CHECK_LAUNCH();
     }
     return 0;
@@ -85,21 +102,15 @@ int cffm_head_fwd_impl2(const cffm_shape_t* s, const float* theta, void* ws, con
 
 extern "C" int cffm_head_bwd(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B,
                              int64_t B_global, void* stream) {
-    return cffm_head_bwd_impl(s, theta, ws, y, B, B_global, false, nullptr, (hipStream_t)stream);
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    return cffm_head_bwd_impl(StepCtx(s, B, theta, ws), y, B_global, BwdOpts(), (hipStream_t)stream);
 }
 
-int cffm_head_bwd_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, int64_t B_global,
-                       bool local_sum, float* loss_out, hipStream_t stream, bool unscaled) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0) return 0;
-    if (2 * s->D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    HeadBwdArgs a;
-    fill_head_bwd_args(s, theta, ws, y, B, B_global, local_sum, loss_out, unscaled, &a);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(small_slabs(B)), dim3(256), 0, (hipStream_t)stream, a);
+int cffm_head_bwd_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t stream) {
+    if (2 * c.g.D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
+    const HeadBwdArgs a = c.head_bwd_args(y, B_global, o);
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(small_slabs(c.B)), dim3(256), 0, stream, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }

@@ -398,32 +398,3 @@ __device__ __forceinline__ void head_bwd_end(const HeadBwdArgs& a, int slab, con
         a.s_linb[sob] = st.g_linb;
     }
 }
-
-static inline void fill_head_bwd_args(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B,
-                                      int64_t B_global, bool local_sum, float* loss_out, bool unscaled, HeadBwdArgs* out) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const SlabRange& rf = sp.r[sp.head_front];
-    const SlabRange& rb = sp.r[sp.head_back];
-    float* gf = (float*)(w + wl.gpart) + rf.base - rf.off;        // slab 0 of theta offset x lives at gf + x
-    float* gb = (float*)(w + wl.gpart) + rb.base - rb.off;
-    HeadBwdArgs& a = *out;
-    a.g = make_geo(s); a.B = B; a.Bg = B_global;
-    a.fb = (const float*)(w + wl.fb); a.t1 = (const float*)(w + wl.t1); a.h1 = (const float*)(w + wl.h1);
-    a.att = (const float*)(w + wl.att); a.out = (const float*)(w + wl.out); a.y = y;
-    const int top = a.g.live - 1;
-    a.Ctop = (const float*)(w + wl.C[top]); a.dCtop = (float*)(w + wl.dC[top]);
-    a.d1_w = theta + tl.d1_w; a.d2_w = theta + tl.d2_w; a.att_W = theta + tl.att_W; a.lin_w = theta + tl.lin_w;
-    a.scalars = (float*)(w + wl.scalars);
-    a.sqerr = local_sum ? (const float*)(w + wl.sqerr) : nullptr;
-    a.loss_out = loss_out;
-    a.dout = (float*)(w + wl.dout); a.dt1 = (float*)(w + wl.dt1); a.dfb = (float*)(w + wl.dfb);
-    a.s_attW = gf + tl.att_W; a.s_attb = gf + tl.att_b; a.s_bias = gf + tl.bias;
-    a.s_d1w = gb + tl.d1_w; a.s_d1b = gb + tl.d1_b; a.s_d2w = gb + tl.d2_w; a.s_d2b = gb + tl.d2_b;
-    a.s_linw = gb + tl.lin_w; a.s_linb = gb + tl.lin_b;
-    a.stride_front = rf.len; a.stride_back = rb.len; a.front_len = rf.len; a.back_len = rb.len;
-    a.loss = s->loss; a.outer_conv = s->outer_conv; a.unscaled = unscaled ? 1 : 0;
-}

@@ -21,60 +21,68 @@ __global__ __launch_bounds__(256) void inner_bwd_kernel(InnerBwdArgs a) {
     inner_bwd_body(a, blockIdx.x, gridDim.x, smem);
 }
 
-extern "C" int cffm_inner_fwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
-    return cffm_inner_fwd_impl(s, theta, ws, B, nullptr, nullptr, (hipStream_t)stream);
-}
-
-int cffm_inner_fwd_impl(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const cffm_tables_t* tab,
-                        const int32_t* ids, hipStream_t stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (B <= 0 || !s->inner_conv) return 0;
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
-    const size_t lds = inner_fwd_lds(g);
-    FusedGather fg;
-    fg.ids = tab ? ids : nullptr;
+InnerFwdArgs StepCtx::inner_fwd_args(const cffm_tables_t* tab, const int32_t* ids) const {
+    InnerFwdArgs ia{};
+    ia.g = g; ia.Ei = at<const float>(wl.Ei); ia.cw = theta + tl.inner_cw; ia.cb = theta + tl.inner_cb;
+    ia.wd = theta + tl.inner_dw; ia.bd = theta + tl.inner_db; ia.inner_out = at(wl.inner_out);
     if (tab) {
+        FusedGather& fg = ia.fg;
+        fg.ids = ids;
         fg.inner = tab->inner_emb; fg.outer = tab->outer_emb; fg.fbias = tab->feat_bias;
-        fg.Ei = (float*)(w + wl.Ei); fg.Eo = (float*)(w + wl.Eo); fg.fb = (float*)(w + wl.fb);
-        fg.keys = (unsigned long long*)(w + wl.sort_keys);
+        fg.Ei = at(wl.Ei); fg.Eo = at(wl.Eo); fg.fb = at(wl.fb);
+        fg.keys = at<unsigned long long>(wl.sort_keys);
         fg.M = s->M; fg.D = s->D;
     }
-    InnerFwdArgs ia;
-    ia.g = g; ia.Ei = (const float*)(w + wl.Ei); ia.cw = theta + tl.inner_cw; ia.cb = theta + tl.inner_cb;
-    ia.wd = theta + tl.inner_dw; ia.bd = theta + tl.inner_db; ia.inner_out = (float*)(w + wl.inner_out); ia.fg = fg;
-    hipLaunchKernelGGL(inner_fwd_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, ia);
+    return ia;
+}
+
+InnerBwdArgs StepCtx::inner_bwd_args(int* nslab) const {
+    const SlabRange& sr = sp.r[sp.inner];
+    float* base = at(wl.gpart) + sr.base - sr.off;      // slab 0 of theta offset x lives at base + x
+    InnerBwdArgs a{};
+    a.g = g; a.B = B;
+    a.Ei = at<const float>(wl.Ei); a.dout = at<const float>(wl.dout);
+    a.out = at<const float>(wl.out); a.y = nullptr; a.loss = s->loss; a.invB = 1.f / (float)B;
+    a.cw = theta + tl.inner_cw; a.cb = theta + tl.inner_cb; a.wd = theta + tl.inner_dw;
+    a.dEi = at(wl.dEi);
+    a.slab_cw = base + tl.inner_cw; a.slab_cb = base + tl.inner_cb; a.slab_dw = base + tl.inner_dw; a.slab_db = base + tl.inner_db;
+    a.slab_stride = sr.len;
+    *nslab = sr.nslab;
+    return a;
+}
+
+extern "C" int cffm_inner_fwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    return cffm_inner_fwd_impl(StepCtx(s, B, theta, ws), nullptr, nullptr, (hipStream_t)stream);
+}
+
+int cffm_inner_fwd_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, hipStream_t stream) {
+    if (!c.s->inner_conv) return 0;
+    const InnerFwdArgs ia = c.inner_fwd_args(tab, ids);
+    hipLaunchKernelGGL(inner_fwd_kernel, dim3(c.B), dim3(256), inner_fwd_lds(c.g), stream, ia);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int cffm_inner_bwd(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, void* stream) {
-    return cffm_inner_bwd_rows(s, theta, ws, B, nullptr, (hipStream_t)stream);
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    return cffm_inner_bwd_rows(StepCtx(s, B, theta, ws), nullptr, (hipStream_t)stream);
 }
 
-int cffm_inner_bwd_wide(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t stream);
+static int cffm_inner_bwd_wide(const StepCtx& c, const RowSrc* rs, hipStream_t stream);
 
-int cffm_inner_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t stream) {
-    int rc = check_shape(s);
+int cffm_inner_bwd_rows(const StepCtx& c, const RowSrc* rs, hipStream_t stream) {
+    if (!c.s->inner_conv) return 0;
+    if (cffm_wide_regather_ok(c.s)) return cffm_inner_bwd_wide(c, rs, stream);
+    const size_t lds = inner_bwd_lds(c.g);
+    int rc = set_lds(inner_bwd_kernel, lds);
     if (rc) return rc;
-    if (B <= 0 || !s->inner_conv) return 0;
-    if (cffm_wide_regather_ok(s)) return cffm_inner_bwd_wide(s, theta, ws, B, rs, stream);
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
-    const size_t lds = inner_bwd_lds(g);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)inner_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    InnerBwdArgs a;
-    const int nslab = fill_inner_bwd_args(s, theta, ws, B, &a);
+    int nslab;
+    InnerBwdArgs a = c.inner_bwd_args(&nslab);
     if (rs) { a.Ei = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }
-    hipLaunchKernelGGL(inner_bwd_kernel, dim3(nslab), dim3(256), lds, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(inner_bwd_kernel, dim3(nslab), dim3(256), lds, stream, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -577,20 +585,22 @@ bool cffm_giw_lds_ok() {
     return ok;
 }
 
-int cffm_gather_inner_fwd_wide(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids, int32_t B,
-                               void* ws, hipStream_t stream, int tab_stride, int tab_rows) {
-    if (!cffm_wide_regather_ok(s) || !tab || !ids) return CFFM_ERR_UNSUPPORTED;
-    if (B <= 0) return 0;
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    const Geo g = make_geo(s);
-    char* w = (char*)ws;
+int cffm_gather_inner_fwd_wide(const StepCtx& c, const RowTables& rows, hipStream_t stream) {
+    const cffm_shape_t* s = c.s;
+    const cffm_tables_t* tab = rows.tab;
+    const int tab_stride = rows.stride;
+    if (!cffm_wide_regather_ok(s) || !tab || !rows.ids) return CFFM_ERR_UNSUPPORTED;
+    const Geo& g = c.g;
+    const cffm_theta_layout_t& tl = c.tl;
+    const cffm_ws_layout_t& wl = c.wl;
+    const float* theta = c.theta;
+    const int32_t B = c.B;
     GatherInnerWideArgs a;
-    a.inner = tab->inner_emb; a.outer = tab->outer_emb; a.fbias = tab->feat_bias; a.ids = ids;
+    a.inner = tab->inner_emb; a.outer = tab->outer_emb; a.fbias = tab->feat_bias; a.ids = rows.ids;
     a.cw = theta + tl.inner_cw; a.cb = theta + tl.inner_cb; a.wd = theta + tl.inner_dw; a.bd = theta + tl.inner_db;
-    a.inner_out = (float*)(w + wl.inner_out); a.t1 = (float*)(w + wl.t1); a.fb = (float*)(w + wl.fb);
-    a.keys = tab_stride > 0 ? nullptr : (unsigned long long*)(w + wl.sort_keys);   // record indices are not update keys
-    a.B = B; a.M = tab_rows > 0 ? tab_rows : s->M; a.F = g.F; a.K = g.K; a.D = g.D; a.P = g.P; a.t1w = 2 * g.D - 2; a.act = g.act;
+    a.inner_out = c.at(wl.inner_out); a.t1 = c.at(wl.t1); a.fb = c.at(wl.fb);
+    a.keys = tab_stride > 0 ? nullptr : c.at<unsigned long long>(wl.sort_keys);   // record indices are not update keys
+    a.B = B; a.M = rows.records > 0 ? rows.records : s->M; a.F = g.F; a.K = g.K; a.D = g.D; a.P = g.P; a.t1w = 2 * g.D - 2; a.act = g.act;
     if (tab_stride > 0 && (tab_stride & 3)) return CFFM_ERR_BAD_SHAPE;            // rows are fetched in 16-byte pieces
     a.row4_in = tab_stride > 0 ? tab_stride / 4 : g.K / 4; a.row4_out = tab_stride > 0 ? tab_stride / 4 : g.D / 4;
     a.fb_stride = tab_stride > 0 ? tab_stride : 1;
@@ -622,7 +632,10 @@ extern "C" int cffm_gather_inner_fwd(const cffm_shape_t* s, const cffm_tables_t*
     int rc = check_shape(s);
     if (rc) return rc;
     if (!t || !theta || !ids || !ws) return CFFM_ERR_BAD_SHAPE;
-    return cffm_gather_inner_fwd_wide(s, t, theta, ids, B, ws, (hipStream_t)stream, 0, 0);
+    if (B <= 0) return cffm_wide_regather_ok(s) ? 0 : CFFM_ERR_UNSUPPORTED;
+    RowTables rows;
+    rows.tab = t; rows.ids = ids;
+    return cffm_gather_inner_fwd_wide(StepCtx(s, B, theta, ws), rows, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -792,16 +805,15 @@ static int launch_ibw(const InnerBwdWideArgs& a, int nslab, hipStream_t st) {
 }
 
 // rs == NULL: rows from ws.Ei.  Returns CFFM_ERR_UNSUPPORTED for shapes outside cffm_wide_regather_ok().
-int cffm_inner_bwd_wide(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t stream) {
-    if (!cffm_wide_regather_ok(s) || s->F > 32) return CFFM_ERR_UNSUPPORTED;
-    if (B <= 0) return 0;
-    InnerBwdArgs o;
-    const int nslab = fill_inner_bwd_args(s, theta, ws, B, &o);
+static int cffm_inner_bwd_wide(const StepCtx& c, const RowSrc* rs, hipStream_t stream) {
+    if (!cffm_wide_regather_ok(c.s) || c.s->F > 32) return CFFM_ERR_UNSUPPORTED;
+    int nslab;
+    const InnerBwdArgs o = c.inner_bwd_args(&nslab);
     InnerBwdWideArgs a;
     a.rows.base = rs ? rs->base : o.Ei; a.rows.idx = rs ? rs->idx : nullptr; a.rows.M = rs ? rs->M : 0; a.rows.stride = rs ? rs->stride : 0;
     a.dout = o.dout; a.out = o.out; a.y = o.y; a.cw = o.cw; a.cb = o.cb; a.wd = o.wd; a.dEi = o.dEi;
     a.slab_cw = o.slab_cw; a.slab_cb = o.slab_cb; a.slab_dw = o.slab_dw; a.slab_db = o.slab_db; a.slab_stride = o.slab_stride;
-    a.B = B; a.F = o.g.F; a.K = o.g.K; a.P = o.g.P; a.act = o.g.act; a.loss = o.loss; a.invB = o.invB; a.L = 1.f;
+    a.B = c.B; a.F = o.g.F; a.K = o.g.K; a.P = o.g.P; a.act = o.g.act; a.loss = o.loss; a.invB = o.invB; a.L = 1.f;
     if (o.g.K == 64) return launch_ibw<32>(a, nslab, stream);
     if (o.g.K == 32) return launch_ibw<16>(a, nslab, stream);
     return CFFM_ERR_UNSUPPORTED;

@@ -266,23 +266,3 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
         slab_db[0] = r[6];
     }
 }
-
-// returns the slab count of the inner range
-static inline int fill_inner_bwd_args(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, InnerBwdArgs* out) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const SlabRange& sr = sp.r[sp.inner];
-    float* base = (float*)(w + wl.gpart) + sr.base - sr.off;      // slab 0 of theta offset x lives at base + x
-    InnerBwdArgs& a = *out;
-    a.g = make_geo(s); a.B = B;
-    a.Ei = (const float*)(w + wl.Ei); a.dout = (const float*)(w + wl.dout);
-    a.out = (const float*)(w + wl.out); a.y = nullptr; a.loss = s->loss; a.invB = 1.f / (float)B;
-    a.cw = theta + tl.inner_cw; a.cb = theta + tl.inner_cb; a.wd = theta + tl.inner_dw;
-    a.dEi = (float*)(w + wl.dEi); a.idx = nullptr; a.idxM = 0; a.idxStride = 0;
-    a.slab_cw = base + tl.inner_cw; a.slab_cb = base + tl.inner_cb; a.slab_dw = base + tl.inner_dw; a.slab_db = base + tl.inner_db;
-    a.slab_stride = sr.len;
-    return sr.nslab;
-}

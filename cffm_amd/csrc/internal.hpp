@@ -5,29 +5,15 @@
 // gather that also emits the sort keys of the sparse update: keys[slot] = (id << 32) | slot
 int cffm_gather_impl(const cffm_shape_t* s, const cffm_tables_t* t, const int32_t* ids, int32_t B, float* Ei, float* Eo,
                      float* fb, unsigned long long* keys, hipStream_t st);
-// do_sum = false skips the separate loss-sum launch (cffm_head_bwd_impl then sums the terms itself)
-int cffm_head_fwd_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, bool do_sum,
-                       hipStream_t st);
-int cffm_head_bwd_impl(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, int64_t B_global,
-                       bool local_sum, float* loss_out, hipStream_t st, bool unscaled = false);
-// theta != nullptr: the dense Adagrad update is fused into the slab reduction
-int cffm_reduce_slabs_impl(const cffm_shape_t* s, void* ws, int32_t B, float* grad, float* theta, float* acc, float lr,
-                           hipStream_t st);
-int cffm_sparse_adagrad_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc,
-                             const int32_t* ids, int64_t n_rows, const float* dEi, const float* dEo, const float* dfb,
-                             void* ws, int32_t B_ws, bool prepacked, hipStream_t st);
-// tab != nullptr: fused step - the kernel gathers the rows of example b itself (all three tables) and leaves
-// Ei/Eo/fb and the packed sort keys in the workspace, so no separate gather launch is needed
-int cffm_inner_fwd_impl(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const cffm_tables_t* tab,
-                        const int32_t* ids, hipStream_t st);
-// fused single-GPU update (both tables branches on): slab reduction + dense Adagrad and the sorted sparse table update
-// as two roles of one launch; the keys must already be sorted in ws.sort_vals
-int cffm_update_all(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
-                    float* theta_acc, float* grad, void* ws, int32_t B, hipStream_t st);
-// ---- one context per ABI call: what every conv launch of a step derives from (s, B, theta, ws) -----------------------------
-// Built once by the entry point (shape checked, B >= 1) and handed down; conv_args / dgrad_args / wgrad_args (conv.hip) return the
-// complete argument block of layer l, every optional member decided there and nowhere else.
-struct ConvArgs; struct DgradArgs; struct WgradArgs;
+// ---- one context per ABI call: what every launch of a step derives from (s, B, theta, ws) ----------------------------------
+// Built once by the entry point (shape checked, B >= 1; the update entry points, whose workspace is sized by B_ws, build it with B_ws)
+// and handed down: nothing below an entry point derives a layout or a slab plan again.  The builders return complete, value-initialised
+// argument blocks, every optional member decided there and nowhere else: conv_args / dgrad_args / wgrad_args of layer l (conv.hip),
+// head_args / head_bwd_args (head.hip), inner_fwd_args / inner_bwd_args (inner.hip), sparse_args (optim.hip).
+struct ConvArgs; struct DgradArgs; struct WgradArgs; struct HeadArgs; struct HeadBwdArgs; struct InnerFwdArgs; struct InnerBwdArgs;
+struct SparseArgs; struct BwdOpts; struct RowGrads;
+// late 1/L of the data-parallel step (optim.hip); on == 0: none
+struct LateScale { const float* sum; float inv_Bg; int on; };
 int cffm_ws_layout_from(const cffm_shape_t* s, int32_t B, const cffm_theta_layout_t& tl, const SlabPlan& sp, cffm_ws_layout_t* out);
 struct StepCtx {
     const cffm_shape_t* s;
@@ -48,6 +34,28 @@ struct StepCtx {
     ConvArgs conv_args(int l) const;
     DgradArgs dgrad_args(int l) const;
     WgradArgs wgrad_args(int l) const;
+    // s0_ready: ws.t1[:, 0:D] already holds the s0 pool (the fused gather computed it): ws.Eo is not read
+    HeadArgs head_args(const float* y, bool s0_ready = false) const;
+    HeadBwdArgs head_bwd_args(const float* y, int64_t B_global, const BwdOpts& o) const;
+    // tab != nullptr: the kernel gathers the rows of its example itself (all three tables) and leaves Ei / Eo / fb and the packed sort
+    // keys in the workspace
+    InnerFwdArgs inner_fwd_args(const cffm_tables_t* tab = nullptr, const int32_t* ids = nullptr) const;
+    InnerBwdArgs inner_bwd_args(int* nslab) const;       // *nslab: slabs of the inner range (= workgroups of the kernel)
+    // segment-sum + Adagrad sweep over the n_rows sorted keys in ws.sort_vals
+    SparseArgs sparse_args(const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r, const LateScale& ls) const;
+};
+// The per-slot row gradients a table update or a packing kernel reads.  dEi / dEo == NULL: that branch is disabled (CFFM.py:301,
+// :348) - it has no table, nothing is applied and its columns travel as zeros.  s*: floats between consecutive slots.
+struct RowGrads {
+    const float *dEi, *dEo, *dfb;
+    int64_t sEi, sEo, sfb;
+    static RowGrads of_ws(const StepCtx& c) {            // what the backward left in this context's workspace
+        return {c.s->inner_conv ? c.at<const float>(c.wl.dEi) : nullptr, c.s->outer_conv ? c.at<const float>(c.wl.dEo) : nullptr,
+                c.at<const float>(c.wl.dfb), c.s->K, c.s->D, 1};
+    }
+    static RowGrads packed(const cffm_shape_t* s, const float* rows, int64_t W) {    // rows [n][W] = (id bits | dEi | dEo | dfb ...)
+        return {s->inner_conv ? rows + 1 : nullptr, s->outer_conv ? rows + 1 + s->K : nullptr, rows + 1 + s->K + s->D, W, W, W};
+    }
 };
 // wide shapes whose forward did not materialise Ei / Eo: the tables (or, stride / records > 0, the packed records) the backward
 // re-reads its rows from
@@ -79,35 +87,48 @@ int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpt
 int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t st, int* next_layer);
 // bwd_fused01_ok: layers 3..0 below the fused top in one launch
 int cffm_conv01_bwd_impl(const StepCtx& c, hipStream_t st);
-// the two halves of the sparse update: stable sort of the packed keys, then the segment-sum + Adagrad sweep
-int cffm_sort_keys_impl(const cffm_shape_t* s, const int32_t* ids, int64_t n_rows, void* ws, int32_t B_ws, bool prepacked,
-                        hipStream_t st, int64_t id_stride = 1);
-struct LateScale;
-int cffm_sparse_apply_strided(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows,
-                              const float* dEi, int64_t sEi, const float* dEo, int64_t sEo, const float* dfb, int64_t sfb,
-                              void* ws, int32_t B_ws, LateScale ls, hipStream_t st);
-int cffm_sparse_apply_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows,
-                           const float* dEi, const float* dEo, const float* dfb, void* ws, int32_t B_ws, hipStream_t st);
+// the head (head.hip).  sum_loss = false skips the separate loss-sum launch (the head backward then sums the terms itself)
+struct HeadFwdOpts {
+    bool sum_loss = true;
+    bool s0_ready = false;               // see StepCtx::head_args
+};
+int cffm_head_fwd_impl(const StepCtx& c, const float* y, const HeadFwdOpts& o, hipStream_t st);
+int cffm_head_bwd_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t st);
+// the inner branch (inner.hip); tab / ids as StepCtx::inner_fwd_args, rs != NULL: the rows come straight from the table
+int cffm_inner_fwd_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, hipStream_t st);
+int cffm_inner_bwd_rows(const StepCtx& c, const RowSrc* rs, hipStream_t st);
+// theta != nullptr: the dense Adagrad update is fused into the slab reduction
+int cffm_reduce_slabs_impl(const StepCtx& c, float* grad, float* theta, float* acc, float lr, hipStream_t st);
+// fused single-GPU update (both tables branches on): slab reduction + dense Adagrad and the sorted sparse table update
+// as two roles of one launch; the keys must already be sorted in ws.sort_vals
+int cffm_update_all(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta, float* theta_acc,
+                    float* grad, hipStream_t st);
+// the two steps of the sparse update: stable sort of the packed keys (ws.sort_keys -> ws.sort_vals), then the segment-sum + Adagrad
+// sweep.  The sort returns early for n_rows <= 0 and refuses n_rows > B * F of its context.
+struct SortOpts {
+    bool prepacked = false;              // ws.sort_keys already holds the packed keys: ids is not read
+    int64_t id_stride = 1;               // ints between consecutive ids (the id column of packed rows)
+};
+int cffm_sort_keys_impl(const StepCtx& c, const int32_t* ids, int64_t n_rows, const SortOpts& o, hipStream_t st);
+int cffm_sparse_apply(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r,
+                      const LateScale& ls, hipStream_t st);
 // slab reduction (gradients only) and the packing of the rows + local loss sum, two roles of one launch
-int cffm_dp_tail(const cffm_shape_t* s, const int32_t* ids, int32_t B, void* ws, float* grad, float* rows, bool with_run,
-                 hipStream_t st);
+int cffm_dp_tail(const StepCtx& c, const int32_t* ids, float* grad, float* rows, bool with_run, hipStream_t st);
 // dense-table variant of cffm_dp_tail: slab reduction ∥ scatter of this rank's summed row gradients into flat
-int cffm_dp_tail_dense(const cffm_shape_t* s, int32_t B, void* ws, float* flat, hipStream_t st);
-// rows[slot] = (id bits | dEi | dEo | dfb) for the all-gather of the data-parallel step; also copies the local
-// loss-term sum (scalars[0]) to *sum_dst
-int cffm_pack_rows(const cffm_shape_t* s, const int32_t* ids, int32_t B, const float* dEi, const float* dEo, const float* dfb,
-                   const float* scalars, float* sum_dst, float* rows, hipStream_t st);
+int cffm_dp_tail_dense(const StepCtx& c, float* flat, hipStream_t st);
+// rows[slot] = (id bits | dEi | dEo | dfb) of the workspace's row gradients for the all-gather of the data-parallel step; also copies
+// the local loss-term sum (scalars[0]) to *sum_dst
+int cffm_pack_rows(const StepCtx& c, const int32_t* ids, float* sum_dst, float* rows, hipStream_t st);
 // whole forward of the fused step in one launch (+ the key sort); only for shapes cffm_fwd_all_ok() accepts
 bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B);
 int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, const float* y, hipStream_t st,
                       bool rank_keys);
 // CFFM_LOSS_SQUARE_L2: tables updated densely with g = scatter(row grads) + lamda * w (feature_bias stays sparse)
-int cffm_tables_adagrad_l2(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids,
-                           int64_t n_rows, void* ws, int32_t B_ws, hipStream_t st);
+int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids, int64_t n_rows,
+                           hipStream_t st);
 // SGD / Momentum / Adam updates of theta and the three tables from grad + the row gradients in ws (CFFM.py:519-529)
-int cffm_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2,
-                   float* theta, float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, void* ws,
-                   int32_t B_ws, int64_t step, hipStream_t st);
+int cffm_apply_opt(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
+                   float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, int64_t step, hipStream_t st);
 
 // ---- wide shapes (Pp > 64): rows consumed where they are fetched, nothing materialised (RowSrc, common.hpp) ---------------
 bool cffm_wide_regather_ok(const cffm_shape_t* s);
@@ -115,11 +136,6 @@ int64_t cffm_wb3_bytes(int Pp);     // bytes of the pre-split filter image of th
 bool cffm_giw_lds_ok();     // the fused gather's LDS addressing assumption holds for every instance (inner.hip; checked on the host)
 // tf.nn.embedding_lookup x3 fused with the inner branch, the s0 pool and the first-order inputs: ids -> ws.inner_out,
 // ws.t1[:, 0:D] (s0), ws.fb, ws.sort_keys; Ei / Eo are NOT written
-// tab_stride > 0: the three "tables" are views into ONE array of records of tab_stride floats (the packed rows a row-sharded rank
-// received: tab->inner_emb = records, outer_emb = records + K, feat_bias = records + K + D) with tab_rows records; ids = slot -> record
-int cffm_gather_inner_fwd_wide(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ids, int32_t B,
-                               void* ws, hipStream_t st, int tab_stride = 0, int tab_rows = 0);
-int cffm_inner_bwd_rows(const cffm_shape_t* s, const float* theta, void* ws, int32_t B, const RowSrc* rs, hipStream_t st);
-// s0_ready: ws.t1[:, 0:D] already holds the s0 pool (the fused gather computed it): ws.Eo is not read
-int cffm_head_fwd_impl2(const cffm_shape_t* s, const float* theta, void* ws, const float* y, int32_t B, bool do_sum, bool s0_ready,
-                        hipStream_t st);
+// rows.stride > 0: the three "tables" are views into ONE array of records of rows.stride floats (the packed rows a row-sharded rank
+// received: tab->inner_emb = records, outer_emb = records + K, feat_bias = records + K + D) with rows.records records; ids = slot -> record
+int cffm_gather_inner_fwd_wide(const StepCtx& c, const RowTables& rows, hipStream_t st);

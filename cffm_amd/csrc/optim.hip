@@ -69,7 +69,6 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
 // WITHOUT the 1/L of the RMSE-style loss (CFFM.py:493), because L needs the loss-term sum over the GLOBAL batch,
 // which only exists after the all-reduce that also carries the gradients.  Every gradient is linear in dL/dout,
 // so the factor 1/L = rsqrt(sum / Bg + 1e-10) is applied here, on the summed gradient.
-struct LateScale { const float* sum; float inv_Bg; int on; };
 __device__ __forceinline__ float late_scale(const LateScale& ls) {
     return ls.on ? 1.f / sqrtf(ls.sum[0] * ls.inv_Bg + 1e-10f) : 1.f;
 }
@@ -230,25 +229,22 @@ __global__ __launch_bounds__(256) void dp_tail_kernel(const float* __restrict__ 
     else pack_rows_body(blockIdx.x - n_reduce, n_pack, pa, red);
 }
 
-int cffm_dp_tail(const cffm_shape_t* s, const int32_t* ids, int32_t B, void* ws, float* grad, float* rows, bool with_run,
-                 hipStream_t st) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
+int cffm_dp_tail(const StepCtx& c, const int32_t* ids, float* grad, float* rows, bool with_run, hipStream_t st) {
+    const cffm_shape_t* s = c.s;
+    const cffm_theta_layout_t& tl = c.tl;
+    const cffm_ws_layout_t& wl = c.wl;
+    const RowGrads r = RowGrads::of_ws(c);
     PackArgs pa;
-    pa.ids = ids; pa.n_slots = (int64_t)B * s->F; pa.K = s->K; pa.D = s->D; pa.B = B;
-    pa.dEi = s->inner_conv ? (const float*)(w + wl.dEi) : nullptr; pa.dEo = s->outer_conv ? (const float*)(w + wl.dEo) : nullptr;
-    pa.dfb = (const float*)(w + wl.dfb);
-    pa.sqerr = (const float*)(w + wl.sqerr); pa.sum_dst = grad + tl.n; pa.rows = rows; pa.scalars = (float*)(w + wl.scalars);
+    pa.ids = ids; pa.n_slots = (int64_t)c.B * s->F; pa.K = s->K; pa.D = s->D; pa.B = c.B;
+    pa.dEi = r.dEi; pa.dEo = r.dEo; pa.dfb = r.dfb;
+    pa.sqerr = c.at<const float>(wl.sqerr); pa.sum_dst = grad + tl.n; pa.rows = rows; pa.scalars = c.at(wl.scalars);
     // n_slots * W floats: W = K + D + 2 is even for the float4-aligned K, D this library accepts, so the run is 8-byte aligned
-    pa.keys_sorted = with_run ? (const unsigned long long*)(w + wl.sort_vals) : nullptr;
+    pa.keys_sorted = with_run ? c.at<const unsigned long long>(wl.sort_vals) : nullptr;
     const int n_reduce = reduce_slab_wgs(tl.n);
     const int64_t total = pa.n_slots * (1 + s->K + s->D + 1);
     int n_pack = (int)((total + 1023) / 1024);
     if (n_pack > 2048) n_pack = 2048;
-    hipLaunchKernelGGL(dp_tail_kernel, dim3(n_reduce + n_pack), dim3(256), 0, st, (const float*)(w + wl.gpart), (int64_t)tl.n, sp,
+    hipLaunchKernelGGL(dp_tail_kernel, dim3(n_reduce + n_pack), dim3(256), 0, st, c.at<const float>(wl.gpart), (int64_t)tl.n, c.sp,
                        grad, n_reduce, pa, n_pack);
     CFFM_CHECK_LAUNCH();
     return 0;
@@ -354,20 +350,14 @@ extern "C" int cffm_debug_upd_times(unsigned long long* host32) {
 #endif
 
 extern "C" int cffm_reduce_slabs(const cffm_shape_t* s, void* ws, int32_t B, float* grad, void* stream) {
-    return cffm_reduce_slabs_impl(s, ws, B, grad, nullptr, nullptr, 0.f, (hipStream_t)stream);
-}
-
-int cffm_reduce_slabs_impl(const cffm_shape_t* s, void* ws, int32_t B, float* grad, float* theta, float* acc, float lr,
-                           hipStream_t stream) {
     int rc = check_shape(s);
     if (rc) return rc;
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const float* gpart = (const float*)((char*)ws + wl.gpart);
-    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)reduce_slab_wgs(tl.n)), dim3(256), 0, stream, gpart,
-                       (int64_t)tl.n, sp, grad, theta, acc, lr);
+    return cffm_reduce_slabs_impl(StepCtx(s, B, nullptr, ws), grad, nullptr, nullptr, 0.f, (hipStream_t)stream);
+}
+
+int cffm_reduce_slabs_impl(const StepCtx& c, float* grad, float* theta, float* acc, float lr, hipStream_t stream) {
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)reduce_slab_wgs(c.tl.n)), dim3(256), 0, stream,
+                       c.at<const float>(c.wl.gpart), (int64_t)c.tl.n, c.sp, grad, theta, acc, lr);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -384,35 +374,25 @@ extern "C" int cffm_dense_adagrad(float* theta, float* acc, const float* grad, i
 extern "C" int cffm_sparse_adagrad(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc,
                                    const int32_t* ids, int64_t n_rows, const float* dEi, const float* dEo,
                                    const float* dfb, void* ws, int32_t B_ws, void* stream) {
-    return cffm_sparse_adagrad_impl(s, tab, acc, ids, n_rows, dEi, dEo, dfb, ws, B_ws, false, (hipStream_t)stream);
-}
-
-int cffm_sparse_adagrad_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc,
-                             const int32_t* ids, int64_t n_rows, const float* dEi, const float* dEo, const float* dfb,
-                             void* ws, int32_t B_ws, bool prepacked, hipStream_t st) {
-    int rc = cffm_sort_keys_impl(s, ids, n_rows, ws, B_ws, prepacked, st);
-    if (rc) return rc;
-    return cffm_sparse_apply_impl(s, tab, acc, n_rows, dEi, dEo, dfb, ws, B_ws, st);
-}
-
-int cffm_sort_keys_impl(const cffm_shape_t* s, const int32_t* ids, int64_t n_rows, void* ws, int32_t B_ws, bool prepacked,
-                        hipStream_t st, int64_t id_stride) {
     int rc = check_shape(s);
     if (rc) return rc;
+    const StepCtx c(s, B_ws, nullptr, ws);               // (the sort returns before it touches the workspace where B_ws < 1)
+    if ((rc = cffm_sort_keys_impl(c, ids, n_rows, SortOpts(), (hipStream_t)stream))) return rc;
+    return cffm_sparse_apply(c, tab, acc, n_rows, RowGrads{dEi, dEo, dfb, s->K, s->D, 1}, LateScale{nullptr, 0.f, 0}, (hipStream_t)stream);
+}
+
+int cffm_sort_keys_impl(const StepCtx& c, const int32_t* ids, int64_t n_rows, const SortOpts& o, hipStream_t st) {
+    const cffm_shape_t* s = c.s;
     if (n_rows <= 0) return 0;
-    if (n_rows > (int64_t)B_ws * s->F) return CFFM_ERR_BAD_SHAPE;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B_ws, &wl);
-    char* w = (char*)ws;
-    unsigned long long* keys_in = (unsigned long long*)(w + wl.sort_keys);     // (id << 32) | slot
-    unsigned long long* keys_out = (unsigned long long*)(w + wl.sort_vals);
-    void* tmp = (void*)(w + wl.sort_tmp);
+    if (n_rows > (int64_t)c.B * s->F) return CFFM_ERR_BAD_SHAPE;
+    unsigned long long* keys_in = c.at<unsigned long long>(c.wl.sort_keys);     // (id << 32) | slot
+    unsigned long long* keys_out = c.at<unsigned long long>(c.wl.sort_vals);
+    void* tmp = c.at<void>(c.wl.sort_tmp);
     size_t tmp_bytes = 0;
-    int bits = 1;
-    while ((1ll << bits) <= (long long)s->M && bits < 31) ++bits;      // ids 0 .. M (M = the key of every out-of-range id)
+    const int bits = id_key_bits(s->M);
     // slots are unique, so sorting the packed keys IS the stable sort by id with slots ascending inside a segment
-    if (!prepacked) {
-        hipLaunchKernelGGL(pack_keys_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, ids, keys_in, n_rows, id_stride, s->M);
+    if (!o.prepacked) {
+        hipLaunchKernelGGL(pack_keys_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, ids, keys_in, n_rows, o.id_stride, s->M);
         CFFM_CHECK_LAUNCH();
     }
     if (n_rows <= 4096) {                       // one workgroup, one launch
@@ -427,61 +407,40 @@ int cffm_sort_keys_impl(const cffm_shape_t* s, const int32_t* ids, int64_t n_row
     hipError_t e = rocprim::radix_sort_keys((void*)nullptr, tmp_bytes, keys_in, keys_out, (size_t)n_rows, 0u,
                                             (unsigned)(32 + bits), st);
     if (e != hipSuccess) return (int)e;
-    if (tmp_bytes > (size_t)wl.sort_tmp_bytes) return CFFM_ERR_BAD_SHAPE;
+    if (tmp_bytes > (size_t)c.wl.sort_tmp_bytes) return CFFM_ERR_BAD_SHAPE;
     e = rocprim::radix_sort_keys(tmp, tmp_bytes, keys_in, keys_out, (size_t)n_rows, 0u, (unsigned)(32 + bits), st);
     return e == hipSuccess ? 0 : (int)e;
 }
 
-static void fill_sparse_args(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows,
-                             const float* dEi, int64_t sEi, const float* dEo, int64_t sEo, const float* dfb, int64_t sfb,
-                             void* ws, int32_t B_ws, LateScale ls, SparseArgs* out) {
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B_ws, &wl);
-    SparseArgs& a = *out;
-    a.keys = (const unsigned long long*)((char*)ws + wl.sort_vals);
+SparseArgs StepCtx::sparse_args(const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r,
+                                const LateScale& ls) const {
+    SparseArgs a{};                       // run_len = 0: the slots address one array (cffm_dp_apply sets the run members for its blocks)
+    a.keys = at<const unsigned long long>(wl.sort_vals);
     a.n = n_rows; a.M = s->M; a.K = s->K; a.D = s->D;
-    a.dEi = dEi; a.dEo = dEo; a.dfb = dfb;
+    a.dEi = r.dEi; a.dEo = r.dEo; a.dfb = r.dfb;
     a.inner = tab->inner_emb; a.outer = tab->outer_emb; a.fbias = tab->feat_bias;
     a.a_inner = acc->inner_emb; a.a_outer = acc->outer_emb; a.a_fbias = acc->feat_bias;
-    a.lr = s->lr; a.sEi = sEi; a.sEo = sEo; a.sfb = sfb; a.ls = ls;
-    a.run_len = 0; a.run_stride = 0; a.inv_run_len = 0.f;
+    a.lr = s->lr; a.sEi = r.sEi; a.sEo = r.sEo; a.sfb = r.sfb; a.ls = ls;
+    return a;
 }
 
-int cffm_sparse_apply_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows,
-                           const float* dEi, const float* dEo, const float* dfb, void* ws, int32_t B_ws, hipStream_t st) {
-    LateScale ls = {nullptr, 0.f, 0};
-    return cffm_sparse_apply_strided(s, tab, acc, n_rows, dEi, s->K, dEo, s->D, dfb, 1, ws, B_ws, ls, st);
-}
-
-int cffm_sparse_apply_strided(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows,
-                              const float* dEi, int64_t sEi, const float* dEo, int64_t sEo, const float* dfb, int64_t sfb,
-                              void* ws, int32_t B_ws, LateScale ls, hipStream_t st) {
+int cffm_sparse_apply(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r,
+                      const LateScale& ls, hipStream_t st) {
     if (n_rows <= 0) return 0;
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B_ws, &wl);
-    SparseArgs a;
-    fill_sparse_args(s, tab, acc, n_rows, dEi, sEi, dEo, sEo, dfb, sfb, ws, B_ws, ls, &a);
+    const SparseArgs a = c.sparse_args(tab, acc, n_rows, r, ls);
     hipLaunchKernelGGL(sparse_adagrad_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
 
 // fused single-GPU update: slab reduction + dense Adagrad and the sparse table update in one launch
-int cffm_update_all(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
-                    float* theta_acc, float* grad, void* ws, int32_t B, hipStream_t st) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
-    const int64_t n_rows = (int64_t)B * s->F;
-    LateScale ls = {nullptr, 0.f, 0};
-    SparseArgs a;
-    fill_sparse_args(s, tab, tab_acc, n_rows, (const float*)(w + wl.dEi), s->K, (const float*)(w + wl.dEo), s->D,
-                     (const float*)(w + wl.dfb), 1, ws, B, ls, &a);
-    const int n_reduce = reduce_slab_wgs(tl.n);
+int cffm_update_all(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta, float* theta_acc,
+                    float* grad, hipStream_t st) {
+    const int64_t n_rows = (int64_t)c.B * c.s->F;
+    const SparseArgs a = c.sparse_args(tab, tab_acc, n_rows, RowGrads::of_ws(c), LateScale{nullptr, 0.f, 0});
+    const int n_reduce = reduce_slab_wgs(c.tl.n);
     hipLaunchKernelGGL(update_all_kernel, dim3((unsigned)(n_reduce + (n_rows + 3) / 4)), dim3(256), 0, st,
-                       (const float*)(w + wl.gpart), (int64_t)tl.n, sp, grad, theta, theta_acc, s->lr, n_reduce, a);
+                       c.at<const float>(c.wl.gpart), (int64_t)c.tl.n, c.sp, grad, theta, theta_acc, c.s->lr, n_reduce, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -495,34 +454,27 @@ extern "C" int cffm_dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, co
     if (rc) return rc;
     if (s->optimizer != CFFM_OPT_ADAGRAD) return CFFM_ERR_UNSUPPORTED;    // the data-parallel update is Adagrad only
     hipStream_t st = (hipStream_t)stream;
-    cffm_theta_layout_t tl;
-    cffm_theta_layout(s, &tl);
+    // B_ws < 1: every path that touches the workspace refuses (n_rows > B_ws * F) or has nothing to do (n_rows <= 0) before it would
+    const StepCtx c(s, B_ws, theta, ws);
+    const cffm_theta_layout_t& tl = c.tl;
     LateScale ls = {grad_sum + tl.n, 1.f / (float)B_global, s->loss == CFFM_LOSS_SQUARE_RMSE ? 1 : 0};
     const int64_t W = 1 + s->K + s->D + 1;
-    // a disabled branch (CFFM.py:301, :348) has no table: its columns of the rows are zeros and are not applied
-    const float* rEi = s->inner_conv ? rows + 1 : nullptr;
-    const float* rEo = s->outer_conv ? rows + 1 + s->K : nullptr;
+    const RowGrads rg = RowGrads::packed(s, rows, W);
     const int n_dense = (int)((tl.n + 255) / 256);
     if (n_runs > 0) {
         // sorted runs (one per rank, from cffm_dp_local): merge by rank, rows addressed block-wise
-        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > 150 * 1024) return CFFM_ERR_BAD_SHAPE;
+        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > CFFM_LDS_SHARED_CU) return CFFM_ERR_BAD_SHAPE;
         const int m = (int)(n_rows / n_runs);
         if (m % s->F || !cffm_fwd_all_ok(s, m / s->F)) return CFFM_ERR_UNSUPPORTED;      // the runs only exist on that path
-        cffm_ws_layout_t wl;
-        cffm_ws_layout(s, B_ws, &wl);
         MergeArgs ma;
         ma.rows = rows; ma.block_floats = (int64_t)m * (W + 2); ma.keys_off = (int64_t)m * W; ma.m = m; ma.n_runs = n_runs;
-        ma.out = (unsigned long long*)((char*)ws + wl.sort_vals);
+        ma.out = c.at<unsigned long long>(c.wl.sort_vals);
         const size_t lds = (size_t)n_rows * 4;
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void*)dp_head_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
+        if ((rc = set_lds(dp_head_merge_kernel, lds))) return rc;
         hipLaunchKernelGGL(dp_head_merge_kernel, dim3(n_dense + (unsigned)((n_rows + 255) / 256)), dim3(256), lds, st, theta, theta_acc,
                            grad_sum, (int64_t)tl.n, s->lr, ls, loss_out, n_dense, ma);
         CFFM_CHECK_LAUNCH();
-        SparseArgs a;
-        fill_sparse_args(s, tab, acc, n_rows, rEi, W, rEo, W, rows + 1 + s->K + s->D, W, ws, B_ws, ls, &a);
+        SparseArgs a = c.sparse_args(tab, acc, n_rows, rg, ls);
         a.run_len = m; a.run_stride = ma.block_floats; a.inv_run_len = 1.f / (float)m;
         hipLaunchKernelGGL(sparse_adagrad_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a);
         CFFM_CHECK_LAUNCH();
@@ -530,21 +482,20 @@ extern "C" int cffm_dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, co
     }
     if (n_rows > 0 && n_rows <= 8192 && n_rows <= (int64_t)B_ws * s->F) {
         // dense update and key placement are independent: one launch, two roles
-        cffm_ws_layout_t wl;
-        cffm_ws_layout(s, B_ws, &wl);
         const int n_rank = 256;                              // kpw = ceil(n_rows / 256) <= 32 keys per workgroup
         hipLaunchKernelGGL(dp_head_kernel, dim3(n_dense + n_rank), dim3(256), 0, st, theta, theta_acc, grad_sum, (int64_t)tl.n,
                            s->lr, ls, loss_out, n_dense, (const int32_t*)rows, W, (int)n_rows, n_rank,
-                           (unsigned long long*)((char*)ws + wl.sort_vals));
+                           c.at<unsigned long long>(c.wl.sort_vals));
         CFFM_CHECK_LAUNCH();
     } else {
         hipLaunchKernelGGL(dense_adagrad_kernel, dim3((unsigned)n_dense), dim3(256), 0, st, theta, theta_acc, grad_sum,
                            (int64_t)tl.n, s->lr, ls, loss_out);
         CFFM_CHECK_LAUNCH();
-        rc = cffm_sort_keys_impl(s, (const int32_t*)rows, n_rows, ws, B_ws, false, st, W);
-        if (rc) return rc;
+        SortOpts so;
+        so.id_stride = W;                                    // the id column of the rows
+        if ((rc = cffm_sort_keys_impl(c, (const int32_t*)rows, n_rows, so, st))) return rc;
     }
-    return cffm_sparse_apply_strided(s, tab, acc, n_rows, rEi, W, rEo, W, rows + 1 + s->K + s->D, W, ws, B_ws, ls, st);
+    return cffm_sparse_apply(c, tab, acc, n_rows, rg, ls, st);
 }
 
 // ---- data-parallel step for SMALL vocabularies: the tables' gradients travel as one dense buffer --------------------
@@ -599,24 +550,23 @@ __global__ __launch_bounds__(256) void dp_tail_dense_kernel(const float* __restr
     else scatter_rows_body(blockIdx.x - n_reduce, sa, red);
 }
 
-int cffm_dp_tail_dense(const cffm_shape_t* s, int32_t B, void* ws, float* flat, hipStream_t st) {
-    cffm_theta_layout_t tl; cffm_ws_layout_t wl;
-    cffm_theta_layout(s, &tl); cffm_ws_layout(s, B, &wl);
-    char* w = (char*)ws;
-    SlabPlan sp;
-    make_slab_plan(s, B, tl, &sp);
+int cffm_dp_tail_dense(const StepCtx& c, float* flat, hipStream_t st) {
+    const cffm_shape_t* s = c.s;
+    const cffm_theta_layout_t& tl = c.tl;
+    const cffm_ws_layout_t& wl = c.wl;
     const int64_t toff = dp_dense_table_off(tl);
+    const RowGrads r = RowGrads::of_ws(c);           // both branches are on (cffm_fwd_all_ok)
     ScatterArgs sa;
-    sa.keys = (const unsigned long long*)(w + wl.sort_vals); sa.n = (int64_t)B * s->F;
-    sa.M = s->M; sa.K = s->K; sa.D = s->D; sa.B = B;
-    sa.dEi = (const float*)(w + wl.dEi); sa.dEo = (const float*)(w + wl.dEo); sa.dfb = (const float*)(w + wl.dfb);
-    sa.sqerr = (const float*)(w + wl.sqerr);
+    sa.keys = c.at<const unsigned long long>(wl.sort_vals); sa.n = (int64_t)c.B * s->F;
+    sa.M = s->M; sa.K = s->K; sa.D = s->D; sa.B = c.B;
+    sa.dEi = r.dEi; sa.dEo = r.dEo; sa.dfb = r.dfb;
+    sa.sqerr = c.at<const float>(wl.sqerr);
     sa.Gi = flat + toff; sa.Go = sa.Gi + (int64_t)s->M * s->K; sa.Gfb = sa.Go + (int64_t)s->M * s->D;
-    sa.sum_dst = flat + tl.n; sa.scalars = (float*)(w + wl.scalars);
+    sa.sum_dst = flat + tl.n; sa.scalars = c.at(wl.scalars);
     const int n_reduce = reduce_slab_wgs(tl.n);
     const int n_scatter = 1 + (int)((sa.n + 3) / 4);
-    hipLaunchKernelGGL(dp_tail_dense_kernel, dim3(n_reduce + n_scatter), dim3(256), 0, st, (const float*)(w + wl.gpart),
-                       (int64_t)tl.n, sp, flat, n_reduce, sa);
+    hipLaunchKernelGGL(dp_tail_dense_kernel, dim3(n_reduce + n_scatter), dim3(256), 0, st, c.at<const float>(wl.gpart),
+                       (int64_t)tl.n, c.sp, flat, n_reduce, sa);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -717,23 +667,24 @@ __global__ __launch_bounds__(256) void table_adagrad_l2_kernel(float* __restrict
     w[i] -= lr * g / sqrtf(a);
 }
 
-int cffm_tables_adagrad_l2(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids,
-                           int64_t n_rows, void* ws, int32_t B_ws, hipStream_t st) {
-    cffm_ws_layout_t wl;
-    cffm_ws_layout(s, B_ws, &wl);
-    char* w = (char*)ws;
-    float* Gi = (float*)(w + wl.Gi);
-    float* Go = (float*)(w + wl.Go);
+int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids, int64_t n_rows,
+                           hipStream_t st) {
+    const cffm_shape_t* s = c.s;
+    const cffm_ws_layout_t& wl = c.wl;
+    float* Gi = c.at(wl.Gi);
+    float* Go = c.at(wl.Go);
     const int64_t ni = (int64_t)s->M * s->K, no = (int64_t)s->M * s->D;
     hipError_t e = hipMemsetAsync(Gi, 0, (size_t)ni * 4, st);
     if (e != hipSuccess) return (int)e;
     e = hipMemsetAsync(Go, 0, (size_t)no * 4, st);
     if (e != hipSuccess) return (int)e;
-    int rc = cffm_sort_keys_impl(s, ids, n_rows, ws, B_ws, true, st);
+    SortOpts so;
+    so.prepacked = true;
+    int rc = cffm_sort_keys_impl(c, ids, n_rows, so, st);
     if (rc) return rc;
-    const unsigned long long* keys = (const unsigned long long*)(w + wl.sort_vals);
-    hipLaunchKernelGGL(scatter_rows_l2_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, keys, n_rows, s->M, s->K,
-                       s->D, (const float*)(w + wl.dEi), (const float*)(w + wl.dEo), (const float*)(w + wl.dfb), Gi, Go,
+    const RowGrads r = RowGrads::of_ws(c);           // both branches are on (cffm_train_step refuses the loss otherwise)
+    hipLaunchKernelGGL(scatter_rows_l2_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st,
+                       c.at<const unsigned long long>(wl.sort_vals), n_rows, s->M, s->K, s->D, r.dEi, r.dEo, r.dfb, Gi, Go,
                        tab->feat_bias, acc->feat_bias, s->lr);
     CFFM_CHECK_LAUNCH();
     hipLaunchKernelGGL(table_adagrad_l2_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, tab->inner_emb,
@@ -813,12 +764,11 @@ __global__ __launch_bounds__(256) void sparse_opt_kernel(const unsigned long lon
     }
 }
 
-int cffm_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2,
-                   float* theta, float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, void* ws,
-                   int32_t B_ws, int64_t step, hipStream_t st) {
-    cffm_ws_layout_t wl; cffm_theta_layout_t tl;
-    cffm_ws_layout(s, B_ws, &wl); cffm_theta_layout(s, &tl);
-    char* w = (char*)ws;
+int cffm_apply_opt(const StepCtx& cx, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
+                   float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, int64_t step, hipStream_t st) {
+    const cffm_shape_t* s = cx.s;
+    const cffm_theta_layout_t& tl = cx.tl;
+    const cffm_ws_layout_t& wl = cx.wl;
     OptConst c;
     c.opt = s->optimizer; c.lr = s->lr; c.b1 = 0.9f; c.b2 = 0.999f; c.omb1 = (float)(1.0 - 0.9); c.omb2 = (float)(1.0 - 0.999); c.eps = 1e-8f; c.mom = 0.95f;
     c.lr_t = (float)((double)s->lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
@@ -832,18 +782,20 @@ int cffm_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_t
     float *Gi = nullptr, *Go = nullptr, *Gfb = nullptr;
     const int64_t ni = (int64_t)s->M * s->K, no = (int64_t)s->M * s->D, nf = s->M;
     if (adam || l2) {
-        Gi = (float*)(w + wl.Gi); Go = (float*)(w + wl.Go); Gfb = (float*)(w + wl.Gfb);
+        Gi = cx.at(wl.Gi); Go = cx.at(wl.Go); Gfb = cx.at(wl.Gfb);
         hipError_t e = hipMemsetAsync(Gi, 0, (size_t)(wl.Gfb + nf * 4 - wl.Gi), st);     // the three buffers are contiguous
         if (e != hipSuccess) return (int)e;
     }
-    int rc = cffm_sort_keys_impl(s, ids, n_rows, ws, B_ws, true, st);
+    SortOpts so;
+    so.prepacked = true;
+    int rc = cffm_sort_keys_impl(cx, ids, n_rows, so, st);
     if (rc) return rc;
+    const RowGrads r = RowGrads::of_ws(cx);
     cffm_tables_t t1 = st1 ? *st1 : cffm_tables_t{nullptr, nullptr, nullptr};
     cffm_tables_t t2 = st2 ? *st2 : cffm_tables_t{nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(sparse_opt_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st,
-                       (const unsigned long long*)(w + wl.sort_vals), n_rows, s->M, s->K, s->D,
-                       s->inner_conv ? (const float*)(w + wl.dEi) : nullptr, s->outer_conv ? (const float*)(w + wl.dEo) : nullptr,
-                       (const float*)(w + wl.dfb), *tab, t1, Gi, Go, Gfb, c, l2 ? 1 : 0);
+                       cx.at<const unsigned long long>(wl.sort_vals), n_rows, s->M, s->K, s->D, r.dEi, r.dEo, r.dfb, *tab, t1, Gi, Go,
+                       Gfb, c, l2 ? 1 : 0);
     CFFM_CHECK_LAUNCH();
     if (adam || l2) {      // dense sweeps; a disabled branch has no table variable and is left alone
         if (s->inner_conv)

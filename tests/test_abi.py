@@ -105,6 +105,93 @@ def test_data_parallel_updates_refuse_other_optimizers(lib):
     assert lib.cffm_dp_apply(C.byref(s), None, None, None, None, None, 8, None, 0, None, 8, None, 3, None) == 10001
 
 
+def test_entry_points_return_early_before_any_device_work(lib):
+    """The early returns of the per-stage and composite entry points, recorded from the library before their launchers took
+    one step context: which code comes back, and that it comes back before the first HIP call (every device pointer is NULL,
+    so a case that got any further would read through one).  The order matters: a shape is checked before an empty batch is
+    accepted, and an argument the function refuses outright is refused before either where the case says so."""
+    base = dict(M=10, F=3, K=8, D=8, act=0, linear_att=1, inner_conv=1, outer_conv=1, loss=0, lamda_att=1.0, beta_outer=1.0,
+                lr=0.05)
+    good = hip.Shape(optimizer=0, **base)
+    bad = hip.Shape(optimizer=0, **dict(base, F=1))                    # check_shape wants F >= 2
+    N = None
+
+    def batch_calls(p, B):             # the entry points that take (shape, ..., B, ...): name -> arguments
+        return {
+            'cffm_inner_fwd': (p, N, N, B, N), 'cffm_inner_bwd': (p, N, N, B, N),
+            'cffm_outer_conv0_fwd': (p, N, N, B, N), 'cffm_outer_conv0_bwd': (p, N, N, B, N),
+            'cffm_conv_fwd': (p, N, N, B, 1, N), 'cffm_conv_bwd': (p, N, N, B, 1, N),
+            'cffm_head_fwd': (p, N, N, N, B, N), 'cffm_head_bwd': (p, N, N, N, B, 8, N),
+            'cffm_stage_packed': (p, N, N, 4, B, N, N), 'cffm_pack_rows_dedup': (p, N, N, N, B, N, N, N),
+            'cffm_forward': (p, N, N, N, N, B, N, N), 'cffm_predict': (p, N, N, N, B, N, N, N),
+            'cffm_backward': (p, N, N, B, 8, N, N, N), 'cffm_backward_unscaled': (p, N, N, N, B, 8, N, N, N, N),
+            'cffm_dp_local': (p, N, N, N, N, B, 8, N, N, N, N), 'cffm_dp_local_dense': (p, N, N, N, N, B, 8, N, N, N),
+            'cffm_train_step': (p, N, N, N, N, N, N, N, B, N, N, N),
+            'cffm_train_step_opt': (p, N, N, N, N, N, N, N, N, N, B, N, N, 1, N),
+        }
+    for name, args in batch_calls(None, 8).items():                   # NULL shape: check_shape is the first statement
+        assert getattr(lib, name)(*args) == 10001, name
+    for name, args in batch_calls(C.byref(bad), 8).items():           # bad shape: refused by the same first statement
+        assert getattr(lib, name)(*args) == 10001, name
+    for name, args in batch_calls(C.byref(good), 0).items():          # good shape, empty batch: `if (rc || B <= 0) return rc`
+        assert getattr(lib, name)(*args) == 0, name
+
+    g = C.byref(good)
+    sh = lambda **kw: C.byref(hip.Shape(**dict(dict(base, optimizer=0), **kw)))
+    cases = [
+        # layer 0 has an entry point of its own: refused after the shape / batch checks, before the context is built
+        ('cffm_conv_fwd', (g, N, N, 8, 0, N), 10001),
+        ('cffm_conv_bwd', (g, N, N, 8, 0, N), 10001),
+        # a disabled outer branch has no conv layers: `if (B <= 0 || !s->outer_conv) return 0`
+        ('cffm_conv_fwd', (sh(outer_conv=0), N, N, 8, 1, N), 0),
+        ('cffm_inner_fwd', (sh(inner_conv=0), N, N, 8, N), 0),         # ... and a disabled inner branch nothing to run
+        ('cffm_inner_bwd', (sh(inner_conv=0), N, N, 8, N), 0),
+        # D = 1024 would overflow the head's 1024-float t1 row, but it has more conv layers than the ABI's arrays: a bad shape
+        ('cffm_head_fwd', (sh(D=1024), N, N, N, 8, N), 10001),
+        ('cffm_head_bwd', (sh(D=1024), N, N, N, 8, 8, N), 10001),
+        # no workspace slots at all: the NULL shape is seen first, then nothing to sort or apply, then too many rows for B_ws * F
+        ('cffm_reduce_slabs', (N, N, 8, N, N), 10001),
+        ('cffm_reduce_slabs', (C.byref(bad), N, 8, N, N), 10001),
+        ('cffm_sparse_adagrad', (N, N, N, N, 24, N, N, N, N, 8, N), 10001),
+        ('cffm_sparse_adagrad', (C.byref(bad), N, N, N, 24, N, N, N, N, 8, N), 10001),
+        ('cffm_sparse_adagrad', (g, N, N, N, 0, N, N, N, N, 8, N), 0),         # n_rows = 0: the sort and the apply both return 0
+        ('cffm_sparse_adagrad', (g, N, N, N, 25, N, N, N, N, 8, N), 10001),    # n_rows > B_ws * F = 24: refused by the sort
+        ('cffm_sparse_adagrad', (g, N, N, N, 1, N, N, N, N, 0, N), 10001),     # ... also for a workspace of no slots
+        # NULL pointers of a non-empty batch are refused by the pointer check that follows the batch check
+        ('cffm_stage_packed', (g, N, N, 4, 8, N, N), 10001),
+        ('cffm_pack_rows_dedup', (g, N, N, N, 8, N, N, N), 10001),
+        # cffm_gather_inner_fwd checks its pointers right after the shape, whatever B is
+        ('cffm_gather_inner_fwd', (N, N, N, N, 8, N, N), 10001),
+        ('cffm_gather_inner_fwd', (C.byref(bad), N, N, N, 8, N, N), 10001),
+        ('cffm_gather_inner_fwd', (g, N, N, N, 0, N, N), 10001),
+        # packed records: an empty batch returns check_shape(s); pos = NULL is refused before the records are looked at
+        ('cffm_forward_packed', (N, N, N, N, 4, N, 0, N, N), 10001),
+        ('cffm_forward_packed', (g, N, N, N, 4, N, 0, N, N), 0),
+        ('cffm_forward_packed', (g, N, N, N, 4, N, 8, N, N), 10002),
+        ('cffm_backward_unscaled_packed', (g, N, N, N, 4, N, 0, 8, N, N, N), 0),
+        ('cffm_backward_unscaled_packed', (g, N, N, N, 4, N, 8, 8, N, N, N), 10002),
+        # the single-process losses are refused by the first statement of the data-parallel backward, before the batch check
+        ('cffm_backward_unscaled', (sh(loss=5), N, N, N, 8, 8, N, N, N, N), 10002),
+        ('cffm_backward_unscaled', (sh(loss=5), N, N, N, 0, 8, N, N, N, N), 10002),
+        ('cffm_backward_unscaled', (sh(loss=4), N, N, N, 8, 8, N, N, N, N), 10002),
+        ('cffm_backward_unscaled_packed', (sh(loss=5), N, N, N, 4, N, 8, 8, N, N, N), 10002),
+        # y = NULL / a single-process loss: refused right after the context (host arithmetic only) is built
+        ('cffm_dp_local', (g, N, N, N, N, 8, 8, N, N, N, N), 10002),
+        ('cffm_dp_local', (sh(loss=5), N, N, N, N, 8, 8, N, N, N, N), 10002),
+        ('cffm_dp_local', (sh(loss=5), N, N, N, N, 0, 8, N, N, N, N), 0),       # ... but after the empty batch
+        ('cffm_dp_local_dense', (g, N, N, N, N, 8, 8, N, N, N), 10002),
+        # regularised square loss with a disabled branch: refused before the forward
+        ('cffm_train_step', (sh(loss=4, inner_conv=0), N, N, N, N, N, N, N, 8, N, N, N), 10002),
+        ('cffm_train_step_opt', (sh(loss=4, inner_conv=0, optimizer=1), N, N, N, N, N, N, N, N, N, 8, N, N, 1, N), 10002),
+        ('cffm_train_step_opt', (sh(loss=4, inner_conv=0, optimizer=1), N, N, N, N, N, N, N, N, N, 0, N, N, 1, N), 0),
+        # sorted runs: more rows than a workspace of B_ws = 0 examples holds (the context is built with B_ws as it is)
+        ('cffm_dp_apply', (g, N, N, N, N, N, 8, N, 24, N, 0, N, 3, N), 10001),
+        ('cffm_dp_apply', (N, N, N, N, N, N, 8, N, 24, N, 8, N, 0, N), 10001),
+    ]
+    for i, (name, args, want) in enumerate(cases):
+        assert getattr(lib, name)(*args) == want, (i, name)
+
+
 def test_engine_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():
