@@ -217,12 +217,15 @@ static inline int conv_slabs_plain(const cffm_shape_t* s, int32_t B, int l) {
     return (Pp <= 64 && (int64_t)B * S * S >= 256 * 64) ? 256 : CFFM_NSLAB;
 }
 // The layer right below the fused top runs its input and weight gradient as two roles of one launch
-// (conv_bwd_pair_kernel) when its slabs are shorter than 128 rows.
+// (conv_bwd_pair_kernel) when its slabs are shorter than 128 rows.  The one statement of the rule: the slab plan asks it with the
+// plain slab count (conv_pair_ok), the kernel choice of the backward with the count the plan gave the layer (conv_bwd_choice).
+static inline bool conv_pair_slabs_ok(int Pp, int l, int64_t rows, int nslab) {
+    return l >= 1 && Pp <= 64 && (rows + nslab - 1) / nslab < 128;
+}
 static inline bool conv_pair_ok(const cffm_shape_t* s, int32_t B, int l) {
     const int F = s->F, Pp = (F * (F - 1) / 2 + 15) / 16 * 16;
-    const int64_t S = s->D >> (l + 1), rows = (int64_t)B * S * S;
-    const int nslab = conv_slabs_plain(s, B, l);
-    return l >= 1 && Pp <= 64 && (rows + nslab - 1) / nslab < 128;
+    const int64_t S = s->D >> (l + 1);
+    return conv_pair_slabs_ok(Pp, l, (int64_t)B * S * S, conv_slabs_plain(s, B, l));
 }
 // The weight gradients of the fused top's conv layers have few rows (B*4 and B*16 at D = 32): with one slab per example
 // they cost 2 x 256 slabs of 4*Pp*Pp floats (19 MB written and read again at frappe) for 5120 rows of work.  When a pair

@@ -2869,16 +2869,27 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-// The direct layers run for Pp > 64 only, where pick_nt(Pp / 16) returns 6 or 8 (and pick_nt(4 * Pp / 16), the column tiles
-// of the input gradient, returns 8): no other column-tile count is compiled, and meeting one is an error.
-#define DISPATCH_NT68(NTV, CALL)                        \
-    switch (NTV) {                                      \
-        case 6: { constexpr int NT_ = 6; CALL; } break; \
-        case 8: { constexpr int NT_ = 8; CALL; } break; \
-        default: rc = CFFM_ERR_UNSUPPORTED; break;      \
-    }
-
 template <int N> using IntC = std::integral_constant<int, N>;
+#define CV(x) decltype(x)::value
+// Run-time value -> template argument: go(IntC<V>()) for the V of the list that equals v.  Only the listed values are compiled, and
+// meeting another one is an error.
+template <int... Vs, class Go>
+static int with_int(int v, Go&& go) {
+    int rc = CFFM_ERR_UNSUPPORTED;
+    (void)((v == Vs ? (rc = go(IntC<Vs>()), true) : false) || ...);
+    return rc;
+}
+#define NT4 1, 2, 3, 4      // column tiles of the narrow filters (Pp <= 64)
+#define NT68 6, 8           // ... of the direct layers (Pp > 64): what pick_nt(Pp / 16) returns there
+// the lines every launcher ends with: raise the LDS limit of the instance if need be, launch, report a launch error
+template <class... P, class... A>
+static int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    int rc = set_lds(kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    CFFM_CHECK_LAUNCH();
+    return 0;
+}
 
 // ---- dynamic LDS: one function per size, shared by the launcher, the *_ok() predicate and cffm_fwd_all_impl ----------------------
 // Examples whose embedding tile ([F][D+1] floats each) a workgroup of BM rows stages.  Forward kinds (layer-0 forward and weight
@@ -2919,121 +2930,75 @@ static inline bool conv_b3_on() {
     static const bool on = getenv("CFFM_CONV_FP32") == nullptr;
     return on;
 }
-template <int NT, int RM, bool GEN>
+// B3: the bf16x3 K loop (the 128 x 128 instance of layers >= 1 only); the filter changes every step: split it once for this launch
+template <int NT, int RM, bool GEN, bool B3 = false>
 static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
     ConvArgs b = a;
     b.nblk = nblk;
     const int64_t nb1 = 8 * xcd_per((a.Mtot + BM - 1) / BM) * nblk;
-    if (nb1 > 0x7fffffffll) return CFFM_ERR_UNSUPPORTED;
-    if constexpr (NT == 8 && RM == 2 && !GEN) {
-        if (conv_b3_on() && b.wb3 != nullptr) {
-            const size_t lds3 = (size_t)gemm_b3_lds_bytes<NT>() + 16;
-            int rc3 = set_lds(conv_fwd_kernel<NT, RM, GEN, true>, lds3);
-            if (rc3) return rc3;
-            b.wb3_npad = (a.Pp + 127) / 128 * 128;        // the filter changes every step: split it once for this launch
-            if ((rc3 = pack_w_b3<false>(a.W, a.Pp, 4 * a.Pp, a.Pp, b.wb3, st))) return rc3;
-            hipLaunchKernelGGL((conv_fwd_kernel<NT, RM, GEN, true>), dim3((unsigned)nb1), dim3(256), lds3, st, b);
-            CFFM_CHECK_LAUNCH();
-            return 0;
-        }
+    if (nb1 > 0x7fffffffll || (B3 && b.wb3 == nullptr)) return CFFM_ERR_UNSUPPORTED;
+    size_t lds = ((size_t)2 * KSTEP * (NT * 16 + 4) + (GEN ? emb_tile_floats(a.Pp, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) + 4) * 4;
+    if constexpr (B3) {
+        lds = (size_t)gemm_b3_lds_bytes<NT>() + 16;
+        b.wb3_npad = (a.Pp + 127) / 128 * 128;
+        if (int rc = pack_w_b3<false>(a.W, a.Pp, 4 * a.Pp, a.Pp, b.wb3, st)) return rc;
     }
-    const size_t lds = ((size_t)2 * KSTEP * (NT * 16 + 4) + (GEN ? emb_tile_floats(a.Pp, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) + 4) * 4;
-    int rc = set_lds(conv_fwd_kernel<NT, RM, GEN>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv_fwd_kernel<NT, RM, GEN>), dim3((unsigned)nb1), dim3(256), lds, st, b);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv_fwd_kernel<NT, RM, GEN, B3>, dim3((unsigned)nb1), dim3(256), lds, st, b);
 }
 
-template <int NT, int RM, bool L0>
+template <int NT, int RM, bool L0, bool B3 = false>
 static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
     const int rows_per_wg = L0 ? dgrad0_rows_per_wg(BM, a.lgSo) : BM;
     const int n_ex = L0 ? dgrad0_tile_examples(BM, a.lgSo) : 0;
-    const size_t lds = (size_t)(2 * KSTEP * (NT * 16 + 4) + (L0 ? a.Pp + 5 * n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F : 0) + 4) * 4;
+    size_t lds = (size_t)(2 * KSTEP * (NT * 16 + 4) + (L0 ? a.Pp + 5 * n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F : 0) + 4) * 4;
     DgradArgs b = a;
     b.nblk = L0 ? 1 : nblk;
     const int64_t nb1 = 8 * xcd_per((a.Mtot + rows_per_wg - 1) / rows_per_wg) * b.nblk;
-    if (nb1 > 0x7fffffffll) return CFFM_ERR_UNSUPPORTED;
-    if constexpr (NT == 8 && RM == 2 && !L0) {
-        if (conv_b3_on() && b.wb3 != nullptr) {
-            const size_t lds3 = (size_t)gemm_b3_lds_bytes<NT>() + 16;
-            int rc3 = set_lds(dgrad_kernel<NT, RM, L0, true>, lds3);
-            if (rc3) return rc3;
-            b.wb3_npad = (4 * a.Pp + 127) / 128 * 128;
-            if ((rc3 = pack_w_b3<true>(a.W, a.Pp, a.Pp, 4 * a.Pp, b.wb3, st))) return rc3;
-            hipLaunchKernelGGL((dgrad_kernel<NT, RM, L0, true>), dim3((unsigned)nb1), dim3(256), lds3, st, b);
-            CFFM_CHECK_LAUNCH();
-            return 0;
-        }
+    if (nb1 > 0x7fffffffll || (B3 && b.wb3 == nullptr)) return CFFM_ERR_UNSUPPORTED;
+    if constexpr (B3) {
+        lds = (size_t)gemm_b3_lds_bytes<NT>() + 16;
+        b.wb3_npad = (4 * a.Pp + 127) / 128 * 128;
+        if (int rc = pack_w_b3<true>(a.W, a.Pp, a.Pp, 4 * a.Pp, b.wb3, st)) return rc;
     }
-    int rc = set_lds(dgrad_kernel<NT, RM, L0>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dgrad_kernel<NT, RM, L0>), dim3((unsigned)nb1), dim3(256), lds, st, b);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(dgrad_kernel<NT, RM, L0, B3>, dim3((unsigned)nb1), dim3(256), lds, st, b);
 }
 
 template <int NT>
 static int launch_wgrad(const WgradArgs& a, hipStream_t st) {
     constexpr int BI = 64, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16);
     const size_t lds = ((size_t)WG_KM * LDB + emb_tile_floats(a.Pp, fwd_tile_examples(WG_KM, a.lgSo), a.F, a.D) + 4) * 4;
-    int rc = set_lds(wgrad_kernel<NT>, lds);
-    if (rc) return rc;
     WgradArgs b = a;
     b.nslab = CFFM_NSLAB;                                                       // Pp > 64: conv_slabs() == CFFM_NSLAB
     b.nxy = ((4 * a.Pp + BI - 1) / BI) * a.qblocks;
-    dim3 grid((unsigned)(8 * xcd_per(b.nslab) * b.nxy));
-    hipLaunchKernelGGL((wgrad_kernel<NT>), grid, dim3(256), lds, st, b);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(wgrad_kernel<NT>, dim3((unsigned)(8 * xcd_per(b.nslab) * b.nxy)), dim3(256), lds, st, b);
 }
 
-template <int NT>
+// B3: the same tile on the bf16 pipe (wgrad3_kernel: bf16x3 split, fp32 accumulate)
+template <int NT, bool B3>
 static int launch_wgrad2(const WgradArgs& a, hipStream_t st) {
     constexpr int BI = 128, BQ = NT * 16;
     WgradArgs b = a;
     b.nslab = CFFM_NSLAB;                                                       // Pp > 64: conv_slabs() == CFFM_NSLAB
     b.nxy = ((4 * a.Pp + BI - 1) / BI) * a.qblocks;
-    if constexpr (NT == 8) {
-        if (conv_b3_on()) {                                 // the same tile on the bf16 pipe (bf16x3 split, fp32 accumulate)
-            const size_t lds3 = (size_t)3 * 4 * (BI + BQ) * 16 + 16;
-            int rc3 = set_lds(wgrad3_kernel<NT>, lds3);
-            if (rc3) return rc3;
-            hipLaunchKernelGGL((wgrad3_kernel<NT>), dim3((unsigned)(8 * xcd_per(b.nslab) * b.nxy)), dim3(256), lds3, st, b);
-            CFFM_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    const size_t lds = (size_t)(WG_KM * BI + WG_KM * BQ) * 4 + 16;
-    int rc = set_lds(wgrad2_kernel<NT>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((wgrad2_kernel<NT>), dim3((unsigned)(8 * xcd_per(b.nslab) * b.nxy)), dim3(256), lds, st, b);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    const dim3 grid((unsigned)(8 * xcd_per(b.nslab) * b.nxy));
+    if constexpr (B3) return launch(wgrad3_kernel<NT>, grid, dim3(256), (size_t)3 * 4 * (BI + BQ) * 16 + 16, st, b);
+    else return launch(wgrad2_kernel<NT>, grid, dim3(256), (size_t)(WG_KM * BI + WG_KM * BQ) * 4 + 16, st, b);
 }
 
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_taps(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 16 * RM;
     const size_t lds = conv_fwd_taps_scratch(PP, RM) + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
-    int rc = set_lds(conv_fwd_taps_kernel<NT, RM, GEN>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv_fwd_taps_kernel<NT, RM, GEN>), dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv_fwd_taps_kernel<NT, RM, GEN>, dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
 }
 
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_rows(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 64 * RM;
     const size_t lds = (size_t)4 * PP * PP * 4 + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
-    int rc = set_lds(conv_fwd_rows_kernel<NT, RM, GEN>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv_fwd_rows_kernel<NT, RM, GEN>), dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv_fwd_rows_kernel<NT, RM, GEN>, dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
 }
 
 // Layer 0 in factorised form for WIDE filters (Pp > 64, e.g. F = 32: P = 496): the T planes of all channels no longer
@@ -3471,30 +3436,23 @@ __global__ __launch_bounds__(1024) void conv0_fact_tile_wgrad_all_kernel(WgradAr
     }
 }
 
+// ALL: the four groups in one workgroup of 16 wavefronts (F <= 32): the dC tile is staged ONCE per (example, column tile); 4 units
+// per wavefront, 64 accumulation registers - 122 registers and nothing spilled since phase D stopped computing an operand address
+// per MFMA (before: 31-49 spilled, slower than two groups).  Else (F = 33, five groups): one workgroup per group.
+template <bool ALL>
 static int launch_conv0_fact_tile_wgrad(const WgradArgs& a, int nslab, hipStream_t st) {
-    const int S = a.D / 2, G = (2 * a.F + 15) / 16;
-    if (S > 32) return CFFM_ERR_UNSUPPORTED;
-    if (G <= 4) {
-        // all four groups in one workgroup of 16 wavefronts: the dC tile is staged ONCE per (example, column tile); 4 units per
-        // wavefront, 64 accumulation registers - 122 registers and nothing spilled since phase D stopped computing an operand
-        // address per MFMA (before: 31-49 spilled, slower than two groups)
-        const size_t lds = (size_t)(2 * ((a.F * (a.D + 1) + 3) / 4 * 4) + 2 * 32 * 256 + 4 * 16 * 256) * 4 + 16;
-        int rc = set_lds(conv0_fact_tile_wgrad_all_kernel<32, 4>, lds);
-        if (rc) return rc;
-        const int64_t grid = (int64_t)(a.Pp / 16) * nslab;
-        hipLaunchKernelGGL((conv0_fact_tile_wgrad_all_kernel<32, 4>), dim3((unsigned)grid), dim3(1024), lds, st, a, nslab);
-        CFFM_CHECK_LAUNCH();
-        return 0;
+    const int S = a.D / 2, G = (2 * a.F + 15) / 16, es = (a.F * (a.D + 1) + 3) / 4 * 4;
+    if (S > 32 || (ALL && G > 4)) return CFFM_ERR_UNSUPPORTED;
+    if constexpr (ALL) {
+        const size_t lds = (size_t)(2 * es + 2 * 32 * 256 + 4 * 16 * 256) * 4 + 16;
+        const dim3 grid((unsigned)((int64_t)(a.Pp / 16) * nslab));
+        return launch(conv0_fact_tile_wgrad_all_kernel<32, 4>, grid, dim3(1024), lds, st, a, nslab);
+    } else {
+        constexpr int NW = 8;
+        const size_t lds = (size_t)(es + 32 * 256 + 16 * 256) * 4 + 16;
+        const dim3 grid((unsigned)((int64_t)(a.Pp / 16) * G * nslab));
+        return launch(conv0_fact_tile_wgrad_kernel<32, NW>, grid, dim3(64 * NW), lds, st, a, nslab);
     }
-    // G > 4 (F = 33): one workgroup per group
-    const size_t lds = (size_t)((a.F * (a.D + 1) + 3) / 4 * 4 + 32 * 256 + 16 * 256) * 4 + 16;
-    constexpr int NW = 8;
-    int rc = set_lds(conv0_fact_tile_wgrad_kernel<32, NW>, lds);
-    if (rc) return rc;
-    const int64_t grid = (int64_t)(a.Pp / 16) * G * nslab;
-    hipLaunchKernelGGL((conv0_fact_tile_wgrad_kernel<32, NW>), dim3((unsigned)grid), dim3(64 * NW), lds, st, a, nslab);
-    CFFM_CHECK_LAUNCH();
-    return 0;
 }
 
 // Input gradient of layer 0 (dEo) for wide filters in factorised form.  With T and dT as above,
@@ -3832,7 +3790,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv0_fact_tile_dgrad2_kernel(Dgra
 
 static int launch_conv0_fact_tile_dgrad(const DgradArgs& a, float* wpack, hipStream_t st) {
     constexpr int NW = 4;
-    if (wpack == nullptr || a.F > 32 || a.D / 2 > 32) return CFFM_ERR_UNSUPPORTED;   // ws.w0pack exists iff conv0_tile_dgrad2_ok
+    if (wpack == nullptr || a.F > 32 || a.D / 2 > 32) return CFFM_ERR_UNSUPPORTED;   // a guard: ws.w0pack exists iff conv0_tile_dgrad2_ok
     const int QT = a.Pp / 16, CE = (a.F + 3) / 4;
     float* WA = wpack;
     float4* WE = reinterpret_cast<float4*>(wpack + (int64_t)2 * a.F * QT * 1024);
@@ -3840,11 +3798,7 @@ static int launch_conv0_fact_tile_dgrad(const DgradArgs& a, float* wpack, hipStr
     CFFM_CHECK_LAUNCH();
     // Es [4*CE + 1][D+1] | dCt [32][260] | Tg [16][258] | dTg [4096]
     const size_t lds = (size_t)(((4 * CE + 1) * (a.D + 1) + 3) / 4 * 4 + 32 * 260 + 16 * 258 + 4096) * 4 + 16;
-    int rc = set_lds(conv0_fact_tile_dgrad2_kernel<32, NW>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv0_fact_tile_dgrad2_kernel<32, NW>), dim3(a.B), dim3(64 * NW), lds, st, a, (const float*)WA, (const float4*)WE);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv0_fact_tile_dgrad2_kernel<32, NW>, dim3(a.B), dim3(64 * NW), lds, st, a, (const float*)WA, (const float4*)WE);
 }
 
 // Layer-0 forward of the wide shapes, ONE workgroup per example walking the (column tile, channel tile) pairs - the round-2
@@ -4012,6 +3966,7 @@ __global__ __launch_bounds__(64 * NW, 4) void conv0_fact_tile_fwd2_kernel(ConvAr
 
 static int launch_conv0_fact_tile_fwd2(const ConvArgs& a, float* wpack, hipStream_t st) {
     constexpr int NW = 8;
+    if (wpack == nullptr || a.F > 32 || a.D / 2 > 32) return CFFM_ERR_UNSUPPORTED;   // as launch_conv0_fact_tile_dgrad
     const int QT = a.Pp / 16, CE = (a.F + 3) / 4, S = a.D / 2;
     float* WA = wpack;
     float4* WE = reinterpret_cast<float4*>(wpack + (int64_t)2 * a.F * QT * 1024);
@@ -4019,36 +3974,22 @@ static int launch_conv0_fact_tile_fwd2(const ConvArgs& a, float* wpack, hipStrea
     CFFM_CHECK_LAUNCH();
     // T [2*Fp][272] | E2 [2][Fp + 1][S + 1] | PS [NW][S]
     const size_t lds = (size_t)(8 * CE * (16 * 16 + 16) + (2 * (4 * CE + 1) * (S + 1) + 3) / 4 * 4 + NW * S) * 4 + 16;
-    int rc = set_lds(conv0_fact_tile_fwd2_kernel<NW>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv0_fact_tile_fwd2_kernel<NW>), dim3(a.B), dim3(64 * NW), lds, st, a, (const float*)WA);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv0_fact_tile_fwd2_kernel<NW>, dim3(a.B), dim3(64 * NW), lds, st, a, (const float*)WA);
 }
 
-static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st, float* wpack = nullptr) {
-    if (wpack != nullptr && a.F <= 32 && a.D / 2 <= 32) return launch_conv0_fact_tile_fwd2(a, wpack, st);
-
+// the round-2 kernel: shapes without the packed filter (D >= 128)
+static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st) {
     constexpr int NW = 8;                // measured at F32 D64 B8192: 38.6 ms with 4 wavefronts, 29.2 with 8, 36.6 with 16 (one workgroup per CU)
     const int S = a.D / 2;
     const size_t lds = (size_t)(2 * a.F * (16 * 16 + 16) + a.F * (a.D + 1) + NW * S) * 4 + 16;
-    int rc = set_lds(conv0_fact_tile_fwd_kernel<NW>, lds);
-    if (rc) return rc;
     const int64_t grid = (int64_t)a.B * (a.Pp / 16) * (S / 16);
     if (grid > 0x7fffffffll) return CFFM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((conv0_fact_tile_fwd_kernel<NW>), dim3((unsigned)grid), dim3(64 * NW), lds, st, a);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv0_fact_tile_fwd_kernel<NW>, dim3((unsigned)grid), dim3(64 * NW), lds, st, a);
 }
 
 template <int NT>
 static int launch_conv0_fact_fwd(const ConvArgs& a, hipStream_t st) {
-    const size_t lds = conv0_fact_fwd_lds(NT * 16, a.F, a.D);
-    int rc = set_lds(conv0_fact_fwd_kernel<NT>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((conv0_fact_fwd_kernel<NT>), dim3(a.B), dim3(256), lds, st, a);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(conv0_fact_fwd_kernel<NT>, dim3(a.B), dim3(256), conv0_fact_fwd_lds(NT * 16, a.F, a.D), st, a);
 }
 
 // the factorised layer-0 kernels keep the filter, the embedding tile and T[2F][S][Pp] of one example in LDS
@@ -4075,12 +4016,7 @@ static int launch_conv0_fact_bwd(const DgradArgs& a, float* slabW, float* slabB,
     constexpr int NW = 16;
     const size_t lds = conv0_fact_bwd_lds(PP, a.F, a.D);
     auto go = [&](auto fv, auto dv) {          // (F, D) compiled in for the README shapes, (0, 0): read at run time
-        constexpr int FV = decltype(fv)::value, DV = decltype(dv)::value;
-        int rc = set_lds(conv0_fact_bwd_kernel<NT, FV, DV, NW>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((conv0_fact_bwd_kernel<NT, FV, DV, NW>), dim3(nsl), dim3(64 * NW), lds, st, a, slabW, slabB, stride);
-        CFFM_CHECK_LAUNCH();
-        return 0;
+        return launch(conv0_fact_bwd_kernel<NT, CV(fv), CV(dv), NW>, dim3(nsl), dim3(64 * NW), lds, st, a, slabW, slabB, stride);
     };
     if constexpr (NT == 3) {
         if (a.F == 10 && a.D == 32) return go(IntC<10>(), IntC<32>());     // frappe        (README.md:28)
@@ -4100,40 +4036,18 @@ static int launch_dgrad_taps(const DgradArgs& a, hipStream_t st) {
     const bool fast = L0 && RM == 4 && a.lgSo >= 4 && a.lgSo <= 6;
     const size_t scratch = fast ? (size_t)(4 + 4 * HALVES) * PP * So : (size_t)4 * HALVES * n_ex * a.F * (a.D + 1);
     const size_t lds = (L0 ? (size_t)PP + n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F + scratch : 0) * 4 + 16;
-    int rc = set_lds(dgrad_taps_kernel<NT, RM, L0, HALVES>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((dgrad_taps_kernel<NT, RM, L0, HALVES>), dim3((unsigned)((a.Mtot + rows_per_wg - 1) / rows_per_wg)),
-                       dim3(256 * HALVES), lds, st, a);
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    return launch(dgrad_taps_kernel<NT, RM, L0, HALVES>, dim3((unsigned)((a.Mtot + rows_per_wg - 1) / rows_per_wg)), dim3(256 * HALVES),
+                  lds, st, a);
 }
 
-#define DISPATCH_NT4(NTV, CALL)                    \
-    switch (NTV) {                                 \
-        case 1: { constexpr int NT_ = 1; CALL; } break; \
-        case 2: { constexpr int NT_ = 2; CALL; } break; \
-        case 3: { constexpr int NT_ = 3; CALL; } break; \
-        default: { constexpr int NT_ = 4; CALL; } break; \
-    }
-
-template <int NT, bool GEN>
+// HALVES = 2: the cross-half reduction of the [4][NT][NT] tiles and of the bias on top
+template <int NT, bool GEN, int HALVES>
 static int launch_wgrad_taps(const WgradArgs& a, int nsl, hipStream_t st) {
-    const int64_t rows_per_slab = (a.Mtot + nsl - 1) / nsl;
     const int S2 = 1 << (2 * a.lgSo);
     const int n_ex_max = GEN ? WGT_SUB / S2 + 2 : 0;
     const size_t base = (size_t)(WGT_SUB * NT * 16 + (GEN ? NT * 16 + (n_ex_max * a.F * (a.D + 1) + 7) / 4 * 4 : 0)) * 4 + 16;
-    if (rows_per_slab >= 128) {      // enough rows to give two wavefronts per SIMD something to do
-        const size_t lds = base + (size_t)4 * NT * NT * 64 * 16 + (size_t)NT * 64 * 4;
-        int rc = set_lds(wgrad_taps_kernel<NT, GEN, 2>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((wgrad_taps_kernel<NT, GEN, 2>), dim3(nsl), dim3(512), lds, st, a);
-    } else {
-        int rc = set_lds(wgrad_taps_kernel<NT, GEN, 1>, base);
-        if (rc) return rc;
-        hipLaunchKernelGGL((wgrad_taps_kernel<NT, GEN, 1>), dim3(nsl), dim3(256), base, st, a);
-    }
-    CFFM_CHECK_LAUNCH();
-    return 0;
+    const size_t lds = base + (HALVES == 2 ? (size_t)4 * NT * NT * 64 * 16 + (size_t)NT * 64 * 4 : 0);
+    return launch(wgrad_taps_kernel<NT, GEN, HALVES>, dim3(nsl), dim3(256 * HALVES), lds, st, a);
 }
 
 template <int NT, int RM>
@@ -4156,13 +4070,8 @@ static int launch_conv_bwd_pair(const DgradArgs& d, const WgradArgs& w, int nsl,
     const int xcd_align = (nsl == d.B && (int64_t)nsl * S2 == d.Mtot && S2 % BM == 0 && d.B % 8 == 0 && first_w % 8 == 0 &&
                            first_d % 8 == 0) ? 1 : 0;
     return with_readme_act<NT>(d.act, [&](auto act) {
-        constexpr int ACT = decltype(act)::value;
-        int rc = set_lds(conv_bwd_pair_kernel<NT, RM, ACT>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((conv_bwd_pair_kernel<NT, RM, ACT>), dim3(n_d + nsl + (ib ? n_i : 0) + tw.n[0] + tw.n[1]), dim3(256),
-                           lds, st, d, w, n_d, nsl, ib ? *ib : none, ib ? n_i : 0, tw, xcd_align);
-        CFFM_CHECK_LAUNCH();
-        return 0;
+        return launch(conv_bwd_pair_kernel<NT, RM, CV(act)>, dim3(n_d + nsl + (ib ? n_i : 0) + tw.n[0] + tw.n[1]), dim3(256), lds, st, d, w,
+                      n_d, nsl, ib ? *ib : none, ib ? n_i : 0, tw, xcd_align);
     });
 }
 
@@ -4228,51 +4137,101 @@ DgradArgs StepCtx::dgrad_args(int l) const {
     return a;
 }
 
+// ---- which kernel instance runs layer l of shape g at batch B: decided HERE, once per direction, as a value ---------------------
+// (cffm_kernel_choice_t, include/cffm_hip.h).  cffm_conv_fwd_impl / cffm_conv_bwd_impl switch on it and the launchers choose nothing;
+// cffm_conv_choice hands the same value to the tests.  b3_on: the latch conv_b3_on().
+using KC = cffm_kernel_choice_t;
+static const KC KC_UNSUPPORTED = {CFFM_CHOICE_UNSUPPORTED, 0, 0, 0, 0};
+static KC conv_fwd_choice(const Geo& g, int B, int l, bool b3_on) {
+    int lgSo, nblk, NT;
+    const int64_t Mtot = layer_rows(g, B, l, &lgSo), wg16 = (Mtot + 15) / 16;
+    if (g.Pp <= 64) {                        // tap-split path: no K loop
+        const int nt4 = g.Pp / 16;
+        if (l == 0 && conv0_fact_ok(g)) return {CFFM_FWD_FACT, nt4, 0, 0, 0};   // rank-1 input channels: factorised, a workgroup per example
+        if (wg16 >= 4 * 512) return {CFFM_FWD_ROWS, nt4, 1, 0, 0};              // many rows: whole filter in LDS, a wave runs all four taps
+        return {CFFM_FWD_TAPS, nt4, wg16 >= 2 * 512 ? 2 : 1, 0, 0};             // one wave per filter tap
+    }
+    // rank-1 input channels: factorised, channel-tiled (its step 1 indexes k over ALL fields: 2 * ceil4(F) <= 64 k values)
+    if (l == 0 && conv0_tile_fwd_ok(g)) return {conv0_tile_dgrad2_ok(g) ? CFFM_FWD_TILE_PACKED : CFFM_FWD_TILE, 0, 0, 0, 0};
+    pick_nt(g.Pp / 16, &nblk, &NT);
+    if (NT != 6 && NT != 8) return KC_UNSUPPORTED;
+    const int RM = Mtot >= 128 * 256 ? 2 : 1;
+    return {CFFM_FWD_DIRECT, NT, RM, 0, NT == 8 && RM == 2 && l >= 1 && b3_on};
+}
+struct ConvBwdChoice { KC wgrad, dgrad; bool paired; };
+static ConvBwdChoice conv_bwd_choice(const Geo& g, int B, int l, int nslab, bool b3_on) {
+    int lgSo, nblk, NT;
+    const int64_t Mtot = layer_rows(g, B, l, &lgSo), wg16 = (Mtot + 15) / 16;
+    if (g.Pp <= 64) {
+        const int nt4 = g.Pp / 16, RM = wg16 >= 2 * 512 ? 2 : 1;
+        // factorised layer 0: weight, bias and input gradient in one kernel
+        if (l == 0 && conv0_fact_bwd_ok(g)) return {{CFFM_WGRAD_FACT_BWD, nt4, 0, 0, 0}, {CFFM_DGRAD_NONE, 0, 0, 0, 0}, false};
+        // slabs for the 256-thread weight-gradient variant: pair it up with the input gradient
+        if (conv_pair_slabs_ok(g.Pp, l, Mtot, nslab)) return {{CFFM_WGRAD_TAPS, nt4, 0, 1, 0}, {CFFM_DGRAD_TAPS, nt4, RM, 1, 0}, true};
+        // 128 rows per slab: enough to give two wavefronts per SIMD something to do; layer 0, S2 >= 128: >= 2 m tiles
+        const KC w = {CFFM_WGRAD_TAPS, nt4, 0, (Mtot + nslab - 1) / nslab >= 128 ? 2 : 1, 0};
+        if (l == 0) return {w, {CFFM_DGRAD_TAPS, nt4, 4, (1 << (2 * lgSo)) >= 128 ? 2 : 1, 0}, false};
+        return {w, {CFFM_DGRAD_TAPS, nt4, RM, 1, 0}, false};
+    }
+    ConvBwdChoice c = {KC_UNSUPPORTED, KC_UNSUPPORTED, false};
+    pick_nt(g.Pp / 16, &nblk, &NT);
+    if (l == 0 && conv0_tile_wgrad_ok(g)) c.wgrad = {(2 * g.F + 15) / 16 <= 4 ? CFFM_WGRAD_TILE_ALL : CFFM_WGRAD_TILE_GROUP, 0, 0, 0, 0};
+    else if (NT != 6 && NT != 8) return c;
+    else if (l == 0) c.wgrad = {CFFM_WGRAD_DIRECT0, NT, 0, 0, 0};
+    else if (NT == 8 && b3_on) c.wgrad = {CFFM_WGRAD_WGRAD3, 8, 0, 0, 1};        // 128 x 128 output tile per workgroup, on the bf16 pipe
+    else c.wgrad = {CFFM_WGRAD_WGRAD2, NT, 0, 0, 0};                              // 128 x 128 or 128 x 96
+    if (l == 0 && conv0_tile_dgrad2_ok(g)) { c.dgrad = {CFFM_DGRAD_TILE_PACKED, 0, 0, 0, 0}; return c; }
+    pick_nt(4 * g.Pp / 16, &nblk, &NT);
+    if (NT != 8) return c;                                                         // the only column-tile count compiled
+    const int RM = Mtot >= 128 * 256 ? 2 : 1;
+    c.dgrad = {CFFM_DGRAD_DIRECT, 8, RM, 0, RM == 2 && l >= 1 && b3_on};
+    return c;
+}
+
+extern "C" int cffm_conv_choice(const cffm_shape_t* s, int32_t B, int32_t layer, cffm_conv_choice_t* out) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    const Geo g = make_geo(s);
+    if (B < 1 || layer < 0 || layer >= g.live || !out) return CFFM_ERR_BAD_SHAPE;
+    const ConvBwdChoice b = conv_bwd_choice(g, B, layer, conv_slabs(s, B, layer), conv_b3_on());
+    *out = {conv_fwd_choice(g, B, layer, conv_b3_on()), b.wgrad, b.dgrad, b.paired, top_wgrad_deferred(s, B)};
+    return 0;
+}
+
+// forward of layer l: argument block, choice (conv_fwd_choice), one switch that instantiates and launches
 int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs) {
     const Geo& g = c.g;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
     ConvArgs a = c.conv_args(l);
+    const KC k = conv_fwd_choice(g, c.B, l, conv_b3_on());
+    const bool tiled = k.family == CFFM_FWD_TILE || k.family == CFFM_FWD_TILE_PACKED;
+    if (rs && !tiled) return CFFM_ERR_UNSUPPORTED;                  // cffm_wide_regather_ok() guards the callers
+    if (tiled) take_rows(a, &ConvArgs::in, rs);
     int nblk, NT;
-    int rc = 0;
-    if (g.Pp <= 64) {                       // tap-split path: one wave per filter tap, no K loop
-        const int nt4 = g.Pp / 16;
-        const int64_t wg16 = (a.Mtot + 15) / 16;
-        if (l == 0 && conv0_fact_ok(g)) {        // rank-1 input channels: factorised contraction, one workgroup per example
-            DISPATCH_NT4(nt4, rc = (launch_conv0_fact_fwd<NT_>(a, st)));
-            return rc;
-        }
-        if (wg16 >= 4 * 512) {                    // many rows: whole filter in LDS, a wave runs all four taps
-            if (l == 0) { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_rows<NT_, 1, true>(a, st))); }
-            else { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_rows<NT_, 1, false>(a, st))); }
-            return rc;
-        }
-        if (l == 0) {
-            if (wg16 >= 4 * 1024) { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 4, true>(a, st))); }
-            else if (wg16 >= 2 * 512) { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 2, true>(a, st))); }
-            else { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 1, true>(a, st))); }
-        } else {
-            if (wg16 >= 4 * 1024) { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 4, false>(a, st))); }
-            else if (wg16 >= 2 * 512) { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 2, false>(a, st))); }
-            else { DISPATCH_NT4(nt4, rc = (launch_conv_fwd_taps<NT_, 1, false>(a, st))); }
-        }
-        return rc;
-    }
-    // rank-1 input channels: factorised, channel-tiled (its step 1 indexes k over ALL fields: 2 * ceil4(F) <= 64 k values)
-    if (l == 0 && conv0_tile_fwd_ok(g)) {
-        take_rows(a, &ConvArgs::in, rs);
-        return launch_conv0_fact_tile_fwd(a, st, c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr);
-    }
-    if (l == 0 && rs) return CFFM_ERR_UNSUPPORTED;                  // cffm_wide_regather_ok() guards the callers
     pick_nt(g.Pp / 16, &nblk, &NT);
-    const bool big = a.Mtot >= 128 * 256;
-    if (l == 0) {
-        if (big) { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 2, true>(a, nblk, st))); }
-        else { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 1, true>(a, nblk, st))); }
-    } else {
-        if (big) { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 2, false>(a, nblk, st))); }
-        else { DISPATCH_NT68(NT, rc = (launch_conv_fwd<NT_, 1, false>(a, nblk, st))); }
+    switch (k.family) {
+        case CFFM_FWD_FACT: return with_int<NT4>(k.NT, [&](auto nt) { return launch_conv0_fact_fwd<CV(nt)>(a, st); });
+        case CFFM_FWD_ROWS:
+            return with_int<NT4>(k.NT, [&](auto nt) {
+                return with_int<0, 1>(l == 0, [&](auto gen) { return launch_conv_fwd_rows<CV(nt), 1, CV(gen)>(a, st); });
+            });
+        case CFFM_FWD_TAPS:
+            return with_int<NT4>(k.NT, [&](auto nt) {
+                return with_int<1, 2>(k.RM, [&](auto rm) {
+                    return with_int<0, 1>(l == 0, [&](auto gen) { return launch_conv_fwd_taps<CV(nt), CV(rm), CV(gen)>(a, st); });
+                });
+            });
+        case CFFM_FWD_TILE: return launch_conv0_fact_tile_fwd(a, st);
+        case CFFM_FWD_TILE_PACKED: return launch_conv0_fact_tile_fwd2(a, c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr, st);
+        case CFFM_FWD_DIRECT:
+            if (k.b3) return launch_conv_fwd<8, 2, false, true>(a, nblk, st);
+            return with_int<NT68>(k.NT, [&](auto nt) {
+                return with_int<1, 2>(k.RM, [&](auto rm) {
+                    return with_int<0, 1>(l == 0, [&](auto gen) { return launch_conv_fwd<CV(nt), CV(rm), CV(gen)>(a, nblk, st); });
+                });
+            });
+        default: return CFFM_ERR_UNSUPPORTED;
     }
-    return rc;
 }
 
 template <int NT>
@@ -4313,101 +4272,87 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
     }
     size_t lds = (size_t)(WGT_SUB * g.Pp) * 4 + 16;
     if (inner_bwd_lds(g) > lds) lds = inner_bwd_lds(g);
-    int rc = 0;
-    DISPATCH_NT4(g.Pp / 16, rc = (launch_bwd_top<NT_>(a, lds, st)));
     *next_layer = first - 1;
-    return rc;
+    return with_int<NT4>(g.Pp / 16, [&](auto nt) { return launch_bwd_top<CV(nt)>(a, lds, st); });
 }
 
-// weight / bias gradient and input gradient of layer l: one launch where a fused or paired kernel exists, else one each
+// weight / bias gradient and input gradient of layer l: one launch where a fused or paired kernel exists, else one each.
+// Argument blocks, choice (conv_bwd_choice, with the slab count the plan gave the layer), one switch per role.
 int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o) {
-    const cffm_shape_t* s = c.s;
     const Geo& g = c.g;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
     const SlabRange& sr = c.conv_slab(l);
-    const RowSrc* rs = o.rs;
-    float* w0pack = c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr;
-    int rc = 0;
-    if (l == 0 && conv0_fact_bwd_ok(g)) {   // factorised layer 0: weight, bias and input gradient in one kernel
-        const DgradArgs a = c.dgrad_args(0);
-        const WgradArgs wa = c.wgrad_args(0);
-        DISPATCH_NT4(g.Pp / 16, rc = (launch_conv0_fact_bwd<NT_>(a, wa.slabW, wa.slabB, sr.len, sr.nslab, st)));
+    const int nsl = sr.nslab;
+    WgradArgs wa = c.wgrad_args(l);
+    DgradArgs da = c.dgrad_args(l);
+    const ConvBwdChoice k = conv_bwd_choice(g, c.B, l, nsl, conv_b3_on());
+    const KC &kw = k.wgrad, &kd = k.dgrad;
+    if (kw.family == CFFM_CHOICE_UNSUPPORTED || kd.family == CFFM_CHOICE_UNSUPPORTED) return CFFM_ERR_UNSUPPORTED;
+    // the fused top left its weight gradients to a pair launch (top_wgrad_deferred): no other launch computes them
+    if (o.with_top_wgrad && !k.paired) return CFFM_ERR_UNSUPPORTED;
+    const bool tiled_w = kw.family == CFFM_WGRAD_TILE_ALL || kw.family == CFFM_WGRAD_TILE_GROUP;
+    // rows straight from the table: the tiled layer 0 only (cffm_wide_regather_ok() guards the callers)
+    if (o.rs && !(tiled_w && kd.family == CFFM_DGRAD_TILE_PACKED)) return CFFM_ERR_UNSUPPORTED;
+    if (k.paired) {
+        InnerBwdArgs ib{};
+        int n_i = 0;
+        const bool inner = o.carry_inner != nullptr && c.s->inner_conv;
+        if (inner) ib = c.inner_bwd_args(&n_i);
+        TopWgrad tw;
+        memset(&tw, 0, sizeof(tw));
+        int n_top = 0;
+        for (int lt = g.live - 1; o.with_top_wgrad && lt > l && n_top < 2; --lt, ++n_top) {
+            tw.w[n_top] = c.wgrad_args(lt);
+            tw.n[n_top] = c.conv_slab(lt).nslab;
+        }
+        const int rc = with_int<NT4>(kd.NT, [&](auto nt) {
+            return with_int<1, 2>(kd.RM, [&](auto rm) {
+                return launch_conv_bwd_pair<CV(nt), CV(rm)>(da, wa, nsl, inner ? &ib : nullptr, n_i, st, o.with_top_wgrad ? &tw : nullptr);
+            });
+        });
+        if (inner && !rc) *o.carry_inner = true;
         return rc;
     }
-    if (l >= 1 && g.Pp <= 64) {
-        const WgradArgs wa = c.wgrad_args(l);
-        if ((wa.Mtot + sr.nslab - 1) / sr.nslab < 128) {          // the 256-thread weight-gradient variant: pair it up
-            const DgradArgs da = c.dgrad_args(l);
-            const int64_t wg16 = (wa.Mtot + 15) / 16;
-            InnerBwdArgs ib{};
-            int n_i = 0;
-            const bool inner = o.carry_inner != nullptr && s->inner_conv;
-            if (inner) ib = c.inner_bwd_args(&n_i);
-            TopWgrad tw;
-            memset(&tw, 0, sizeof(tw));
-            if (o.with_top_wgrad) {                             // the fused top left its weight gradients to this launch
-                int k = 0;
-                for (int lt = g.live - 1; lt > l && k < 2; --lt, ++k) {
-                    tw.w[k] = c.wgrad_args(lt);
-                    tw.n[k] = c.conv_slab(lt).nslab;
-                }
-            }
-            const TopWgrad* twp = o.with_top_wgrad ? &tw : nullptr;
-            if (wg16 >= 2 * 512) { DISPATCH_NT4(g.Pp / 16, rc = (launch_conv_bwd_pair<NT_, 2>(da, wa, sr.nslab, inner ? &ib : nullptr, n_i, st, twp))); }
-            else { DISPATCH_NT4(g.Pp / 16, rc = (launch_conv_bwd_pair<NT_, 1>(da, wa, sr.nslab, inner ? &ib : nullptr, n_i, st, twp))); }
-            if (inner && !rc) *o.carry_inner = true;
-            return rc;
-        }
+    int rc = 0;
+    switch (kw.family) {
+        case CFFM_WGRAD_FACT_BWD:
+            return with_int<NT4>(kw.NT, [&](auto nt) { return launch_conv0_fact_bwd<CV(nt)>(da, wa.slabW, wa.slabB, sr.len, nsl, st); });
+        case CFFM_WGRAD_TAPS:
+            rc = with_int<NT4>(kw.NT, [&](auto nt) {
+                return with_int<1, 2>(kw.HALVES, [&](auto h) {
+                    return with_int<0, 1>(l == 0, [&](auto gen) { return launch_wgrad_taps<CV(nt), CV(gen), CV(h)>(wa, nsl, st); });
+                });
+            });
+            break;
+        case CFFM_WGRAD_TILE_ALL: take_rows(wa, &WgradArgs::in, o.rs); rc = launch_conv0_fact_tile_wgrad<true>(wa, nsl, st); break;
+        case CFFM_WGRAD_TILE_GROUP: take_rows(wa, &WgradArgs::in, o.rs); rc = launch_conv0_fact_tile_wgrad<false>(wa, nsl, st); break;
+        case CFFM_WGRAD_DIRECT0: rc = with_int<NT68>(kw.NT, [&](auto nt) { return launch_wgrad<CV(nt)>(wa, st); }); break;
+        case CFFM_WGRAD_WGRAD2: rc = with_int<NT68>(kw.NT, [&](auto nt) { return launch_wgrad2<CV(nt), false>(wa, st); }); break;
+        case CFFM_WGRAD_WGRAD3: rc = launch_wgrad2<8, true>(wa, st); break;
+        default: return CFFM_ERR_UNSUPPORTED;
     }
-    {   // weight / bias gradient
-        WgradArgs a = c.wgrad_args(l);
-        if (g.Pp <= 64) {
-            const int nt4 = g.Pp / 16;
-            const int nsl = sr.nslab;
-            if (l == 0) { DISPATCH_NT4(nt4, rc = (launch_wgrad_taps<NT_, true>(a, nsl, st))); }
-            else { DISPATCH_NT4(nt4, rc = (launch_wgrad_taps<NT_, false>(a, nsl, st))); }
-        } else {
-            int nblk, NT;
-            pick_nt(g.Pp / 16, &nblk, &NT);                 // (nblk is a.qblocks)
-            if (l == 0 && conv0_tile_wgrad_ok(g)) {
-                take_rows(a, &WgradArgs::in, rs);
-                rc = launch_conv0_fact_tile_wgrad(a, sr.nslab, st);
-            }
-            else if (l == 0 && rs) { rc = CFFM_ERR_UNSUPPORTED; }
-            else if (l == 0) { DISPATCH_NT68(NT, rc = (launch_wgrad<NT_>(a, st))); }
-            else if (NT == 8) { rc = launch_wgrad2<8>(a, st); }               // 128 x 128 output tile per workgroup
-            else if (NT == 6) { rc = launch_wgrad2<6>(a, st); }               // 128 x 96
-            else { rc = CFFM_ERR_UNSUPPORTED; }
-        }
-        if (rc) return rc;
+    if (rc) return rc;
+    int nblk, NT;
+    pick_nt(4 * g.Pp / 16, &nblk, &NT);
+    switch (kd.family) {
+        case CFFM_DGRAD_TAPS:
+            if (l == 0)
+                return with_int<NT4>(kd.NT, [&](auto nt) {
+                    return with_int<1, 2>(kd.HALVES, [&](auto h) { return launch_dgrad_taps<CV(nt), 4, true, CV(h)>(da, st); });
+                });
+            return with_int<NT4>(kd.NT, [&](auto nt) {
+                return with_int<1, 2>(kd.RM, [&](auto rm) { return launch_dgrad_taps<CV(nt), CV(rm), false, 1>(da, st); });
+            });
+        case CFFM_DGRAD_TILE_PACKED:
+            take_rows(da, &DgradArgs::Cprev, o.rs);
+            return launch_conv0_fact_tile_dgrad(da, c.wl.w0pack_floats > 0 ? c.at(c.wl.w0pack) : nullptr, st);
+        case CFFM_DGRAD_DIRECT:
+            if (kd.b3) return launch_dgrad<8, 2, false, true>(da, nblk, st);
+            return with_int<1, 2>(kd.RM, [&](auto rm) {
+                return with_int<0, 1>(l == 0, [&](auto l0) { return launch_dgrad<8, CV(rm), CV(l0)>(da, nblk, st); });
+            });
+        default: return CFFM_ERR_UNSUPPORTED;
     }
-    {   // input gradient
-        DgradArgs a = c.dgrad_args(l);
-        int nblk, NT;
-        if (g.Pp <= 64) {
-            const int nt4 = g.Pp / 16;
-            const int64_t wg16 = (a.Mtot + 15) / 16;
-            if (l == 0) {
-                const int S2 = 1 << (2 * a.lgSo);
-                if (S2 >= 128) { DISPATCH_NT4(nt4, rc = (launch_dgrad_taps<NT_, 4, true, 2>(a, st))); }   // >= 2 m tiles
-                else { DISPATCH_NT4(nt4, rc = (launch_dgrad_taps<NT_, 4, true, 1>(a, st))); }
-            }
-            else if (wg16 >= 2 * 512) { DISPATCH_NT4(nt4, rc = (launch_dgrad_taps<NT_, 2, false, 1>(a, st))); }
-            else { DISPATCH_NT4(nt4, rc = (launch_dgrad_taps<NT_, 1, false, 1>(a, st))); }
-            return rc;
-        }
-        if (l == 0 && conv0_tile_dgrad2_ok(g)) {
-            take_rows(a, &DgradArgs::Cprev, rs);
-            return launch_conv0_fact_tile_dgrad(a, w0pack, st);
-        }
-        if (l == 0 && rs) return CFFM_ERR_UNSUPPORTED;
-        pick_nt(4 * g.Pp / 16, &nblk, &NT);
-        if (NT != 8) return CFFM_ERR_UNSUPPORTED;                    // see DISPATCH_NT68
-        const bool big = a.Mtot >= 128 * 256;
-        if (l == 0) rc = big ? launch_dgrad<8, 2, true>(a, nblk, st) : launch_dgrad<8, 1, true>(a, nblk, st);
-        else rc = big ? launch_dgrad<8, 2, false>(a, nblk, st) : launch_dgrad<8, 1, false>(a, nblk, st);
-    }
-    return rc;
 }
 
 // The exported per-stage entry points: each builds a context of its own.
@@ -4558,7 +4503,5 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
         fa.early_off = (need <= t_bytes && ids != nullptr) ? (int)t_off : 0;
         fa.es_off = (int)(t_off + t_bytes);
     }
-    int rc = 0;
-    DISPATCH_NT4(PP / 16, rc = (launch_fwd_all<NT_>(fa, lds, st)));
-    return rc;
+    return with_int<NT4>(PP / 16, [&](auto nt) { return launch_fwd_all<CV(nt)>(fa, lds, st); });
 }

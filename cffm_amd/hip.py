@@ -57,6 +57,15 @@ class WsLayout(C.Structure):
                 ('wb3', C.c_int64), ('wb3_bytes', C.c_int64)]
 
 
+class KernelChoice(C.Structure):
+    _fields_ = [('family', C.c_int32), ('NT', C.c_int32), ('RM', C.c_int32), ('HALVES', C.c_int32), ('b3', C.c_int32)]
+
+
+class ConvChoice(C.Structure):
+    _fields_ = [('fwd', KernelChoice), ('wgrad', KernelChoice), ('dgrad', KernelChoice), ('paired', C.c_int32),
+                ('top_wgrad_deferred', C.c_int32)]
+
+
 class Tables(C.Structure):
     _fields_ = [('inner_emb', C.c_void_p), ('outer_emb', C.c_void_p), ('feat_bias', C.c_void_p)]
 
@@ -71,6 +80,7 @@ PROTOTYPES = {
     'cffm_error_string': (C.c_char_p, [C.c_int]),
     'cffm_theta_layout': (C.c_int, [_SH, _P]),
     'cffm_ws_layout': (C.c_int, [_SH, C.c_int32, _P]),
+    'cffm_conv_choice': (C.c_int, [_SH, C.c_int32, C.c_int32, _P]),
     'cffm_gather': (C.c_int, [_SH, _TB, _P, C.c_int32, _P, _P, _P, _P]),
     'cffm_gather_inner_fwd_ok': (C.c_int, [_SH]),
     'cffm_gather_inner_fwd': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, _P, _P]),
@@ -200,4 +210,12 @@ def ws_layout(shape, B):
     wl = WsLayout()
     check(load().cffm_ws_layout(C.byref(shape), int(B), C.byref(wl)))
     return wl
+
+
+
+def conv_choice(shape, B, layer):
+    """The kernel instances of conv layer `layer` at batch B (cffm_conv_choice, include/cffm_hip.h)."""
+    ch = ConvChoice()
+    check(load().cffm_conv_choice(C.byref(shape), int(B), int(layer), C.byref(ch)))
+    return ch
 

@@ -124,11 +124,49 @@ typedef struct cffm_tables {                /* the three gathered variables and 
     float *feat_bias;                       /* [M]    feature_bias      CFFM.py:276                */
 } cffm_tables_t;
 
+/* Which kernel instance runs one role of a conv layer.  family: one of the values below, by role; a member the family's kernel
+ * does not have as a template argument is 0. */
+#define CFFM_CHOICE_UNSUPPORTED (-1)  /* any role: no kernel is compiled for it, the stage returns CFFM_ERR_UNSUPPORTED          */
+#define CFFM_FWD_FACT 1               /* conv0_fact_fwd_kernel<NT>: factorised layer 0 of the narrow filters (Pp <= 64)           */
+#define CFFM_FWD_ROWS 2               /* conv_fwd_rows_kernel<NT, RM>: narrow, whole filter in LDS                                 */
+#define CFFM_FWD_TAPS 3               /* conv_fwd_taps_kernel<NT, RM>: narrow, one wavefront per filter tap                        */
+#define CFFM_FWD_TILE 4               /* conv0_fact_tile_fwd_kernel: tiled factorised layer 0 of the wide filters                  */
+#define CFFM_FWD_TILE_PACKED 5        /* conv0_fact_tile_fwd2_kernel: the same on the packed filter (ws.w0pack)                    */
+#define CFFM_FWD_DIRECT 6             /* conv_fwd_kernel<NT, RM>: implicit GEMM of the wide filters                                */
+#define CFFM_WGRAD_FACT_BWD 1         /* conv0_fact_bwd_kernel<NT>: narrow layer 0, weight, bias AND input gradient (dgrad: NONE)  */
+#define CFFM_WGRAD_TAPS 2             /* wgrad_taps_kernel<NT, HALVES>; paired: the weight-gradient role of conv_bwd_pair_kernel   */
+#define CFFM_WGRAD_TILE_ALL 3         /* conv0_fact_tile_wgrad_all_kernel: tiled layer 0, all groups in one workgroup              */
+#define CFFM_WGRAD_TILE_GROUP 4       /* conv0_fact_tile_wgrad_kernel: tiled layer 0, one workgroup per group (F = 33)             */
+#define CFFM_WGRAD_DIRECT0 5          /* wgrad_kernel<NT>: direct layer 0                                                          */
+#define CFFM_WGRAD_WGRAD2 6           /* wgrad2_kernel<NT>: layers >= 1 of the wide filters, fp32 MFMA                             */
+#define CFFM_WGRAD_WGRAD3 7           /* wgrad3_kernel<NT>: the same tile as bf16x3                                                */
+#define CFFM_DGRAD_NONE 0             /* the weight-gradient launch also computes the input gradient (CFFM_WGRAD_FACT_BWD)         */
+#define CFFM_DGRAD_TAPS 1             /* dgrad_taps_kernel<NT, RM, HALVES>; paired: the input-gradient role of conv_bwd_pair_kernel */
+#define CFFM_DGRAD_TILE_PACKED 2      /* conv0_fact_tile_dgrad2_kernel: tiled layer 0 on the packed filter                         */
+#define CFFM_DGRAD_DIRECT 3           /* dgrad_kernel<NT, RM>: implicit GEMM of the wide filters                                   */
+typedef struct cffm_kernel_choice {
+    int32_t family;
+    int32_t NT;                             /* column tiles of 16 channels per workgroup                                       */
+    int32_t RM;                             /* row tiles per workgroup: of 16 rows (ROWS: 64) narrow, of 64 rows DIRECT        */
+    int32_t HALVES;                         /* 256-thread halves of a tap-split gradient workgroup                             */
+    int32_t b3;                             /* 1: bf16x3 contraction on the bf16 pipe; always 0 under CFFM_CONV_FP32=1          */
+} cffm_kernel_choice_t;
+typedef struct cffm_conv_choice {
+    cffm_kernel_choice_t fwd, wgrad, dgrad;
+    int32_t paired;                         /* 1: wgrad and dgrad are two roles of ONE launch, conv_bwd_pair_kernel<NT, dgrad.RM> */
+    int32_t top_wgrad_deferred;             /* 1: the slab plan of (shape, B) leaves the weight gradients of the fused top of the
+                                               backward to the pair launch of the layer below it (the same for every layer)      */
+} cffm_conv_choice_t;
+
 /* ---- layout queries (host only, no GPU needed) -------------------------------------------------- */
 int cffm_abi_version(void);
 const char *cffm_error_string(int err);
 int cffm_theta_layout(const cffm_shape_t *s, cffm_theta_layout_t *out);
 int cffm_ws_layout(const cffm_shape_t *s, int32_t B, cffm_ws_layout_t *out);
+/* The kernels cffm_outer_conv0_fwd / cffm_conv_fwd and cffm_outer_conv0_bwd / cffm_conv_bwd launch for conv layer `layer`
+ * (0 <= layer < live) of shape s at batch B >= 1, with the slab count of the real slab plan: the one decision the stages
+ * themselves switch on.  Launches nothing.  b3 reflects this process's CFFM_CONV_FP32 latch. */
+int cffm_conv_choice(const cffm_shape_t *s, int32_t B, int32_t layer, cffm_conv_choice_t *out);
 
 /* ---- stage entry points ------------------------------------------------------------------------ */
 /* tf.nn.embedding_lookup x3 (CFFM.py:303, :354, :422): ids int32 [B*F] -> Ei [B,F,K], Eo [B,F,D],

@@ -8,7 +8,7 @@ Two paths on the same seeded case:
 Cases with a bf16x3 instance (wide filters, NT = 8: the forward / input gradient of a layer with >= 32768 rows, the weight gradient
 of every layer >= 1) run a second time in a child process with CFFM_CONV_FP32=1 (latched in a static at first use, so it cannot
 change within one process); the child returns the statistics of the fp32 loops, which the distribution and bias tiers of the
-bf16x3 tensors are held against (b3_instances() names them per case)."""
+bf16x3 tensors are held against (b3_set() names them per case)."""
 import json
 import os
 import subprocess
@@ -75,27 +75,15 @@ def b3_residual_ceiling(inst, Pp):
     return None
 
 
-def _pick_nt(tiles):
-    nb = (tiles + 7) // 8
-    need = (tiles + nb - 1) // nb
-    return next(n for n in (1, 2, 3, 4, 6, 8) if n >= need)
-
-
-def b3_instances(cfg, B):
-    """(direction, layer) pairs that run on the bf16 pipe by default (conv.hip: launch_conv_fwd / launch_dgrad NT = 8, RM = 2 at
-    >= 128 x 256 rows; launch_wgrad2<8> -> wgrad3_kernel)."""
-    Pp = (cfg.P + 15) // 16 * 16
+def b3_set(cfg, B):
+    """(direction, layer) pairs that run on the bf16 pipe in this process: asked of the library (cffm_conv_choice, the decision the
+    stages themselves switch on), not restated here."""
+    from cffm_amd import hip
+    shape = hip.make_shape(cfg)
     out = set()
-    if Pp <= 64:
-        return out
-    for l in range(1, cfg.live_layers):
-        rows = B * (cfg.D >> (l + 1)) ** 2
-        if _pick_nt(Pp // 16) == 8:
-            out.add(('wgrad', l))
-            if rows >= 128 * 256:
-                out.add(('fwd', l))
-        if _pick_nt(4 * Pp // 16) == 8 and rows >= 128 * 256:
-            out.add(('dgrad', l))
+    for l in range(cfg.live_layers):
+        ch = hip.conv_choice(shape, B, l)
+        out |= {(d, l) for d in ('fwd', 'wgrad', 'dgrad') if getattr(ch, d).b3}
     return out
 
 
@@ -220,13 +208,14 @@ def stage_grads(eng, flat):
     return g
 
 
-def run_case(name, res, fails, twin=None, bias=True, known=None):
-    """Both paths of one case: fills res = {'product': stats, 'stage': stats} and fails (see check_layers)."""
+def run_case(name, res, fails, twin=None, bias=True, known=None, b3=None):
+    """Both paths of one case: fills res = {'product': stats, 'stage': stats} and fails (see check_layers).  b3: the bf16x3 tensors of
+    the case by default (the CFFM_CONV_FP32=1 child gets them from its parent: its own library reports none)."""
     from cffm_amd import hip
     from cffm_amd.engine import HipEngine
     cfg, p32, X, y = make_layer_case(name)
     B = X.shape[0]
-    b3 = frozenset(b3_instances(cfg, B))
+    b3 = frozenset(b3_set(cfg, B) if b3 is None else b3)
     eng = HipEngine(cfg, params=p32)
     ids, yt = torch.from_numpy(X).cuda(), torch.from_numpy(y).cuda()
     eng.forward(ids, yt)
@@ -280,11 +269,11 @@ def run_case(name, res, fails, twin=None, bias=True, known=None):
     torch.cuda.empty_cache()
 
 
-def _fp32_twin(name):
+def _fp32_twin(name, b3):
     env = dict(os.environ, CFFM_CONV_FP32='1')
     code = ('import json, sys; sys.path.insert(0, %r); from tests.test_gpu_layers import run_case; res, fails = {}, []; '
-            'run_case(%r, res, fails, bias=False); print("TWIN " + json.dumps(res)); sys.exit("\\n".join(fails) if fails else 0)'
-            % (ROOT, name))
+            'run_case(%r, res, fails, bias=False, b3=%r); print("TWIN " + json.dumps(res)); sys.exit("\\n".join(fails) if fails else 0)'
+            % (ROOT, name, sorted(b3)))
     r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, 'fp32-loop twin of %s failed (%d):\n%s' % (name, r.returncode, (r.stdout + r.stderr)[-4000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('TWIN ')][-1]
@@ -307,11 +296,11 @@ def _report(name, res, twin):
 @pytest.mark.parametrize('name', list(CASES))
 def test_layers(name):
     cfg, _, X, _ = make_layer_case(name)
-    b3 = b3_instances(cfg, X.shape[0])
-    twin = _fp32_twin(name) if b3 else None
+    b3 = b3_set(cfg, X.shape[0])
+    twin = _fp32_twin(name, b3) if b3 else None
     res, fails, known = {}, [], []
     try:
-        run_case(name, res, fails, twin=twin, known=known if CASES[name].get('heavy') else None)
+        run_case(name, res, fails, twin=twin, known=known if CASES[name].get('heavy') else None, b3=b3)
     finally:
         _report(name, res, twin)
     for path, st in res.items():

@@ -178,11 +178,11 @@ def test_tiers_separate_mutants(replay):
 
 def test_b3_coverage():
     """The GPU layer cases (tests/test_gpu_layers.py) reach every bf16x3 instance with each A-operand activation build, and the gelu arm of the wide kernels."""
-    from tests.test_gpu_layers import CASES, b3_instances, make_layer_case
+    from tests.test_gpu_layers import CASES, b3_set, make_layer_case
     seen = {}
     for name, c in CASES.items():
         cfg, _, X, _ = make_layer_case(name)
-        for d, _ in b3_instances(cfg, X.shape[0]):
+        for d, _ in b3_set(cfg, X.shape[0]):
             seen.setdefault(d, set()).add(c['act'])
     assert {'relu', 'selu', 'gelu'} <= seen.get('fwd', set()) and {'relu', 'selu', 'gelu'} <= seen.get('dgrad', set()), seen
     assert 'gelu' in seen.get('wgrad', set()) and len(seen['wgrad']) >= 3, seen
