@@ -44,7 +44,8 @@ def parse_args(argv=None):
     add('--lr', type=float, default=0.05, help='Learning rate.')
     add('--loss_type', nargs='?', default='square_loss',
         help='Specify a loss type (square_loss or log_loss or mse or mae).')
-    add('--optimizer', nargs='?', default='AdagradOptimizer', help='Specify an optimizer type (AdagradOptimizer).')
+    add('--optimizer', nargs='?', default='AdagradOptimizer', help='Specify an optimizer type (AdagradOptimizer, GradientDescentOptimizer, MomentumOptimizer, AdamOptimizer; '
+                            'under a process group every one but AdamOptimizer).')
     add('--verbose', type=int, default=1, help='Show the results per X epochs (0, 1 ... any positive integer)')
     add('--batch_norm', type=int, default=0, help='Parsed, unused (as in the reference graph).')
     add('--tensorboard', type=int, default=0, help='Accepted and ignored (the reference crashes with 1).')
@@ -191,9 +192,10 @@ class CFFM(object):
         self.world, self.rank = self._join_group(torch.device('cuda', dev) if torch.cuda.is_available() else None)
         if self.world > 1:
             # what the row-sharded step does not implement is refused here, by name, before the first collective
-            if self.optimizer_type != 'AdagradOptimizer':
-                raise ValueError('CFFM_TABLES=sharded: the multi-GPU update is Adagrad only; --optimizer %s runs on one GPU'
-                                 % self.optimizer_type)
+            from .dist import MULTI_GPU_OPTIMIZERS
+            if self.optimizer_type not in MULTI_GPU_OPTIMIZERS:
+                raise ValueError('CFFM_TABLES=sharded: the multi-GPU update implements %s; --optimizer %s runs on one GPU'
+                                 % (', '.join(MULTI_GPU_OPTIMIZERS), self.optimizer_type))
             if self.loss_type == 'hybrid':
                 raise ValueError('CFFM_TABLES=sharded: --loss_type hybrid runs on one GPU only')
             if self.loss_type == 'square_loss' and self.lamda_bilinear > 0:

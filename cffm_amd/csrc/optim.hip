@@ -764,14 +764,20 @@ __global__ __launch_bounds__(256) void sparse_opt_kernel(const unsigned long lon
     }
 }
 
+// the constants of CFFM.py:519-529, for the single-GPU step and the multi-GPU apply alike (step >= 1; only Adam reads lr_t)
+static OptConst opt_const(const cffm_shape_t* s, int64_t step) {
+    OptConst c;
+    c.opt = s->optimizer; c.lr = s->lr; c.b1 = 0.9f; c.b2 = 0.999f; c.omb1 = (float)(1.0 - 0.9); c.omb2 = (float)(1.0 - 0.999); c.eps = 1e-8f; c.mom = 0.95f;
+    c.lr_t = (float)((double)s->lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
+    return c;
+}
+
 int cffm_apply_opt(const StepCtx& cx, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
                    float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, int64_t step, hipStream_t st) {
     const cffm_shape_t* s = cx.s;
     const cffm_theta_layout_t& tl = cx.tl;
     const cffm_ws_layout_t& wl = cx.wl;
-    OptConst c;
-    c.opt = s->optimizer; c.lr = s->lr; c.b1 = 0.9f; c.b2 = 0.999f; c.omb1 = (float)(1.0 - 0.9); c.omb2 = (float)(1.0 - 0.999); c.eps = 1e-8f; c.mom = 0.95f;
-    c.lr_t = (float)((double)s->lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
+    const OptConst c = opt_const(s, step);
     hipLaunchKernelGGL(dense_opt_kernel, dim3((unsigned)((tl.n + 255) / 256)), dim3(256), 0, st, theta, th1, th2, grad,
                        (int64_t)tl.n, c, 0.f);
     CFFM_CHECK_LAUNCH();
@@ -809,5 +815,152 @@ int cffm_apply_opt(const StepCtx& cx, const cffm_tables_t* tab, const cffm_table
                                t2.feat_bias, (const float*)Gfb, nf, c, 0.f);
         CFFM_CHECK_LAUNCH();
     }
+    return 0;
+}
+
+// ---- SGD and Momentum for the data-parallel and row-sharded steps (cffm_dp_apply_opt) -------------------------------
+// The launch structure of cffm_dp_apply with opt_update in place of the Adagrad rule: both rules are, like Adagrad, a dense
+// rule on theta and a duplicates-summed-first rule on the looked-up rows only (TF does not decay the Momentum accumulator
+// of a row nobody looked up), so the late 1/L, the key placement / run merge and the segment walk carry over unchanged.
+// Adam is not here: TF's sparse Adam is non-lazy (every row of every table moves every step).
+__device__ __forceinline__ void dense_opt_late_body(int bid, float* __restrict__ v, float* __restrict__ s1,
+                                                    const float* __restrict__ grad, int64_t n, const OptConst& oc,
+                                                    const LateScale& ls, float* __restrict__ loss_out) {
+    const int64_t i = (int64_t)bid * 256 + threadIdx.x;
+    if (i == 0 && loss_out != nullptr) loss_out[0] = ls.on ? sqrtf(ls.sum[0] * ls.inv_Bg + 1e-10f) : ls.sum[0] * ls.inv_Bg;
+    if (i >= n) return;
+    const float g = grad[i] * late_scale(ls);
+    float wv = v[i];
+    opt_update(wv, oc.opt == CFFM_OPT_MOMENTUM ? s1 + i : nullptr, nullptr, g, oc);
+    v[i] = wv;
+}
+
+// one wavefront per sorted position, segment heads only: sparse_adagrad_body's walk (both addressings of SparseArgs) with
+// opt_update on the row and, for Momentum, on its slot row (a.a_* = the first slot; not read for SGD)
+__device__ __forceinline__ void sparse_opt_late_body(int bid, const SparseArgs& a, const OptConst& oc) {
+    const unsigned long long* __restrict__ keys = a.keys;
+    const int64_t n = a.n;
+    const int M = a.M, K = a.K, D = a.D;
+    const float* __restrict__ dEi = a.dEi; const float* __restrict__ dEo = a.dEo; const float* __restrict__ dfb = a.dfb;
+    const float gscale = late_scale(a.ls);
+    const int64_t pos = (int64_t)bid * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (pos >= n) return;
+    const int id = (int)(keys[pos] >> 32);
+    if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;          // not a segment head
+    if (id < 0 || id >= M) return;
+    const int W = (dEi ? K : 0) + (dEo ? D : 0) + 1;     // columns: inner | outer | bias (a disabled branch has none)
+    const int Ki = dEi ? K : 0;
+    const bool slot = oc.opt == CFFM_OPT_MOMENTUM;
+    for (int c0 = 0; c0 < W; c0 += 64) {
+        const int c = c0 + lane;
+        if (c >= W) continue;
+        float g = 0.f;
+        for (int64_t q = pos; q < n; ++q) {
+            const unsigned long long kq = keys[q];
+            if ((int)(kq >> 32) != id) break;
+            int64_t sl = (int64_t)(kq & 0xffffffffull);
+            int64_t boff = 0;
+            if (a.run_len > 0) {
+                const int blk = fast_div((int)sl, a.inv_run_len);
+                boff = (int64_t)blk * a.run_stride;
+                sl -= (int64_t)blk * a.run_len;
+            }
+            g += c < Ki ? dEi[boff + sl * a.sEi + c] : (c < W - 1 ? dEo[boff + sl * a.sEo + (c - Ki)] : dfb[boff + sl * a.sfb]);
+        }
+        g *= gscale;
+        float *vp, *ap;
+        if (c < Ki) { const int64_t o = (int64_t)id * K + c; vp = a.inner + o; ap = slot ? a.a_inner + o : nullptr; }
+        else if (c < W - 1) { const int64_t o = (int64_t)id * D + (c - Ki); vp = a.outer + o; ap = slot ? a.a_outer + o : nullptr; }
+        else { vp = a.fbias + id; ap = slot ? a.a_fbias + id : nullptr; }
+        float wv = *vp;
+        opt_update(wv, ap, nullptr, g, oc);
+        *vp = wv;
+    }
+}
+
+__global__ __launch_bounds__(256) void dense_opt_late_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                             int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out) {
+    dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
+}
+
+__global__ __launch_bounds__(256) void sparse_opt_late_kernel(SparseArgs a, OptConst oc) { sparse_opt_late_body(blockIdx.x, a, oc); }
+
+// first launch of cffm_dp_apply_opt, sorted runs: dense rule with the late 1/L ∥ merge of the per-rank runs
+__global__ __launch_bounds__(256) void dp_opt_head_merge_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                                int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out,
+                                                                int n_dense, MergeArgs ma) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if ((int)blockIdx.x < n_dense) dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
+    else merge_runs_body(blockIdx.x - n_dense, ma, reinterpret_cast<unsigned*>(smem));
+}
+
+// first launch of cffm_dp_apply_opt, n_rows <= 8192 without runs: dense rule with the late 1/L ∥ placement of the keys
+__global__ __launch_bounds__(256) void dp_opt_head_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                          int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out, int n_dense,
+                                                          const int32_t* __restrict__ ids, int64_t id_stride, int n_keys, int n_rank,
+                                                          unsigned long long* __restrict__ keys_out) {
+    __shared__ float cnt[4 * RANK_KPW_MAX];
+    if ((int)blockIdx.x < n_dense) dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
+    else rank_place_body(blockIdx.x - n_dense, n_rank, ids, id_stride, n_keys, keys_out, cnt);
+}
+
+extern "C" int cffm_dp_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, float* theta,
+                                 float* theta_acc, const float* grad_sum, int64_t B_global, const float* rows,
+                                 int64_t n_rows, void* ws, int32_t B_ws, float* loss_out, int32_t n_runs, void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (s->optimizer == CFFM_OPT_ADAGRAD)
+        return cffm_dp_apply(s, tab, acc, theta, theta_acc, grad_sum, B_global, rows, n_rows, ws, B_ws, loss_out, n_runs, stream);
+    if (s->optimizer == CFFM_OPT_ADAM) return CFFM_ERR_UNSUPPORTED;       // non-lazy: a dense sweep of every table, not this design
+    // the checks of cffm_dp_apply, all of them before the first launch
+    if (n_runs > 0) {
+        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > CFFM_LDS_SHARED_CU) return CFFM_ERR_BAD_SHAPE;
+        const int64_t m = n_rows / n_runs;
+        if (m % s->F || !cffm_fwd_all_ok(s, (int32_t)(m / s->F))) return CFFM_ERR_UNSUPPORTED;      // the runs only exist on that path
+    } else if (n_rows > 0 && n_rows > (int64_t)B_ws * s->F) {
+        return CFFM_ERR_BAD_SHAPE;
+    }
+    const bool mom = s->optimizer == CFFM_OPT_MOMENTUM;
+    if (!tab || !theta || !grad_sum || (n_rows > 0 && (!rows || !ws)) || (mom && (!acc || !theta_acc))) return CFFM_ERR_BAD_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const StepCtx c(s, B_ws, theta, ws);
+    const cffm_theta_layout_t& tl = c.tl;
+    const OptConst oc = opt_const(s, 1);
+    LateScale ls = {grad_sum + tl.n, 1.f / (float)B_global, s->loss == CFFM_LOSS_SQUARE_RMSE ? 1 : 0};
+    const int64_t W = 1 + s->K + s->D + 1;
+    const RowGrads rg = RowGrads::packed(s, rows, W);
+    const cffm_tables_t no_slot = {nullptr, nullptr, nullptr};             // SGD keeps no slot
+    const cffm_tables_t* slot = mom ? acc : &no_slot;
+    float* th1 = mom ? theta_acc : nullptr;
+    const int n_dense = (int)((tl.n + 255) / 256);
+    SparseArgs a = c.sparse_args(tab, slot, n_rows, rg, ls);
+    if (n_runs > 0) {
+        const int m = (int)(n_rows / n_runs);
+        MergeArgs ma;
+        ma.rows = rows; ma.block_floats = (int64_t)m * (W + 2); ma.keys_off = (int64_t)m * W; ma.m = m; ma.n_runs = n_runs;
+        ma.out = c.at<unsigned long long>(c.wl.sort_vals);
+        const size_t lds = (size_t)n_rows * 4;
+        if ((rc = set_lds(dp_opt_head_merge_kernel, lds))) return rc;
+        hipLaunchKernelGGL(dp_opt_head_merge_kernel, dim3(n_dense + (unsigned)((n_rows + 255) / 256)), dim3(256), lds, st, theta, th1,
+                           grad_sum, (int64_t)tl.n, oc, ls, loss_out, n_dense, ma);
+        CFFM_CHECK_LAUNCH();
+        a.run_len = m; a.run_stride = ma.block_floats; a.inv_run_len = 1.f / (float)m;
+    } else if (n_rows > 0 && n_rows <= 8192) {
+        const int n_rank = 256;                              // kpw = ceil(n_rows / 256) <= 32 keys per workgroup
+        hipLaunchKernelGGL(dp_opt_head_kernel, dim3(n_dense + n_rank), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, oc, ls,
+                           loss_out, n_dense, (const int32_t*)rows, W, (int)n_rows, n_rank, c.at<unsigned long long>(c.wl.sort_vals));
+        CFFM_CHECK_LAUNCH();
+    } else {
+        hipLaunchKernelGGL(dense_opt_late_kernel, dim3((unsigned)n_dense), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, oc, ls,
+                           loss_out);
+        CFFM_CHECK_LAUNCH();
+        if (n_rows <= 0) return 0;
+        SortOpts so;
+        so.id_stride = W;                                    // the id column of the rows
+        if ((rc = cffm_sort_keys_impl(c, (const int32_t*)rows, n_rows, so, st))) return rc;
+    }
+    hipLaunchKernelGGL(sparse_opt_late_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a, oc);
+    CFFM_CHECK_LAUNCH();
     return 0;
 }

@@ -68,6 +68,7 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_dp_apply_dense);
     CFFM_BIND(cffm_backward_unscaled);
     CFFM_BIND(cffm_dp_apply);
+    CFFM_BIND(cffm_dp_apply_opt);
     CFFM_BIND(cffm_train_step);
     CFFM_BIND(cffm_train_step_opt);
     CFFM_BIND(cffm_packed_row_floats);

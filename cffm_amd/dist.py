@@ -11,11 +11,12 @@ over the GLOBAL batch, CFFM.py:493) and the parameter gradients:
      (41 K floats at frappe, 5 M at F=32)
   4. 1/L = rsqrt(sum/Bg + 1e-10) is applied to the summed gradients inside the update kernels
   5. sparse tables, three modes:
-       dense image (small vocabularies, e.g. frappe from 3 ranks up): every rank scatters its duplicates-summed row gradients
+       dense image (Adagrad only; small vocabularies, e.g. frappe from 3 ranks up): every rank scatters its duplicates-summed row gradients
            into a zeroed dense [M][K|D|1] image that rides in the SAME all-reduce as the dense gradients; one collective
            per step and a plain sweep of the tables afterwards (rows nobody looked up carry an exact 0 and stay put);
        replicated (default while the tables fit one GPU):  ONE all-gather of packed (id, row gradients); every rank then
-           runs the same sorted segment-sum + Adagrad over the Bg*F rows, so the replicas stay bit-identical;
+           runs the same sorted segment-sum + update (Adagrad, SGD or Momentum) over the Bg*F rows, so the replicas stay
+           bit-identical;
        row-sharded (``ShardedTables``, vocabulary beyond one GPU's HBM): ids all-to-all to the owner
            (row r lives on rank r % G), owners gather and send rows back, row gradients return by all-to-all and
            the owner applies the duplicates-summed-first update locally.
@@ -60,13 +61,19 @@ def replicas_agree(compute, group=None, tables=False):
     return bool(torch.equal(lo, hi))
 
 
-def require_adagrad(compute, who):
-    """The data-parallel updates (cffm_dp_apply, cffm_dp_apply_dense and the CPU stand-ins) implement Adagrad only: refuse
-    any other optimizer of a compute that carries a config, before the first collective."""
+MULTI_GPU_OPTIMIZERS = ('AdagradOptimizer', 'GradientDescentOptimizer', 'MomentumOptimizer')
+
+
+def require_supported_optimizer(compute, who):
+    """The multi-GPU updates (cffm_dp_apply / cffm_dp_apply_opt and the CPU stand-ins) implement Adagrad, SGD and Momentum:
+    a dense rule on theta and a rule on the looked-up rows only.  AdamOptimizer (TF's sparse Adam is non-lazy: every row of
+    every table moves every step, a dense sweep on every rank and not this exchange) and any unknown name are refused for a
+    compute that carries a config, by name, before the first collective."""
     cfg = getattr(compute, 'cfg', None)
     opt = getattr(cfg, 'optimizer', 'AdagradOptimizer') if cfg is not None else 'AdagradOptimizer'
-    if opt != 'AdagradOptimizer':
-        raise ValueError('%s: the multi-GPU update is Adagrad only; --optimizer %s runs on one GPU' % (who, opt))
+    if opt not in MULTI_GPU_OPTIMIZERS:
+        raise ValueError('%s: the multi-GPU update implements %s; --optimizer %s runs on one GPU' % (
+            who, ', '.join(MULTI_GPU_OPTIMIZERS), opt))
 
 
 class DataParallelStep(object):
@@ -76,12 +83,12 @@ class DataParallelStep(object):
     the flat gradient buffer, and 1/L is applied to the summed gradients in the update:
 
         forward (local) -> backward_unscaled (local) -> all-reduce [grad | loss sum] -> all-gather packed rows
-        (id | dEi | dEo | dfb) -> dp_apply: 1/L, dense Adagrad, sorted duplicates-first sparse Adagrad
+        (id | dEi | dEo | dfb) -> dp_apply: 1/L, dense update, sorted duplicates-first sparse update (Adagrad, SGD or Momentum)
 
     Every rank applies the same update to its replica, so the replicas stay bit-identical."""
 
     def __init__(self, compute, group=None, use_graph=False, mode='auto', sync=True):
-        require_adagrad(compute, 'DataParallelStep')
+        require_supported_optimizer(compute, 'DataParallelStep')
         self.c = compute
         self.group = group
         self.world = dist.get_world_size(group)
@@ -293,7 +300,7 @@ class ShardedStep(object):
     CPU tests."""
 
     def __init__(self, compute, group=None, dedup=True, sync=True, M_global=None):
-        require_adagrad(compute, 'ShardedStep')
+        require_supported_optimizer(compute, 'ShardedStep')
         self.c = compute
         self.group = group
         self.world = dist.get_world_size(group)

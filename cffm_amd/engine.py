@@ -566,17 +566,21 @@ class HipEngine(object):
         n_rows = rows_all.numel() // (W + 2) if n_runs > 0 else rows_all.shape[0]
         B_ws = max(1, -(-n_rows // self.cfg.F))       # an owner that received no rows still applies the dense update
         buf, _ = self.workspace(B_ws)
-        hip.check(self.lib.cffm_dp_apply(self._s, self._t, self._ta,
-                                         _ptr(self.theta), _ptr(self.theta_acc), _ptr(grad_full), int(B_global),
-                                         _ptr(rows_all), int(n_rows), _ptr(buf), int(B_ws), _ptr(self.loss_buf),
-                                         int(n_runs), self._stream()))
+        # SGD / Momentum: the same arguments, theta_acc / tables_acc read as the first slot (they start at 0 for these optimizers)
+        apply = self.lib.cffm_dp_apply if self.cfg.optimizer == 'AdagradOptimizer' else self.lib.cffm_dp_apply_opt
+        hip.check(apply(self._s, self._t, self._ta,
+                        _ptr(self.theta), _ptr(self.theta_acc), _ptr(grad_full), int(B_global),
+                        _ptr(rows_all), int(n_rows), _ptr(buf), int(B_ws), _ptr(self.loss_buf),
+                        int(n_runs), self._stream()))
         return self.loss_buf
 
     # ---- dense-table exchange (small vocabularies): ONE all-reduce per step ----------------------------------------
     def dp_dense_ok(self, B, world):
         """The dense image of the tables is at most twice what the ranks' row gradients add up to (it also saves the second
         collective and the merge + segment walk of the gathered rows: measured 133 vs 152 us per step at world size 1,
-        frappe), and the single-launch forward (which leaves the sorted keys the scatter needs) covers this shape."""
+        frappe), and the single-launch forward (which leaves the sorted keys the scatter needs) covers this shape.  Adagrad only:
+        an exact 0 in the all-reduced image cannot tell "row not looked up" from "gradients summed to 0", and Momentum must decay
+        the accumulator in the second case and not in the first; SGD and Momentum always take the all-gather route."""
         W = self.cfg.K + self.cfg.D + 1
         return bool(self.lib.cffm_dp_runs_ok(self._s, int(B))) and \
             self.cfg.M * W <= 2 * world * B * self.cfg.F * (W + 3) and self.cfg.optimizer == 'AdagradOptimizer'

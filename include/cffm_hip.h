@@ -276,14 +276,28 @@ int cffm_dp_apply_dense(const cffm_shape_t *s, const cffm_tables_t *tab, const c
  * n_runs = 0 takes rows [n_rows][1+K+D+1] in any order and sorts the keys itself; with n_runs > 0 rows is the
  * concatenation of n_runs cffm_dp_local buffers (n_rows / n_runs slots each): the sorted runs are merged by rank
  * (binary searches in LDS) instead of a radix sort of all n_rows keys.  cffm_dp_apply takes
- * the all-reduced grad and the all-gathered rows, applies 1/L and the dense + sparse Adagrad updates.  Both data-parallel
- * updates (cffm_dp_apply, cffm_dp_apply_dense) are Adagrad only: any other s->optimizer returns CFFM_ERR_UNSUPPORTED
- * before a pointer is read. */
+ * the all-reduced grad and the all-gathered rows, applies 1/L and the dense + sparse Adagrad updates.  These two entry
+ * points (cffm_dp_apply, cffm_dp_apply_dense) are Adagrad only: any other s->optimizer returns CFFM_ERR_UNSUPPORTED
+ * before a pointer is read.  cffm_dp_apply_opt (below) is the apply of the other optimizers. */
 int cffm_backward_unscaled(const cffm_shape_t *s, const float *theta, const int32_t *ids, const float *y, int32_t B,
                            int64_t B_global, void *ws, float *grad, float *rows, void *stream);
 int cffm_dp_apply(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *acc, float *theta,
                   float *theta_acc, const float *grad_sum, int64_t B_global, const float *rows, int64_t n_rows,
                   void *ws, int32_t B_ws, float *loss_out, int32_t n_runs, void *stream);
+/* cffm_dp_apply for every optimizer the multi-GPU steps run (as cffm_train_step_opt is to cffm_train_step): the same
+ * arguments, the same three routes (sorted runs merged, <= 8192 keys placed, else radix sort) and the same late 1/L.
+ * CFFM_OPT_ADAGRAD forwards to cffm_dp_apply.  CFFM_OPT_SGD: w -= lr * g.  CFFM_OPT_MOMENTUM: a = 0.95 * a + g, w -= lr * a,
+ * with acc / theta_acc read as the Momentum accumulators (the first slot; both may be NULL for SGD).  theta gets the dense
+ * rule; a table row gets the rule once, on the sum of its duplicates, and only if some rank looked it up: the other rows
+ * and their accumulators are neither read nor written (TF's sparse apply; an untouched row's accumulator does not decay).
+ * CFFM_OPT_ADAM returns CFFM_ERR_UNSUPPORTED right after the shape check, before a pointer is read: TF's sparse Adam is
+ * non-lazy (every row of every table moves every step), which is a dense sweep and not this exchange.  There is no
+ * dense-image variant (cffm_dp_apply_dense stays Adagrad only): an exact 0 in the all-reduced image cannot tell "row not
+ * looked up" from "gradients summed to 0", and Momentum must decay the accumulator in the second case only.
+ * CFFM_ERR_BAD_SHAPE as cffm_dp_apply (n_rows / n_runs / B_ws), checked before the first launch. */
+int cffm_dp_apply_opt(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *acc, float *theta,
+                      float *theta_acc, const float *grad_sum, int64_t B_global, const float *rows, int64_t n_rows,
+                      void *ws, int32_t B_ws, float *loss_out, int32_t n_runs, void *stream);
 /* sess.run((self.loss, self.optimizer)) CFFM.py:200: one fused forward + backward + Adagrad update of
  * theta/tables (and their accumulators) in place; loss (device scalar, may be NULL) receives the loss. */
 int cffm_train_step(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *tab_acc,
