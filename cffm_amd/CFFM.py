@@ -71,6 +71,17 @@ def configure_logging(logFilename):
     logging.getLogger().addHandler(console)
 
 
+def ranking_metrics(ranks, k):
+    """(HR@k, NDCG@k) of 0-based ranks of one relevant item each: HR = mean(rank < k), NDCG = mean(1 / log2(rank + 2) if
+    rank < k else 0), in float64 on the host.  A negative rank (a target that was no candidate) counts as a miss."""
+    r = np.asarray(ranks, dtype=np.int64).reshape(-1)
+    if r.size == 0:
+        raise ValueError('ranking_metrics() needs at least one rank')
+    hit = (r >= 0) & (r < int(k))
+    gain = np.where(hit, 1.0 / np.log2(np.where(hit, r, 0).astype(np.float64) + 2.0), 0.0)
+    return float(hit.mean()), float(gain.mean())
+
+
 class CFFM(object):
     def __init__(self, features_M, pretrain_flag, save_file, inner_dims, outer_dims, loss_type, epoch, batch_size,
                  learning_rate, lamda_bilinear, keep, optimizer_type, batch_norm, verbose, tensorboard, num_field,
@@ -134,6 +145,7 @@ class CFFM(object):
         # multi-GPU (set by build_graph under torch.distributed): one process per GPU, data parallel over the batch
         # _sh: CFFM_TABLES=sharded at world size > 1 - cffm_amd.dist.ShardedStep over this rank's rows of the tables
         self.world, self.rank, self._dp, self._sh = 1, 0, None, None
+        self._train_split = None                       # the train split last passed to train()
 
     # ---- engine / data residency -----------------------------------------------------------------------
     def build_graph(self):
@@ -275,6 +287,7 @@ class CFFM(object):
         if self.engine is None:
             self.build_graph()
         eng = self.engine
+        self._train_split = data.Train_data            # recommend() / evaluate_ranking() draw their default candidates from it
         self.calculate_parameters()
         if self.verbose > 0:
             t2 = time()
@@ -431,6 +444,121 @@ class CFFM(object):
         block = max(int(self.batch_size), 8192)
         outs = [self.engine.predict(ids[s:s + block]) for s in range(0, ids.shape[0], block)]
         return torch.cat(outs).cpu().numpy().astype(np.float64) if outs else np.zeros((0,))
+
+    # ---- candidate ranking: what a trained recommender is asked for ------------------------------------------------------
+    # The reference stops at RMSE / R2; these sweep (context, candidate) pairs on the device (cffm_amd/csrc/rank.hip): the ids of
+    # the pairs are expanded there, scored by the ordinary forward, and top-k / rank-of-target run on the score buffer in ONE
+    # total order (score descending, -0 == +0, NaN last, ties by candidate position), so equal scores - frequent with +-1 labels
+    # and saturated predictions - always come back the same way.
+    def _ranking_engine(self):
+        if self.engine is None:
+            self.build_graph()
+        if self._sh is not None:
+            # the row-sharded forward is a matched collective over all ranks; a ranking sweep on it is not implemented
+            raise ValueError('CFFM_TABLES=sharded: recommend / evaluate_ranking run on replicated tables')
+        return self.engine
+
+    def _field_ids(self, splits, field):
+        """Sorted distinct ids in column `field` over the given splits, int32 on the device."""
+        import torch
+        cols = [self._device_split(d)[0][:, field] for d in splits]
+        return torch.unique(torch.cat(cols)).to(torch.int32)
+
+    def _candidates(self, candidates, field, splits):
+        import torch
+        if not 0 <= int(field) < self.num_field:
+            raise ValueError('field %r is outside [0, %d)' % (field, self.num_field))
+        if candidates is None:
+            return self._field_ids(splits, int(field))
+        cand = np.asarray(candidates)
+        if cand.ndim != 1 or cand.size == 0:
+            raise ValueError('candidates must be a non-empty 1-D array of feature ids')
+        return torch.from_numpy(np.ascontiguousarray(cand.astype(np.int32))).to(self.engine.device)
+
+    def recommend(self, contexts, field, candidates=None, k=10, skip=None, score_rows=1 << 22):
+        """For every context row (contexts [C,F] feature ids), the k candidates that score highest when their id is put at column
+        `field`.  candidates: 1-D feature ids (default: the sorted distinct ids in column `field` of the train split last passed
+        to train()); skip: optional boolean [C,N] over candidate positions, True = leave out (e.g. items already seen).
+        Contexts are processed in groups of max(1, score_rows // N), so the score buffer stays bounded.  Returns host arrays
+        (ids int32 [C,k] candidate feature ids, -1 padded; scores float32 [C,k] their raw predictions, NaN padded).  Local to
+        the calling rank: no collective."""
+        import torch
+        eng = self._ranking_engine()
+        if candidates is None and self._train_split is None:
+            raise ValueError('recommend(): no train split yet (train() was not called) - pass candidates')
+        if not 1 <= int(k) <= 1024:
+            raise ValueError('recommend(): k must be in [1, 1024]')
+        cand = self._candidates(candidates, field, [self._train_split])
+        ctx = np.asarray(contexts)
+        if ctx.ndim != 2 or ctx.shape[1] != self.num_field:
+            raise ValueError('contexts must be [C, %d] feature ids' % self.num_field)
+        ctx = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(eng.device)
+        C, N, k = int(ctx.shape[0]), int(cand.numel()), int(k)
+        mask = None
+        if skip is not None:
+            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(skip) != 0)).to(eng.device)
+            if tuple(mask.shape) != (C, N):
+                raise ValueError('skip must be [%d, %d]: contexts x candidates' % (C, N))
+            mask = mask.to(torch.uint8)
+        ids_out = torch.empty((C, k), dtype=torch.int32, device=eng.device)
+        val_out = torch.empty((C, k), dtype=torch.float32, device=eng.device)
+        group = max(1, int(score_rows) // N)
+        cand64 = cand.long()
+        for c0 in range(0, C, group):
+            c1 = min(C, c0 + group)
+            scores = eng.score_candidates(ctx[c0:c1], int(field), cand)
+            idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
+            ids_out[c0:c1] = torch.where(idx >= 0, cand64[idx.clamp(min=0).long()], cand64.new_full((), -1)).to(torch.int32)
+            val_out[c0:c1] = val
+        return ids_out.cpu().numpy(), val_out.cpu().numpy()
+
+    def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22):
+        """(HR@k, NDCG@k) of a split: for every row with label > 0 the context is the row and the target is the row's own id at
+        column `field`, ranked among the candidates (default: the sorted distinct ids in column `field` over the train split and
+        `data` together, so every target is a candidate).  Explicit candidates that lack a target raise ValueError.  The sweep
+        stays on the device: scores, rank of the target, and the two sums and the count in float64; under a process group with
+        replicated tables every rank takes a contiguous share of the positive rows and the sums are all-reduced."""
+        import torch
+        eng = self._ranking_engine()
+        ids, y, _ = self._device_split(data)
+        splits = [data] if self._train_split is None or self._train_split is data else [self._train_split, data]
+        cand = self._candidates(candidates, field, splits)
+        field, k = int(field), int(k)
+        if k < 1:
+            raise ValueError('evaluate_ranking(): k must be >= 1')
+        ctx = ids[y.reshape(-1) > 0]
+        P, N = int(ctx.shape[0]), int(cand.numel())
+        if P == 0:
+            raise ValueError('evaluate_ranking() needs at least one row with a positive label')
+        # position of every target in the candidate list (the first one, should the caller's list repeat an id)
+        tgt = ctx[:, field].long()
+        cs, order = torch.sort(cand.long(), stable=True)
+        at = torch.searchsorted(cs, tgt).clamp(max=N - 1)
+        missing = cs[at] != tgt
+        if bool(missing.any()):
+            raise ValueError('evaluate_ranking(): target id %d at field %d is not among the candidates'
+                             % (int(tgt[missing][0]), field))
+        tpos = order[at].to(torch.int32)
+        r0, r1 = 0, P
+        if self.world > 1:
+            share = -(-P // self.world)
+            r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
+        # [sum of hits, sum of gains, rows, NaN flag]: accumulated on the device, read once
+        sums = torch.zeros(4, dtype=torch.float64, device=eng.device)
+        group = max(1, int(score_rows) // N)
+        for c0 in range(r0, r1, group):
+            c1 = min(r1, c0 + group)
+            scores = eng.score_candidates(ctx[c0:c1], field, cand)
+            rank = eng.rank_of(scores, tpos[c0:c1]).double()
+            hit = rank < k
+            sums[0] += hit.sum()
+            sums[1] += torch.where(hit, 1.0 / torch.log2(rank + 2.0), torch.zeros_like(rank)).sum()
+            sums[2] += c1 - c0
+            sums[3] += torch.isnan(scores).any()
+        hits, gains, rows, bad = (float(v) for v in self._all_reduce_sum(sums).cpu().numpy())
+        if bad:
+            raise ValueError('evaluate_ranking(): predictions contain NaN')
+        return hits / rows, gains / rows
 
     # ---- host-side helpers with the reference's list semantics (CFFM.py:556-635) -------------------------
     def shuffle_in_unison_scary(self, x, y):

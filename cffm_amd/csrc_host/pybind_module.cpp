@@ -82,6 +82,10 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_init_table_rows);
     CFFM_BIND(cffm_eval_scratch_bytes);
     CFFM_BIND(cffm_eval_sums);
+    CFFM_BIND(cffm_expand_candidates);
+    CFFM_BIND(cffm_topk_scratch_bytes);
+    CFFM_BIND(cffm_topk);
+    CFFM_BIND(cffm_rank_of);
     CFFM_BIND(cffm_probe_copy);
     CFFM_BIND(cffm_probe_read);
     CFFM_BIND(cffm_probe_mfma);

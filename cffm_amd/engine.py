@@ -367,6 +367,84 @@ class HipEngine(object):
                                           self._stream()))
         return sums
 
+    # ---- candidate ranking (csrc/rank.hip): scores of (context, candidate) pairs, top-k and rank-of-target on the device ----
+    def score_candidates(self, ctx, field, cand, block=8192):
+        """Raw predictions of every (context, candidate) pair: ctx int32 [C,F] and cand int32 [N] on the device -> fp32 [C,N] on
+        the device, row c being context c with its id at `field` replaced by each candidate in turn.  The flattened [C*N] range
+        is swept in consecutive pieces of `block` rows (ragged last one): cffm_expand_candidates writes a piece's id rows,
+        cffm_predict writes its outputs into the piece's slice of the result.  The ordinary workspace serves every piece, as in
+        eval_sums; nothing synchronises."""
+        ctx, cand = self._ids(ctx), self._ids(cand.reshape(-1))
+        C, F = int(ctx.shape[0]), int(self.cfg.F)
+        N, block = int(cand.numel()), int(block)
+        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
+            raise ValueError('contexts must be [C, %d] feature ids' % F)
+        if N < 1 or block < 1 or not 0 <= int(field) < F:
+            raise ValueError('score_candidates: needs a candidate, block >= 1 and 0 <= field < %d' % F)
+        scores = torch.empty((C, N), dtype=torch.float32, device=self.device)
+        key = ('cand_ids', block)
+        ids = self._ws.get(key)
+        if ids is None:
+            ids = torch.empty((block, F), dtype=torch.int32, device=self.device)
+            self._ws[key] = ids
+        flat, st = scores.view(-1), self._stream()
+        for s0 in range(0, C * N, block):
+            m = min(block, C * N - s0)
+            buf, _ = self.workspace(m)
+            hip.check(self.lib.cffm_expand_candidates(self._s, _ptr(ctx), C, int(field), _ptr(cand), N, s0, m, _ptr(ids), st))
+            hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
+        return scores
+
+    def _rank_args(self, scores, skip):
+        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+            raise ValueError('scores must be fp32 [C, N] with contiguous rows')
+        C, N = int(scores.shape[0]), int(scores.shape[1])
+        row_stride = int(scores.stride(0)) if C > 1 else N
+        skip_stride = 0
+        if skip is not None:
+            if tuple(skip.shape) != (C, N):
+                raise ValueError('skip must be [C, N] like the scores')
+            if skip.dtype == torch.bool:
+                skip = skip.contiguous().view(torch.uint8)
+            elif skip.dtype != torch.uint8 or not skip.is_contiguous():
+                skip = (skip != 0).contiguous().view(torch.uint8)
+            skip_stride = N
+        return C, N, row_stride, skip, skip_stride
+
+    def topk(self, scores, k, skip=None):
+        """The k best candidates of every row of scores fp32 [C,N] (device) in the order of include/cffm_hip.h (score descending,
+        -0 == +0, NaN last, ties by position): (idx int32 [C,k] candidate positions, -1 padded; val fp32 [C,k] their scores bit
+        for bit, NaN padded; count int32 [C] = min(k, N - skipped)).  skip: optional [C,N] mask, non-zero = leave out."""
+        C, N, row_stride, skip, skip_stride = self._rank_args(scores, skip)
+        k = int(k)
+        key = ('topk', C, N, k)
+        scratch = self._ws.get(key)
+        if scratch is None:
+            nbytes = int(self.lib.cffm_topk_scratch_bytes(C, N, k))
+            if nbytes < 0:
+                raise ValueError('topk: needs N >= 1 and 1 <= k <= 1024 (N = %d, k = %d)' % (N, k))
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws[key] = scratch
+        dev = self.device
+        idx = torch.empty((C, k), dtype=torch.int32, device=dev)
+        val = torch.empty((C, k), dtype=torch.float32, device=dev)
+        count = torch.empty((C,), dtype=torch.int32, device=dev)
+        hip.check(self.lib.cffm_topk(_ptr(scores), row_stride, _ptr(skip), skip_stride, C, N, k, _ptr(scratch), _ptr(idx), _ptr(val),
+                                     _ptr(count), self._stream()))
+        return idx, val, count
+
+    def rank_of(self, scores, target, skip=None):
+        """0-based rank of candidate target[c] among the non-skipped candidates of row c, in the same order as topk: int32 [C] on
+        the device (-1 for a target outside [0, N))."""
+        C, N, row_stride, skip, skip_stride = self._rank_args(scores, skip)
+        target = self._ids(target.reshape(-1))
+        if int(target.numel()) != C:
+            raise ValueError('rank_of: one target per row of the scores')
+        rank = torch.empty((C,), dtype=torch.int32, device=self.device)
+        hip.check(self.lib.cffm_rank_of(_ptr(scores), row_stride, _ptr(skip), skip_stride, C, N, _ptr(target), _ptr(rank),
+                                        self._stream()))
+        return rank
+
     def predictions(self, B):
         """The [B] outputs the last forward (forward / forward_staged / forward_packed) left in the workspace, as a tensor of
         their own."""

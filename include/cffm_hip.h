@@ -369,6 +369,36 @@ int64_t cffm_eval_scratch_bytes(void);
 int cffm_eval_sums(const float *pred, const float *y, int64_t n, float lo, float hi, void *scratch, double *sums,
                    void *stream);
 
+/* ---- candidate ranking: score, top-k and rank-of-target on the device (cffm_amd/csrc/rank.hip) ---------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9, no existing signature, struct or kernel changes.  The reference has no
+ * ranking sweep (its evaluate() stops at RMSE / R2, CFFM.py:583-615): these replace nothing in it.
+ * THE ORDER on the candidates of one context, used by cffm_topk, cffm_rank_of and the numpy reference of the tests alike:
+ *   scores compare as IEEE floats with -0 == +0; NaN ranks below everything, -inf included; among equal scores the smaller
+ *   candidate position wins.  As a 64-bit key (larger = better): u = bits(s + 0.0f); key32 = 0 if s is NaN, ~u if the sign bit
+ *   of u is set, else u | 0x80000000; key64 = key32 << 32 | (0xffffffff - position); a skipped candidate has key64 = 0.
+ * Every compare is a 64-bit integer compare: the results are the same bits on every run.
+ * Argument rules: scores is [C][row_stride] floats with row_stride >= N, elements beyond N of a row are never read; skip may be
+ * NULL, else [C][skip_stride] bytes, non-zero = skipped.  C == 0 (rows == 0) returns 0 without a launch.  CFFM_ERR_BAD_SHAPE,
+ * before the first launch or HIP call, for: a NULL pointer that would be read or written; field outside [0, F); N < 1; k < 1;
+ * k > 1024; first < 0; rows < 0; first + rows > C * N; row_stride < N; skip_stride < N with skip != NULL.
+ *
+ * cffm_expand_candidates: the id rows of (context, candidate) pairs.  For global row g in [first, first + rows) of the flattened
+ * [C * N] range, c = g / N, n = g % N: ids_out[g - first][f] = (f == field) ? cand[n] : ctx[c][f]; ctx int32 [C][F], cand int32 [N].
+ * Writes exactly rows * F int32 values and nothing else.  Ids are not validated: cffm_predict clamps them as it always does. */
+int cffm_expand_candidates(const cffm_shape_t *s, const int32_t *ctx, int32_t C, int32_t field, const int32_t *cand, int32_t N,
+                           int64_t first, int32_t rows, int32_t *ids_out, void *stream);
+/* cffm_topk: for every row c the m = min(k, N - skipped) best candidates in descending order: idx_out[c][j] = candidate position,
+ * val_out[c][j] = its score bit for bit (j < m); idx_out[c][j] = -1 and val_out[c][j] = the bits 0x7fc00000 for m <= j < k;
+ * count_out[c] = m.  1 <= k <= 1024.  scratch: cffm_topk_scratch_bytes(C, N, k) bytes (< 0 on bad arguments; never smaller for a
+ * larger N).  Chunks of 8192 candidates are sorted in LDS by one workgroup each, their k survivors merged level by level. */
+int64_t cffm_topk_scratch_bytes(int32_t C, int32_t N, int32_t k);
+int cffm_topk(const float *scores, int64_t row_stride, const uint8_t *skip, int64_t skip_stride, int32_t C, int32_t N, int32_t k,
+              void *scratch, int32_t *idx_out, float *val_out, int32_t *count_out, void *stream);
+/* cffm_rank_of: rank_out[c] = number of non-skipped candidates of row c whose key64 is larger than the one of candidate target[c]
+ * (its 0-based rank; the skip flag at the target position itself is ignored); -1 for a target outside [0, N). */
+int cffm_rank_of(const float *scores, int64_t row_stride, const uint8_t *skip, int64_t skip_stride, int32_t C, int32_t N,
+                 const int32_t *target, int32_t *rank_out, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
