@@ -148,7 +148,8 @@ static int forward_impl(const StepCtx& c, const RowTables& rows, const float* y,
     const cffm_ws_layout_t& wl = c.wl;
     HeadFwdOpts ho;
     ho.sum_loss = !o.fused_step;
-    int rc = 0;
+    int rc = cffm_route_check(c);        // a kernel of this shape's step cannot fit a CU's LDS: refused before the first launch
+    if (rc) return rc;
     if (o.no_materialise && wide_rows(s, rows)) {
         if ((rc = cffm_gather_inner_fwd_wide(c, rows, stream))) return rc;
         const RowSrc ro = table_rows(s, tab->outer_emb, rows);
@@ -201,7 +202,8 @@ static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, flo
                          const BwdOpts& o = BwdOpts()) {
     const cffm_shape_t* s = c.s;
     const int32_t B = c.B;
-    int rc = 0;
+    int rc = cffm_route_check(c);        // as in forward_impl (also covers the inner-branch roles of bwd_top / conv_bwd_pair)
+    if (rc) return rc;
     if (!s->inner_conv || !s->outer_conv || !s->linear_att) {   // slabs of a disabled branch must read as zeros
         hipError_t e = hipMemsetAsync(c.at(c.wl.gpart), 0, (size_t)c.wl.gpart_floats * 4, stream);
         if (e != hipSuccess) return (int)e;

@@ -96,6 +96,26 @@ static inline int check_shape(const cffm_shape_t* s) {
     return 0;
 }
 
+// Dynamic LDS of the three per-example kernels whose claim grows with the shape (their bodies: head_body.hpp, inner_body.hpp).
+//   head forward    t1s [1024] + hpart [8][32] + rs [CFFM_MAX_FIELDS] + sc [4] + Et [F][D] + aW [F][F]
+//   inner forward   E [F][K] + pair lut [Pp] + up to 16 wavefront partials
+//   inner backward  E [F][K] + dE [4][F][K] + pair lut [Pp] + red [8]
+static inline size_t head_fwd_lds(const Geo& g) { return (size_t)(1024 + 8 * CFFM_HEAD_UNITS + CFFM_MAX_FIELDS + 4 + g.F * g.D + g.F * g.F) * 4 + 16; }
+static inline size_t inner_fwd_lds(const Geo& g) { return ((size_t)g.F * g.K + g.Pp + 16) * 4; }   // size_t: K has no upper bound
+static inline size_t inner_bwd_lds(const Geo& g) { return ((size_t)5 * g.F * g.K + g.Pp + 8) * 4; }
+// check_shape() bounds F and D but not K, so a shape it accepts can ask the inner-branch kernels for more LDS than a CU has (the
+// backward from F * K ~ 7,560 .. 8,160 on).  The head tops out at 152,864 bytes (F = 64 at D = 512) and always fits.  Such a shape is
+// refused on the host, before anything is launched: by every composite (cffm_route_check, internal.hpp) and by the stage launchers
+// of the head and the inner branch.  One answer per shape: the forward alone would still fit where only the backward does not.
+static inline int check_lds(const cffm_shape_t* s) {
+    const Geo g = make_geo(s);
+    static_assert((1024 + 8 * CFFM_HEAD_UNITS + CFFM_MAX_FIELDS + 4 + CFFM_MAX_FIELDS * 512 + CFFM_MAX_FIELDS * CFFM_MAX_FIELDS) * 4 + 16 <=
+                  CFFM_LDS_WHOLE_CU, "the head forward fits a CU at every accepted (F, D)");
+    if (s->inner_conv && (inner_fwd_lds(g) > (size_t)CFFM_LDS_WHOLE_CU || inner_bwd_lds(g) > (size_t)CFFM_LDS_WHOLE_CU))
+        return CFFM_ERR_UNSUPPORTED;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wide filters (Pp > 64): which kernel runs layer 0, how the conv GEMMs cut their columns, and the partial sum pools the conv
 // epilogues leave for the head (shared by the workspace layout in api.hip and the kernels in conv.hip / head.hip).
@@ -410,8 +430,9 @@ __device__ __forceinline__ void build_pair_lut(uint32_t* lut, int F, int Pp) {
     for (int p = P + threadIdx.x; p < Pp; p += blockDim.x) lut[p] = 0u;   // padded pairs -> (0,0), weights are 0
 }
 
-// n / d for 0 <= n < 2^19 and 1 <= d <= 2048 without the ~40-instruction integer division sequence:
-// (n + 0.5) * (1/d) is at least 0.5/d away from every integer, far above the fp32 rounding error.
+// n / d for 0 <= n < 2^19 and 1 <= d <= 4096 without the ~40-instruction integer division sequence:
+// (n + 0.5) * (1/d) is at least 0.5/d away from every integer, far above the fp32 rounding error.  tests/test_shape_domain.py lists
+// every call site with its divisors and checks that whole domain, with 1/d moved one ulp either way.
 __device__ __forceinline__ int fast_div(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {

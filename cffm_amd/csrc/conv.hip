@@ -480,7 +480,6 @@ __global__ __launch_bounds__(256, (NT == 8 && RM == 2 && !GEN) ? 3 : 1) void con
     for (int rm = 0; rm < RM; ++rm)
 #pragma unroll
         for (int j = 0; j < 4; ++j) psum[rm][j] = 0.f;
-    const int pact = GEN ? CFFM_ACT_RELU : a.act;              // (the pools apply self.activation to the stored relu output, :387)
     // The bias of every column tile is requested BEFORE the first store: a.bias and a.out may alias as far as hipcc knows, so a load
     // that follows a store is kept behind it and waits with vmcnt(0) - for itself and for every store in front of it (16 such round
     // trips per tile in the loop below as it was first written).
@@ -522,10 +521,12 @@ __global__ __launch_bounds__(256, (NT == 8 && RM == 2 && !GEN) ? 3 : 1) void con
             }
         }
     };
-    const bool plain_act = GEN || (a.act != CFFM_ACT_SELU && a.act != CFFM_ACT_GELU);
+    // (the pools apply self.activation to the stored relu output of EVERY layer, CFFM.py:387 - layer 0 included: GEN only means that
+    //  the A operand is generated from unactivated embedding rows.  Taking GEN as plain left selu's scale / gelu out of the layer-0
+    //  pool partials of every interior tile; tests/test_gpu_layers.py 'f16-d16-b5-selu', 'f23-d8-b4-gelu')
+    const bool plain_act = a.act != CFFM_ACT_SELU && a.act != CFFM_ACT_GELU;
     if (nvalid == NT && m0 + BM <= a.Mtot && plain_act) epilogue(std::true_type(), std::true_type());
     else epilogue(std::false_type(), std::false_type());
-    (void)pact;
     if (a.pool != nullptr) {
         // s_{l+1}[b][y] partial of this column block: columns over the 16 lanes of a DPP row, then the So rows (x) of one y in
         // row order out of LDS (the filter tiles are dead; So <= 64 <= BM and both are powers of two: a y never straddles tiles)
@@ -2931,6 +2932,26 @@ static inline bool conv_b3_on() {
     return on;
 }
 // B3: the bf16x3 K loop (the 128 x 128 instance of layers >= 1 only); the filter changes every step: split it once for this launch
+// Dynamic LDS of the layer-0 instances whose embedding tile grows with F * D (the fp32 loops; the launchers below and the host-side
+// refusal cffm_conv_lds_check use the same functions)
+static inline size_t conv_fwd_direct_lds(int NT, int RM, bool gen, int Pp, int lgSo, int F, int D) {
+    return ((size_t)2 * KSTEP * (NT * 16 + 4) + (gen ? emb_tile_floats(Pp, fwd_tile_examples(64 * RM, lgSo), F, D) : 0) + 4) * 4;
+}
+static inline size_t dgrad_direct_lds(int NT, int RM, bool l0, int Pp, int lgSo, int F, int D) {
+    const size_t n_ex = l0 ? dgrad0_tile_examples(64 * RM, lgSo) : 0;
+    return ((size_t)2 * KSTEP * (NT * 16 + 4) + (l0 ? (size_t)Pp + 5 * n_ex * F * (D + 1) + 2 * n_ex * F : 0) + 4) * 4;
+}
+static inline size_t wgrad_direct0_lds(int NT, int Pp, int lgSo, int F, int D) {
+    const int LDB = NT * 16 + ((NT & 1) ? 0 : 16);
+    return ((size_t)WG_KM * LDB + emb_tile_floats(Pp, fwd_tile_examples(WG_KM, lgSo), F, D) + 4) * 4;
+}
+static inline size_t conv_fwd_taps_lds(int NT, int RM, bool gen, int lgSo, int F, int D) {
+    return conv_fwd_taps_scratch(NT * 16, RM) + (gen ? emb_tile_floats(NT * 16, fwd_tile_examples(16 * RM, lgSo), F, D) : 0) * 4 + 16;
+}
+static inline size_t conv_fwd_rows_lds(int NT, int RM, bool gen, int lgSo, int F, int D) {
+    return (size_t)4 * NT * 16 * NT * 16 * 4 + (gen ? emb_tile_floats(NT * 16, fwd_tile_examples(64 * RM, lgSo), F, D) : 0) * 4 + 16;
+}
+
 template <int NT, int RM, bool GEN, bool B3 = false>
 static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
@@ -2938,7 +2959,7 @@ static int launch_conv_fwd(const ConvArgs& a, int nblk, hipStream_t st) {
     b.nblk = nblk;
     const int64_t nb1 = 8 * xcd_per((a.Mtot + BM - 1) / BM) * nblk;
     if (nb1 > 0x7fffffffll || (B3 && b.wb3 == nullptr)) return CFFM_ERR_UNSUPPORTED;
-    size_t lds = ((size_t)2 * KSTEP * (NT * 16 + 4) + (GEN ? emb_tile_floats(a.Pp, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) + 4) * 4;
+    size_t lds = conv_fwd_direct_lds(NT, RM, GEN, a.Pp, a.lgSo, a.F, a.D);
     if constexpr (B3) {
         lds = (size_t)gemm_b3_lds_bytes<NT>() + 16;
         b.wb3_npad = (a.Pp + 127) / 128 * 128;
@@ -2951,8 +2972,7 @@ template <int NT, int RM, bool L0, bool B3 = false>
 static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
     constexpr int BM = 64 * RM;
     const int rows_per_wg = L0 ? dgrad0_rows_per_wg(BM, a.lgSo) : BM;
-    const int n_ex = L0 ? dgrad0_tile_examples(BM, a.lgSo) : 0;
-    size_t lds = (size_t)(2 * KSTEP * (NT * 16 + 4) + (L0 ? a.Pp + 5 * n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F : 0) + 4) * 4;
+    size_t lds = dgrad_direct_lds(NT, RM, L0, a.Pp, a.lgSo, a.F, a.D);
     DgradArgs b = a;
     b.nblk = L0 ? 1 : nblk;
     const int64_t nb1 = 8 * xcd_per((a.Mtot + rows_per_wg - 1) / rows_per_wg) * b.nblk;
@@ -2967,8 +2987,8 @@ static int launch_dgrad(const DgradArgs& a, int nblk, hipStream_t st) {
 
 template <int NT>
 static int launch_wgrad(const WgradArgs& a, hipStream_t st) {
-    constexpr int BI = 64, BQ = NT * 16, LDB = BQ + ((NT & 1) ? 0 : 16);
-    const size_t lds = ((size_t)WG_KM * LDB + emb_tile_floats(a.Pp, fwd_tile_examples(WG_KM, a.lgSo), a.F, a.D) + 4) * 4;
+    constexpr int BI = 64, BQ = NT * 16;
+    const size_t lds = wgrad_direct0_lds(NT, a.Pp, a.lgSo, a.F, a.D);
     WgradArgs b = a;
     b.nslab = CFFM_NSLAB;                                                       // Pp > 64: conv_slabs() == CFFM_NSLAB
     b.nxy = ((4 * a.Pp + BI - 1) / BI) * a.qblocks;
@@ -2990,14 +3010,14 @@ static int launch_wgrad2(const WgradArgs& a, hipStream_t st) {
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_taps(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 16 * RM;
-    const size_t lds = conv_fwd_taps_scratch(PP, RM) + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
+    const size_t lds = conv_fwd_taps_lds(NT, RM, GEN, a.lgSo, a.F, a.D);
     return launch(conv_fwd_taps_kernel<NT, RM, GEN>, dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
 }
 
 template <int NT, int RM, bool GEN>
 static int launch_conv_fwd_rows(const ConvArgs& a, hipStream_t st) {
     constexpr int PP = NT * 16, BM = 64 * RM;
-    const size_t lds = (size_t)4 * PP * PP * 4 + (GEN ? emb_tile_floats(PP, fwd_tile_examples(BM, a.lgSo), a.F, a.D) : 0) * 4 + 16;
+    const size_t lds = conv_fwd_rows_lds(NT, RM, GEN, a.lgSo, a.F, a.D);
     return launch(conv_fwd_rows_kernel<NT, RM, GEN>, dim3((unsigned)((a.Mtot + BM - 1) / BM)), dim3(256), lds, st, a);
 }
 
@@ -3978,10 +3998,11 @@ static int launch_conv0_fact_tile_fwd2(const ConvArgs& a, float* wpack, hipStrea
 }
 
 // the round-2 kernel: shapes without the packed filter (D >= 128)
+static inline size_t conv0_tile_fwd_lds(int F, int D) { return (size_t)(2 * F * (16 * 16 + 16) + F * (D + 1) + 8 * (D / 2)) * 4 + 16; }   // 8 = NW
 static int launch_conv0_fact_tile_fwd(const ConvArgs& a, hipStream_t st) {
     constexpr int NW = 8;                // measured at F32 D64 B8192: 38.6 ms with 4 wavefronts, 29.2 with 8, 36.6 with 16 (one workgroup per CU)
     const int S = a.D / 2;
-    const size_t lds = (size_t)(2 * a.F * (16 * 16 + 16) + a.F * (a.D + 1) + NW * S) * 4 + 16;
+    const size_t lds = conv0_tile_fwd_lds(a.F, a.D);
     const int64_t grid = (int64_t)a.B * (a.Pp / 16) * (S / 16);
     if (grid > 0x7fffffffll) return CFFM_ERR_UNSUPPORTED;
     return launch(conv0_fact_tile_fwd_kernel<NW>, dim3((unsigned)grid), dim3(64 * NW), lds, st, a);
@@ -4027,15 +4048,25 @@ static int launch_conv0_fact_bwd(const DgradArgs& a, float* slabW, float* slabB,
     return go(IntC<0>(), IntC<0>());
 }
 
+static inline size_t dgrad_taps_lds(int NT, int RM, bool l0, int HALVES, int lgSo, int F, int D) {
+    const int PP = NT * 16, So = 1 << lgSo;
+    const size_t n_ex = l0 ? dgrad0_tile_examples(16 * RM, lgSo) : 0;
+    const bool fast = l0 && RM == 4 && lgSo >= 4 && lgSo <= 6;
+    const size_t scratch = fast ? (size_t)(4 + 4 * HALVES) * PP * So : (size_t)4 * HALVES * n_ex * F * (D + 1);
+    return (l0 ? (size_t)PP + n_ex * F * (D + 1) + 2 * n_ex * F + scratch : 0) * 4 + 16;
+}
+static inline size_t wgrad_taps_lds(int NT, bool gen, int HALVES, int lgSo, int F, int D) {
+    const int S2 = 1 << (2 * lgSo);
+    const size_t n_ex_max = gen ? WGT_SUB / S2 + 2 : 0;
+    const size_t base = (size_t)(WGT_SUB * NT * 16 + (gen ? NT * 16 + (n_ex_max * F * (D + 1) + 7) / 4 * 4 : 0)) * 4 + 16;
+    return base + (HALVES == 2 ? (size_t)4 * NT * NT * 64 * 16 + (size_t)NT * 64 * 4 : 0);
+}
+
 template <int NT, int RM, bool L0, int HALVES>
 static int launch_dgrad_taps(const DgradArgs& a, hipStream_t st) {
-    constexpr int PP = NT * 16, BM = 16 * RM;
+    constexpr int BM = 16 * RM;
     const int rows_per_wg = L0 ? dgrad0_rows_per_wg(BM, a.lgSo) : BM;
-    const int n_ex = L0 ? dgrad0_tile_examples(BM, a.lgSo) : 0;
-    const int So = 1 << a.lgSo;
-    const bool fast = L0 && RM == 4 && a.lgSo >= 4 && a.lgSo <= 6;
-    const size_t scratch = fast ? (size_t)(4 + 4 * HALVES) * PP * So : (size_t)4 * HALVES * n_ex * a.F * (a.D + 1);
-    const size_t lds = (L0 ? (size_t)PP + n_ex * a.F * (a.D + 1) + 2 * n_ex * a.F + scratch : 0) * 4 + 16;
+    const size_t lds = dgrad_taps_lds(NT, RM, L0, HALVES, a.lgSo, a.F, a.D);
     return launch(dgrad_taps_kernel<NT, RM, L0, HALVES>, dim3((unsigned)((a.Mtot + rows_per_wg - 1) / rows_per_wg)), dim3(256 * HALVES),
                   lds, st, a);
 }
@@ -4043,10 +4074,7 @@ static int launch_dgrad_taps(const DgradArgs& a, hipStream_t st) {
 // HALVES = 2: the cross-half reduction of the [4][NT][NT] tiles and of the bias on top
 template <int NT, bool GEN, int HALVES>
 static int launch_wgrad_taps(const WgradArgs& a, int nsl, hipStream_t st) {
-    const int S2 = 1 << (2 * a.lgSo);
-    const int n_ex_max = GEN ? WGT_SUB / S2 + 2 : 0;
-    const size_t base = (size_t)(WGT_SUB * NT * 16 + (GEN ? NT * 16 + (n_ex_max * a.F * (a.D + 1) + 7) / 4 * 4 : 0)) * 4 + 16;
-    const size_t lds = base + (HALVES == 2 ? (size_t)4 * NT * NT * 64 * 16 + (size_t)NT * 64 * 4 : 0);
+    const size_t lds = wgrad_taps_lds(NT, GEN, HALVES, a.lgSo, a.F, a.D);
     return launch(wgrad_taps_kernel<NT, GEN, HALVES>, dim3(nsl), dim3(256 * HALVES), lds, st, a);
 }
 
@@ -4198,10 +4226,44 @@ extern "C" int cffm_conv_choice(const cffm_shape_t* s, int32_t B, int32_t layer,
     return 0;
 }
 
+// Host-side refusal of the conv stack: the layer-0 instances stage the F rows of their examples in LDS, [F][D + 1]
+// floats per example (five copies in the input gradients), so for large F * D the instance the dispatch picks asks for more than a
+// CU has.  The layers >= 1 and the tiled / factorised layer-0 kernels have LDS claims that do not grow with F * D beyond what their
+// own *_ok() predicates admit.  CFFM_ERR_UNSUPPORTED before anything is launched; 0 for outer_conv = 0.
+int cffm_conv_lds_check(const StepCtx& c) {
+    const Geo& g = c.g;
+    if (!c.s->outer_conv) return 0;
+    int lgSo;
+    layer_rows(g, c.B, 0, &lgSo);
+    const KC f = conv_fwd_choice(g, c.B, 0, conv_b3_on());
+    const ConvBwdChoice b = conv_bwd_choice(g, c.B, 0, c.conv_slab(0).nslab, conv_b3_on());
+    size_t need = 0;
+    auto take = [&](size_t v) { if (v > need) need = v; };
+    switch (f.family) {
+        case CFFM_FWD_TAPS: take(conv_fwd_taps_lds(f.NT, f.RM, true, lgSo, g.F, g.D)); break;
+        case CFFM_FWD_ROWS: take(conv_fwd_rows_lds(f.NT, 1, true, lgSo, g.F, g.D)); break;
+        case CFFM_FWD_TILE: take(conv0_tile_fwd_lds(g.F, g.D)); break;
+        case CFFM_FWD_DIRECT: take(conv_fwd_direct_lds(f.NT, f.RM, true, g.Pp, lgSo, g.F, g.D)); break;
+        default: break;                   // FACT: conv0_fact_ok(); TILE_PACKED: D <= 64, F <= 32
+    }
+    switch (b.wgrad.family) {
+        case CFFM_WGRAD_TAPS: take(wgrad_taps_lds(b.wgrad.NT, true, b.wgrad.HALVES, lgSo, g.F, g.D)); break;
+        case CFFM_WGRAD_DIRECT0: take(wgrad_direct0_lds(b.wgrad.NT, g.Pp, lgSo, g.F, g.D)); break;
+        default: break;                   // FACT_BWD: conv0_fact_bwd_ok(); TILE_*: D <= 64, F <= 33
+    }
+    switch (b.dgrad.family) {
+        case CFFM_DGRAD_TAPS: take(dgrad_taps_lds(b.dgrad.NT, 4, true, b.dgrad.HALVES, lgSo, g.F, g.D)); break;
+        case CFFM_DGRAD_DIRECT: take(dgrad_direct_lds(8, b.dgrad.RM, true, g.Pp, lgSo, g.F, g.D)); break;
+        default: break;
+    }
+    return need > (size_t)CFFM_LDS_WHOLE_CU ? CFFM_ERR_UNSUPPORTED : 0;
+}
+
 // forward of layer l: argument block, choice (conv_fwd_choice), one switch that instantiates and launches
 int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs) {
     const Geo& g = c.g;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
+    if (int rc = cffm_conv_lds_check(c)) return rc;
     ConvArgs a = c.conv_args(l);
     const KC k = conv_fwd_choice(g, c.B, l, conv_b3_on());
     const bool tiled = k.family == CFFM_FWD_TILE || k.family == CFFM_FWD_TILE_PACKED;
@@ -4281,6 +4343,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
 int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o) {
     const Geo& g = c.g;
     if (l < 0 || l >= g.live) return CFFM_ERR_BAD_SHAPE;
+    if (int rc = cffm_conv_lds_check(c)) return rc;
     const SlabRange& sr = c.conv_slab(l);
     const int nsl = sr.nslab;
     WgradArgs wa = c.wgrad_args(l);
@@ -4464,6 +4527,7 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
     const Geo& g = c.g;
     const int32_t B = c.B;
     const cffm_ws_layout_t& wl = c.wl;
+    if (int rc = cffm_route_check(c)) return rc;
     FwdAllArgs fa{};
     fa.inner = c.inner_fwd_args(tab, ids);
     for (int l = 0; l < g.live; ++l) fa.conv[l] = c.conv_args(l);

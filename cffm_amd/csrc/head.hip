@@ -89,8 +89,12 @@ extern "C" int cffm_head_fwd(const cffm_shape_t* s, const float* theta, void* ws
 
 int cffm_head_fwd_impl(const StepCtx& c, const float* y, const HeadFwdOpts& o, hipStream_t stream) {
     if (2 * c.g.D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
+    int rc = check_lds(c.s);
+    if (rc) return rc;
+    const size_t lds = head_fwd_lds(c.g);          // above 64 KB from F * D + F * F > 15,032 on (F >= 50 at D = 256, F >= 28 at D = 512)
+    if ((rc = set_lds(head_fwd_kernel, lds))) return rc;
     const HeadArgs a = c.head_args(y, o.s0_ready);
-    hipLaunchKernelGGL(head_fwd_kernel, dim3(c.B), dim3(256), head_fwd_lds(c.g), stream, a);
+    hipLaunchKernelGGL(head_fwd_kernel, dim3(c.B), dim3(256), lds, stream, a);
     CFFM_CHECK_LAUNCH();
     if (y && o.sum_loss) {
         hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, stream, c.at<const float>(c.wl.sqerr), (int64_t)c.B,
@@ -109,6 +113,8 @@ extern "C" int cffm_head_bwd(const cffm_shape_t* s, const float* theta, void* ws
 
 int cffm_head_bwd_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t stream) {
     if (2 * c.g.D - 2 > 1024) return CFFM_ERR_UNSUPPORTED;
+    int rc = check_lds(c.s);
+    if (rc) return rc;
     const HeadBwdArgs a = c.head_bwd_args(y, B_global, o);
     hipLaunchKernelGGL(head_bwd_kernel, dim3(small_slabs(c.B)), dim3(256), 0, stream, a);
     CFFM_CHECK_LAUNCH();

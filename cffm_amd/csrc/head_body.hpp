@@ -35,7 +35,7 @@ __device__ __forceinline__ float loss_term(float out_raw, float y, int loss, flo
 // embedding tile, this thread's slice of the dense(32) kernel, the first-order inputs), so the kernel pays the
 // L2/HBM latency once instead of once per phase; the pooling sweep keeps four rows in flight per lane.
 #define HEAD_KPP 16      // preloaded dense(32) rows per thread: covers 2D-2 <= 128
-static inline size_t head_fwd_lds(const Geo& g) { return (size_t)(1024 + 8 * CFFM_HEAD_UNITS + CFFM_MAX_FIELDS + 4 + g.F * g.D + g.F * g.F) * 4 + 16; }
+// dynamic LDS: head_fwd_lds(g), common.hpp
 
 // NW wavefronts: the pooling sweeps, the embedding tile and s0 use all of them; the dense(32) partials stay on the
 // first 256 threads (8 parts x 32 units)

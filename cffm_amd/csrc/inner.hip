@@ -59,8 +59,12 @@ extern "C" int cffm_inner_fwd(const cffm_shape_t* s, const float* theta, void* w
 
 int cffm_inner_fwd_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, hipStream_t stream) {
     if (!c.s->inner_conv) return 0;
+    int rc = check_lds(c.s);
+    if (rc) return rc;
+    const size_t lds = inner_fwd_lds(c.g);         // (at most 38,848 bytes for a shape check_lds serves: set_lds is a no-op today and keeps the launch honest if that changes)
+    if ((rc = set_lds(inner_fwd_kernel, lds))) return rc;
     const InnerFwdArgs ia = c.inner_fwd_args(tab, ids);
-    hipLaunchKernelGGL(inner_fwd_kernel, dim3(c.B), dim3(256), inner_fwd_lds(c.g), stream, ia);
+    hipLaunchKernelGGL(inner_fwd_kernel, dim3(c.B), dim3(256), lds, stream, ia);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -75,10 +79,11 @@ static int cffm_inner_bwd_wide(const StepCtx& c, const RowSrc* rs, hipStream_t s
 
 int cffm_inner_bwd_rows(const StepCtx& c, const RowSrc* rs, hipStream_t stream) {
     if (!c.s->inner_conv) return 0;
+    int rc = check_lds(c.s);
+    if (rc) return rc;
     if (cffm_wide_regather_ok(c.s)) return cffm_inner_bwd_wide(c, rs, stream);
     const size_t lds = inner_bwd_lds(c.g);
-    int rc = set_lds(inner_bwd_kernel, lds);
-    if (rc) return rc;
+    if ((rc = set_lds(inner_bwd_kernel, lds))) return rc;
     int nslab;
     InnerBwdArgs a = c.inner_bwd_args(&nslab);
     if (rs) { a.Ei = rs->base; a.idx = rs->idx; a.idxM = rs->M; a.idxStride = rs->stride; }

@@ -43,7 +43,7 @@ struct InnerFwdArgs {
     float* inner_out;
     FusedGather fg;
 };
-static inline size_t inner_fwd_lds(const Geo& g) { return (size_t)(g.F * g.K + g.Pp + 16) * 4; }   // + up to 16 wavefront partials
+// dynamic LDS: inner_fwd_lds(g), common.hpp
 
 // ACTC >= 0: the activation id as a compile-time constant (the README shapes): every act switch folds away
 // EoL != nullptr (fused forward): the gather also leaves the outer rows of the example in LDS, [F][EoLp] floats, where the
@@ -147,7 +147,7 @@ struct InnerBwdArgs {
     int idxM = 0;
     int idxStride = 0;                                // floats between rows of that table (0 = K): see RowSrc
 };
-static inline size_t inner_bwd_lds(const Geo& g) { return (size_t)(5 * g.F * g.K + g.Pp + 8) * 4; }
+// dynamic LDS: inner_bwd_lds(g), common.hpp
 
 template <int ACTC = -1>
 __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, int nslab, char* smem, float L = 1.f) {

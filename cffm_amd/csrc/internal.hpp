@@ -79,6 +79,15 @@ struct ConvBwdOpts {
     bool with_top_wgrad = false;         // the fused top left its weight gradients to this launch (top_wgrad_deferred)
     const RowSrc* rs = nullptr;          // layer 0 of the wide shapes: rows straight from the table
 };
+// Shapes the shape check accepts but a CU's LDS cannot hold are refused on the host with CFFM_ERR_UNSUPPORTED, before
+// anything is launched: check_lds (common.hpp: the inner branch, sized by F * K) and cffm_conv_lds_check (conv.hip: the layer-0
+// instance the dispatch picks at this B, sized by F * D).  forward_impl / backward_impl / cffm_fwd_all_impl ask both first, the stage
+// launchers ask for their own kernels.
+int cffm_conv_lds_check(const StepCtx& c);
+static inline int cffm_route_check(const StepCtx& c) {
+    const int rc = check_lds(c.s);
+    return rc ? rc : cffm_conv_lds_check(c);
+}
 // forward / backward of conv layer l (0 = the outer-product layer); the exported per-stage entry points wrap these
 int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs = nullptr);
 int cffm_conv_bwd_impl(const StepCtx& c, int l, hipStream_t st, const ConvBwdOpts& o = ConvBwdOpts());

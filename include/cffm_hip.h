@@ -162,6 +162,11 @@ typedef struct cffm_conv_choice {
 int cffm_abi_version(void);
 const char *cffm_error_string(int err);
 int cffm_theta_layout(const cffm_shape_t *s, cffm_theta_layout_t *out);
+/* Pure layout queries: they serve every shape the shape check accepts.  What a step can RUN is smaller: with the
+ * inner branch on, 5 F K + Pp + 8 floats must fit a CU's LDS (163,328 bytes), and with the outer branch on the layer-0 kernels
+ * bound F * D (every F up to D = 64; F <= 48 except 11 at D = 128, F <= 24 at D = 256, F <= 8 or F = 12 at D = 512).  Every entry
+ * point that launches returns CFFM_ERR_UNSUPPORTED for a shape beyond that, before anything is launched.  One answer per shape:
+ * a forward-only caller is refused too where only a backward kernel does not fit. */
 int cffm_ws_layout(const cffm_shape_t *s, int32_t B, cffm_ws_layout_t *out);
 /* The kernels cffm_outer_conv0_fwd / cffm_conv_fwd and cffm_outer_conv0_bwd / cffm_conv_bwd launch for conv layer `layer`
  * (0 <= layer < live) of shape s at batch B >= 1, with the slab count of the real slab plan: the one decision the stages

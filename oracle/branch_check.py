@@ -87,6 +87,9 @@ C_SOFTMAX = 2 * DEV_ULP + 6                     # exp of the numerator and of ea
 C_LOSS = DEV_ULP + 4                            # per term: s + eps (its rounding moves the log by u: the |y| + |1 - y| part of S), log, the product, the sum
 C_DOUT = DEV_ULP + 10                           # worst: hybrid, two divisions
 C_HEAD_BWD = 12                                 # softmax backward: da, sda, dz, / lamda, dfb terms
+#   dC[top] = dt1[off_top + y] * act'(C_top) where C_top > 0 (head_bwd_example): one term; act' as in dz above (2 D + 6: cdf + x pdf),
+#   the product (1)
+C_DCTOP = 2 * DEV_ULP + 7
 
 
 # ---- activations ----------------------------------------------------------------------------------------------------------

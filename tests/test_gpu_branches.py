@@ -80,6 +80,19 @@ CASES = {
     'no-inner-f6-elu': dict(M=700, F=6, K=32, D=32, act='elu', B=33, family=None, inner_conv=0),
     'no-outer-f6-selu': dict(M=700, F=6, K=32, D=32, act='selu', B=33, family=None, outer_conv=0),
     'nolinatt-f10-gelu': dict(M=700, F=10, K=32, D=32, act='gelu', B=40, family=None, linear_att=0),
+    # the K and F edges of the accepted domain ("Shape domain"), all on inner_fwd_body / inner_bwd_body.  K no power of two,
+    # very small or large: the unit split p = u / K2, t = u % K2 (fast_div) and the 16-byte pieces of a row
+    'k4-f3-b9-prelu': dict(M=400, F=3, K=4, D=32, act='prelu', B=9, family=None),
+    'k12-f7-b40-gelu': dict(M=600, F=7, K=12, D=32, act='gelu', B=40, family=None),
+    'k20-f10-b33-selu': dict(M=900, F=10, K=20, D=32, act='selu', B=33, family=None, bad_ids=True),
+    'tie-k36-f6-b64-elu': dict(M=700, F=6, K=36, D=32, act='elu', B=64, family=None, tie=True),
+    'k100-f5-b17-relu': dict(M=400, F=5, K=100, D=32, act='relu', B=17, family=None),
+    'probe-last-f10-k128-selu': dict(M=900, F=10, K=128, D=32, act='selu', B=6, family=None, probe=(44, 63, 1)),
+    # F > 32: K == D in {32, 64} no longer takes the non-materialising route (cffm_wide_regather_ok wants F <= 32); the LDS of
+    # inner_bwd_body (5 F K floats) at its largest in the suite; F = CFFM_MAX_FIELDS with P = 2016 pairs
+    'f34-k32-d32-b3-relu': dict(M=2000, F=34, K=32, D=32, act='relu', B=3, family=None),
+    'f40-k64-d8-b3-elu': dict(M=2000, F=40, K=64, D=8, act='elu', B=3, family=None),
+    'f64-k8-d4-b3-gelu': dict(M=2000, F=64, K=8, D=4, act='gelu', B=3, family=None),
 }
 LOSSES = ('square_loss', 'mse', 'mae', 'log_loss', 'hybrid', 'square_l2')
 for _l in LOSSES[1:]:

@@ -27,6 +27,8 @@ from oracle import layer_check as lc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
+FWD_ROWS, FWD_TAPS, FWD_TILE, FWD_DIRECT, WGRAD_TAPS, WGRAD_DIRECT0, DGRAD_TAPS = 2, 3, 4, 6, 2, 5, 1      # include/cffm_hip.h
+
 CASES = {
     # narrow filters (Pp <= 64): tap-split kernels with 1 and 2 row groups, the rows kernel (>= 32768 rows at layer 1)
     'f6-d32-b16-selu': dict(F=6, K=8, D=32, act='selu', B=16),
@@ -50,8 +52,45 @@ CASES = {
     # weight gradients over all rows through the chunked float64 device reference; product path only (the stage path runs the
     # same instances at this shape).
     'cfg4-f32-d64-b8192-relu': dict(F=32, K=64, D=64, act='relu', B=8192, M=100000, heavy=True),
+    # The D and F edges of the accepted domain ("Shape domain").  'want' names the layer-0 instances a case is there for,
+    # (role, family, NT, RM, HALVES) as cffm_conv_choice reports them; the test asserts them, so a dispatch change cannot empty a case.
+    # B is the smallest that selects the instance.
+    # narrow filters away from D = 32 (no factorised layer 0): the tap-split layer-0 kernels at NT = 2, 3, 4; HALVES = 2 of the
+    # weight gradient wants >= 128 rows per slab (B = 8 at D = 64), of the input gradient >= 128 rows per example (D >= 64)
+    'f7-d16-b5-selu': dict(F=7, K=8, D=16, act='selu', B=5,
+                           want=[('fwd', FWD_TAPS, 2, 1, 0), ('wgrad', WGRAD_TAPS, 2, 0, 1), ('dgrad', DGRAD_TAPS, 2, 4, 1)]),
+    'f7-d64-b8-elu': dict(F=7, K=8, D=64, act='elu', B=8, want=[('wgrad', WGRAD_TAPS, 2, 0, 2), ('dgrad', DGRAD_TAPS, 2, 4, 2)]),
+    'f10-d16-b5-gelu': dict(F=10, K=8, D=16, act='gelu', B=5,
+                            want=[('fwd', FWD_TAPS, 3, 1, 0), ('wgrad', WGRAD_TAPS, 3, 0, 1), ('dgrad', DGRAD_TAPS, 3, 4, 1)]),
+    'f10-d64-b8-relu': dict(F=10, K=8, D=64, act='relu', B=8,
+                            want=[('fwd', FWD_TAPS, 3, 1, 0), ('wgrad', WGRAD_TAPS, 3, 0, 2), ('dgrad', DGRAD_TAPS, 3, 4, 2)]),
+    'f11-d8-b9-selu': dict(F=11, K=8, D=8, act='selu', B=9,
+                           want=[('fwd', FWD_TAPS, 4, 1, 0), ('wgrad', WGRAD_TAPS, 4, 0, 1), ('dgrad', DGRAD_TAPS, 4, 4, 1)]),
+    # wide filters at D <= 16 (no tiled layer 0): the direct layer-0 forward and wgrad_kernel at NT = 6 and NT = 8
+    'f12-d8-b7-elu': dict(F=12, K=8, D=8, act='elu', B=7, want=[('fwd', FWD_DIRECT, 6, 1, 0), ('wgrad', WGRAD_DIRECT0, 6, 0, 0)]),
+    'f20-d16-b3-relu': dict(F=20, K=8, D=16, act='relu', B=3, want=[('fwd', FWD_DIRECT, 6, 1, 0), ('wgrad', WGRAD_DIRECT0, 6, 0, 0)]),
+    'f16-d16-b5-selu': dict(F=16, K=8, D=16, act='selu', B=5, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    'f23-d8-b4-gelu': dict(F=23, K=8, D=8, act='gelu', B=4, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    # D = 128: six layers.  Narrow: two row groups on layer 0 (20480 rows).  Wide: the tiled layer-0 forward without the packed
+    # filter and wgrad_kernel over S = 64
+    'f3-d128-b5-relu': dict(F=3, K=8, D=128, act='relu', B=5, want=[('fwd', FWD_TAPS, 1, 2, 0)]),
+    'f10-d128-b2-selu': dict(F=10, K=8, D=128, act='selu', B=2,
+                             want=[('fwd', FWD_TAPS, 3, 1, 0), ('wgrad', WGRAD_TAPS, 3, 0, 2), ('dgrad', DGRAD_TAPS, 3, 4, 2)]),
+    # ... two row groups of the tap-split layer-0 forward at NT = 2, 3 (16384 rows), and conv_fwd_rows on layer 0 (32768 rows)
+    'f7-d128-b4-elu': dict(F=7, K=8, D=128, act='elu', B=4, want=[('fwd', FWD_TAPS, 2, 2, 0)]),
+    'f10-d128-b4-gelu': dict(F=10, K=8, D=128, act='gelu', B=4, want=[('fwd', FWD_TAPS, 3, 2, 0)]),
+    'f7-d128-b8-selu': dict(F=7, K=8, D=128, act='selu', B=8, want=[('fwd', FWD_ROWS, 2, 1, 0)]),
+    'f10-d128-b8-relu': dict(F=10, K=8, D=128, act='relu', B=8, want=[('fwd', FWD_ROWS, 3, 1, 0)]),
+    'f12-d128-b2-elu': dict(F=12, K=8, D=128, act='elu', B=2, want=[('fwd', FWD_TILE, 0, 0, 0), ('wgrad', WGRAD_DIRECT0, 6, 0, 0)]),
+    'f32-d128-b1-relu': dict(F=32, K=8, D=128, act='relu', B=1, want=[('fwd', FWD_TILE, 0, 0, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    # F above the tiled range (2 (F - 1) > 64 k values), up to CFFM_MAX_FIELDS at the one D whose workspace stays below 4 GiB
+    'f34-d8-b5-relu': dict(F=34, K=8, D=8, act='relu', B=5, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    'f34-d32-b3-selu': dict(F=34, K=8, D=32, act='selu', B=3, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    'f40-d16-b2-elu': dict(F=40, K=8, D=16, act='elu', B=2, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    'f64-d4-b3-relu': dict(F=64, K=8, D=4, act='relu', B=3, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
 }
 HEAVY = [k for k, v in CASES.items() if v.get('heavy')]
+WS_CAP = 4 << 30          # bytes of workspace a case of this file may ask for (the heavy case apart)
 
 
 # Two bf16x3 contractions keep a slope with the round-to-nearest split that the CPU replay of the split does not have and the
@@ -85,6 +124,22 @@ def b3_set(cfg, B):
         ch = hip.conv_choice(shape, B, l)
         out |= {(d, l) for d in ('fwd', 'wgrad', 'dgrad') if getattr(ch, d).b3}
     return out
+
+
+def check_instances(name, cfg, B):
+    """The layer-0 instances the case names ('want') are what the library picks at this (shape, B), and the workspace stays below
+    WS_CAP: asked on the host, before anything is allocated."""
+    from cffm_amd import hip
+    shape = hip.make_shape(cfg)
+    if not CASES[name].get('heavy'):
+        nbytes = hip.ws_layout(shape, B).bytes
+        assert nbytes < WS_CAP, '%s: workspace of %d bytes' % (name, nbytes)
+    ch = hip.conv_choice(shape, B, 0)
+    for role, family, NT, RM, HALVES in CASES[name].get('want', ()):
+        k = getattr(ch, role)
+        assert (k.family, k.NT, k.RM, k.HALVES) == (family, NT, RM, HALVES), \
+            '%s: layer 0 %s now runs (family %d, NT %d, RM %d, HALVES %d), the case is there for %s' % (
+                name, role, k.family, k.NT, k.RM, k.HALVES, (family, NT, RM, HALVES))
 
 
 def make_layer_case(name, seed=0):
@@ -296,6 +351,7 @@ def _report(name, res, twin):
 @pytest.mark.parametrize('name', list(CASES))
 def test_layers(name):
     cfg, _, X, _ = make_layer_case(name)
+    check_instances(name, cfg, X.shape[0])
     b3 = b3_set(cfg, X.shape[0])
     twin = _fp32_twin(name, b3) if b3 else None
     res, fails, known = {}, [], []

@@ -78,6 +78,13 @@ CASES = {
     # examples at Pp = 64 (too wide for conv01_bwd_kernel) and at D = 64 (five conv layers)
     'f11-d32-b256-relu': dict(M=800, F=11, K=8, D=32, act='relu', B=256),
     'f6-d64-b256-elu': dict(M=500, F=6, K=8, D=64, act='elu', B=256),
+    # the edges of the accepted shape domain ("Shape domain") as whole models, forward, backward and train step: D = 128
+    # (six conv layers, the head's dense(32) loop past its preloaded rows) with K = 12; F above the tiled range of layer 0;
+    # F = CFFM_MAX_FIELDS (P = 2016 pairs, the softmax on all 64 lanes); K = 20 with the tap-split layer 0 at D = 16
+    'd128-f3-k12-gelu': dict(M=300, F=3, K=12, D=128, act='gelu', B=5),
+    'f34-k8-d8-relu': dict(M=2000, F=34, K=8, D=8, act='relu', B=3),
+    'f64-k8-d4-selu': dict(M=2000, F=64, K=8, D=4, act='selu', B=3),
+    'f10-k20-d16-elu': dict(M=900, F=10, K=20, D=16, act='elu', B=37),
 }
 HEAVY = [k for k, v in CASES.items() if v.get('heavy')]       # oracle needs several GB and ~a minute per pass
 LIGHT = [k for k in CASES if k not in HEAVY]
@@ -164,7 +171,7 @@ TRAIN_CASES = ['tiny-relu', 'd16-gelu', 'bookx-relu', 'frappe-selu', 'mltag-full
                'bookx-b1024-dups', 'no-inner', 'no-outer', 'no-inner-no-outer', 'no-inner-nolinatt', 'no-outer-nolinatt',
                'fm-only-nolinatt', 'f10-d32-b100-elu', 'f7-d32-b64-gelu', 'f5-d32-b200-relu', 'f7-d32-b63-gelu',
                'f11-d32-b256-relu', 'f6-d64-b256-elu', 'f16-k32-d32-b70-selu', 'f13-k64-d64-b9-prelu', 'f20-k32-d32-b3-relu',
-               'f32-k64-d64-b11-selu']
+               'f32-k64-d64-b11-selu', 'd128-f3-k12-gelu', 'f34-k8-d8-relu', 'f64-k8-d4-selu', 'f10-k20-d16-elu']
 
 
 @pytest.mark.parametrize('name,trained_like', [(n, t) for n in TRAIN_CASES for t in (True, False)] + [(n, True) for n in HEAVY])
