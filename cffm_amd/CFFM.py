@@ -71,6 +71,11 @@ def configure_logging(logFilename):
     logging.getLogger().addHandler(console)
 
 
+# CFFM.recommend / CFFM.evaluate_ranking(sweep='auto'): the smallest candidate count from which the shared sweep
+# (HipEngine.score_candidates_shared) is used where the shape is served.  Set from profiles/sweep_vs_expand.md (how: there).
+SWEEP_MIN_N = 4082
+
+
 def ranking_metrics(ranks, k):
     """(HR@k, NDCG@k) of 0-based ranks of one relevant item each: HR = mean(rank < k), NDCG = mean(1 / log2(rank + 2) if
     rank < k else 0), in float64 on the host.  A negative rank (a target that was no candidate) counts as a miss."""
@@ -458,6 +463,23 @@ class CFFM(object):
             raise ValueError('CFFM_TABLES=sharded: recommend / evaluate_ranking run on replicated tables')
         return self.engine
 
+    @staticmethod
+    def _candidate_scorer(eng, sweep, N):
+        """The engine call that scores one group of contexts.  'expand': score_candidates, called exactly as before the shared
+        sweep existed; 'shared': score_candidates_shared (ValueError where the shape is not served); 'auto': the shared sweep
+        where the shape is served and N >= SWEEP_MIN_N, else expand."""
+        if sweep not in ('expand', 'shared', 'auto'):
+            raise ValueError("sweep must be 'expand', 'shared' or 'auto', not %r" % (sweep,))
+        if sweep == 'expand':
+            return eng.score_candidates
+        if sweep == 'shared':
+            if not eng.sweep_ok():
+                raise ValueError("sweep='shared': the shared sweep does not serve this shape (both branches, D = 32, F <= 10)")
+            return eng.score_candidates_shared
+        if SWEEP_MIN_N is not None and N >= SWEEP_MIN_N and eng.sweep_ok():
+            return eng.score_candidates_shared
+        return eng.score_candidates
+
     def _field_ids(self, splits, field):
         """Sorted distinct ids in column `field` over the given splits, int32 on the device."""
         import torch
@@ -475,13 +497,15 @@ class CFFM(object):
             raise ValueError('candidates must be a non-empty 1-D array of feature ids')
         return torch.from_numpy(np.ascontiguousarray(cand.astype(np.int32))).to(self.engine.device)
 
-    def recommend(self, contexts, field, candidates=None, k=10, skip=None, score_rows=1 << 22):
+    def recommend(self, contexts, field, candidates=None, k=10, skip=None, score_rows=1 << 22, sweep='expand'):
         """For every context row (contexts [C,F] feature ids), the k candidates that score highest when their id is put at column
         `field`.  candidates: 1-D feature ids (default: the sorted distinct ids in column `field` of the train split last passed
         to train()); skip: optional boolean [C,N] over candidate positions, True = leave out (e.g. items already seen).
         Contexts are processed in groups of max(1, score_rows // N), so the score buffer stays bounded.  Returns host arrays
         (ids int32 [C,k] candidate feature ids, -1 padded; scores float32 [C,k] their raw predictions, NaN padded).  Local to
-        the calling rank: no collective."""
+        the calling rank: no collective.  sweep: 'expand' (default) scores the expanded id rows with the ordinary forward;
+        'shared' does the fixed-field work once per context (equal to rounding, not bit for bit; ValueError for a shape it does
+        not serve); 'auto' picks 'shared' where it is served and N >= SWEEP_MIN_N."""
         import torch
         eng = self._ranking_engine()
         if candidates is None and self._train_split is None:
@@ -504,20 +528,22 @@ class CFFM(object):
         val_out = torch.empty((C, k), dtype=torch.float32, device=eng.device)
         group = max(1, int(score_rows) // N)
         cand64 = cand.long()
+        score = self._candidate_scorer(eng, sweep, N)
         for c0 in range(0, C, group):
             c1 = min(C, c0 + group)
-            scores = eng.score_candidates(ctx[c0:c1], int(field), cand)
+            scores = score(ctx[c0:c1], int(field), cand)
             idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
             ids_out[c0:c1] = torch.where(idx >= 0, cand64[idx.clamp(min=0).long()], cand64.new_full((), -1)).to(torch.int32)
             val_out[c0:c1] = val
         return ids_out.cpu().numpy(), val_out.cpu().numpy()
 
-    def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22):
+    def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22, sweep='expand'):
         """(HR@k, NDCG@k) of a split: for every row with label > 0 the context is the row and the target is the row's own id at
         column `field`, ranked among the candidates (default: the sorted distinct ids in column `field` over the train split and
         `data` together, so every target is a candidate).  Explicit candidates that lack a target raise ValueError.  The sweep
         stays on the device: scores, rank of the target, and the two sums and the count in float64; under a process group with
-        replicated tables every rank takes a contiguous share of the positive rows and the sums are all-reduced."""
+        replicated tables every rank takes a contiguous share of the positive rows and the sums are all-reduced.  sweep: as in
+        recommend()."""
         import torch
         eng = self._ranking_engine()
         ids, y, _ = self._device_split(data)
@@ -546,9 +572,10 @@ class CFFM(object):
         # [sum of hits, sum of gains, rows, NaN flag]: accumulated on the device, read once
         sums = torch.zeros(4, dtype=torch.float64, device=eng.device)
         group = max(1, int(score_rows) // N)
+        score = self._candidate_scorer(eng, sweep, N)
         for c0 in range(r0, r1, group):
             c1 = min(r1, c0 + group)
-            scores = eng.score_candidates(ctx[c0:c1], field, cand)
+            scores = score(ctx[c0:c1], field, cand)
             rank = eng.rank_of(scores, tpos[c0:c1]).double()
             hit = rank < k
             sums[0] += hit.sum()

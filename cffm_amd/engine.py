@@ -395,6 +395,37 @@ class HipEngine(object):
             hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
         return scores
 
+    def sweep_ok(self):
+        """True where score_candidates_shared serves this engine's shape (cffm_sweep_ok, include/cffm_hip.h)."""
+        return bool(self.lib.cffm_sweep_ok(self._s))
+
+    def score_candidates_shared(self, ctx, field, cand):
+        """The scores of score_candidates with the fixed-field work done once per context (cffm_score_sweep, csrc/sweep.hip):
+        same arguments, fp32 [C,N] on the device, equal to score_candidates to rounding (not bit for bit).  The per-context
+        scratch is kept in self._ws; the ordinary workspace is not touched and nothing synchronises.  ValueError for a shape the
+        sweep does not serve (sweep_ok())."""
+        ctx, cand = self._ids(ctx), self._ids(cand.reshape(-1))
+        F, N = int(self.cfg.F), int(cand.numel())
+        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
+            raise ValueError('contexts must be [C, %d] feature ids' % F)
+        if N < 1 or not 0 <= int(field) < F:
+            raise ValueError('score_candidates_shared: needs a candidate and 0 <= field < %d' % F)
+        C = int(ctx.shape[0])
+        if not self.sweep_ok():
+            raise ValueError('score_candidates_shared: the shared sweep does not serve this shape (both branches, D = 32, F <= 10)')
+        scores = torch.empty((C, N), dtype=torch.float32, device=self.device)
+        if C == 0:
+            return scores
+        key = 'sweep'
+        scratch = self._ws.get(key)
+        nbytes = int(self.lib.cffm_sweep_scratch_bytes(self._s, C))
+        if scratch is None or int(scratch.numel()) < nbytes:
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws[key] = scratch
+        hip.check(self.lib.cffm_score_sweep(self._s, self._t, _ptr(self.theta), _ptr(ctx), C, int(field), _ptr(cand), N, _ptr(scores),
+                                            N, _ptr(scratch), self._stream()))
+        return scores
+
     def _rank_args(self, scores, skip):
         if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
             raise ValueError('scores must be fp32 [C, N] with contiguous rows')

@@ -24,6 +24,7 @@ ABI_VERSION = 9
 MAX_LAYERS = 8
 NSLAB = 64
 HEAD_UNITS = 32
+SWEEP_CHUNK = 64            # CFFM_SWEEP_CHUNK: candidates of one (context, chunk) unit of cffm_score_sweep
 LOSS_IDS = {'square_loss': 0, 'mse': 1, 'mae': 2, 'log_loss': 3, 'hybrid': 5}
 OPT_IDS = {'AdagradOptimizer': 0, 'GradientDescentOptimizer': 1, 'MomentumOptimizer': 2, 'AdamOptimizer': 3}
 
@@ -121,6 +122,9 @@ PROTOTYPES = {
     'cffm_topk_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'cffm_topk': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     'cffm_rank_of': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    'cffm_sweep_ok': (C.c_int, [_SH]),
+    'cffm_sweep_scratch_bytes': (C.c_int64, [_SH, C.c_int32]),
+    'cffm_score_sweep': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, _P]),
     'cffm_probe_copy': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_read': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_mfma': (C.c_int, [_P, C.c_int32, _P, _P]),

@@ -404,6 +404,26 @@ int cffm_topk(const float *scores, int64_t row_stride, const uint8_t *skip, int6
 int cffm_rank_of(const float *scores, int64_t row_stride, const uint8_t *skip, int64_t skip_stride, int32_t C, int32_t N,
                  const int32_t *target, int32_t *rank_out, void *stream);
 
+/* ---- candidate sweep with the fixed-field work done once per context (cffm_amd/csrc/sweep.hip) -------
+ * Additive entry points: CFFM_ABI_VERSION stays 9, no existing signature, struct or kernel changes.
+ * cffm_score_sweep: scores[c * row_stride + n] (indexed in 64 bits) = the raw prediction of context row ctx[c] (int32 [C][F]) with its
+ * id at `field` replaced by cand[n] (int32 [N]): the value cffm_predict defines for that id row, to rounding (the sums run in
+ * another order), ids clamped the same way (< 0 -> 0, >= M -> M - 1).  Elements n >= N of a row are never written; the ordinary
+ * workspace is not touched; scratch: cffm_sweep_scratch_bytes(s, C) bytes (< 0: bad arguments or a shape that is not served; never
+ * smaller for a larger C).  A candidate's score does not depend on its position: the same id gives the same bits anywhere in cand,
+ * and on every call.  Workgroups take (context, chunk of CFFM_SWEEP_CHUNK candidates) units, so one context with many candidates
+ * fills the chip.
+ * Served domain (cffm_sweep_ok(s) == 1, host only): both branches on, D = 32, F <= 10 (Pp <= 48), every activation, linear_att 0 and 1,
+ * every K whose rows fit the two kernels' LDS next to their tiles (K = 64 at F = 10 does; K <= 2012 at most); D = 64 and F = 11 are not served.
+ * CFFM_ERR_UNSUPPORTED where cffm_sweep_ok(s) == 0: after the shape check, before any pointer is read.  CFFM_ERR_BAD_SHAPE, before the
+ * first launch or HIP call, for: a NULL pointer that would be read or written; field outside [0, F); N < 1; C < 0; row_stride < N.
+ * C == 0 returns 0 without a launch. */
+#define CFFM_SWEEP_CHUNK 64
+int cffm_sweep_ok(const cffm_shape_t *s);
+int64_t cffm_sweep_scratch_bytes(const cffm_shape_t *s, int32_t C);
+int cffm_score_sweep(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
+                     int32_t field, const int32_t *cand, int32_t N, float *scores, int64_t row_stride, void *scratch, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
