@@ -380,7 +380,7 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
         if (!s->inner_conv || !s->outer_conv) return CFFM_ERR_UNSUPPORTED;
         if ((rc = forward_impl(c, step_rows(tab, ids), y, st, fo))) return rc;
         if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-        return cffm_tables_adagrad_l2(c, tab, tab_acc, ids, (int64_t)B * s->F, st);
+        return cffm_tables_adagrad_l2(c, tab, tab_acc, (int64_t)B * s->F, st);
     }
     if (cffm_fwd_all_ok(s, B)) {                 // small-channel shapes: the whole forward (and the key sort) in one launch
         const bool later = defer_rank(s, B);
@@ -397,7 +397,7 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
     SortOpts so;
     so.prepacked = true;                         // the gather left the packed keys in ws.sort_keys
     if ((rc = cffm_sort_keys_impl(c, ids, (int64_t)B * s->F, so, st))) return rc;
-    return cffm_sparse_apply(c, tab, tab_acc, (int64_t)B * s->F, RowGrads::of_ws(c), LateScale{nullptr, 0.f, 0}, st);
+    return cffm_sparse_apply(c, tab, tab_acc, (int64_t)B * s->F, RowGrads::of_ws(c), LateScale::none(), st);
 }
 
 extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_state1,
@@ -420,5 +420,5 @@ extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* t
     bo.loss_out = loss;
     if (fo.no_materialise) bo.rows = step_rows(tab, ids);
     if ((rc = backward_impl(c, y, (int64_t)B, grad, st, bo))) return rc;
-    return cffm_apply_opt(c, tab, tab_state1, tab_state2, theta, theta_state1, theta_state2, grad, ids, (int64_t)B * s->F, step, st);
+    return cffm_apply_opt(c, tab, tab_state1, tab_state2, theta, theta_state1, theta_state2, grad, (int64_t)B * s->F, step, st);
 }

@@ -13,7 +13,10 @@ int cffm_gather_impl(const cffm_shape_t* s, const cffm_tables_t* t, const int32_
 struct ConvArgs; struct DgradArgs; struct WgradArgs; struct HeadArgs; struct HeadBwdArgs; struct InnerFwdArgs; struct InnerBwdArgs;
 struct SparseArgs; struct BwdOpts; struct RowGrads;
 // late 1/L of the data-parallel step (optim.hip); on == 0: none
-struct LateScale { const float* sum; float inv_Bg; int on; };
+struct LateScale {
+    const float* sum; float inv_Bg; int on;
+    static LateScale none() { return {nullptr, 0.f, 0}; }
+};
 int cffm_ws_layout_from(const cffm_shape_t* s, int32_t B, const cffm_theta_layout_t& tl, const SlabPlan& sp, cffm_ws_layout_t* out);
 struct StepCtx {
     const cffm_shape_t* s;
@@ -41,8 +44,8 @@ struct StepCtx {
     // keys in the workspace
     InnerFwdArgs inner_fwd_args(const cffm_tables_t* tab = nullptr, const int32_t* ids = nullptr) const;
     InnerBwdArgs inner_bwd_args(int* nslab) const;       // *nslab: slabs of the inner range (= workgroups of the kernel)
-    // segment-sum + Adagrad sweep over the n_rows sorted keys in ws.sort_vals
-    SparseArgs sparse_args(const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r, const LateScale& ls) const;
+    // the segment walk over the n_rows sorted keys in ws.sort_vals, row gradients at r
+    SparseArgs sparse_args(int64_t n_rows, const RowGrads& r) const;
 };
 // The per-slot row gradients a table update or a packing kernel reads.  dEi / dEo == NULL: that branch is disabled (CFFM.py:301,
 // :348) - it has no table, nothing is applied and its columns travel as zeros.  s*: floats between consecutive slots.
@@ -133,11 +136,10 @@ bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B);
 int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t* ids, const float* y, hipStream_t st,
                       bool rank_keys);
 // CFFM_LOSS_SQUARE_L2: tables updated densely with g = scatter(row grads) + lamda * w (feature_bias stays sparse)
-int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids, int64_t n_rows,
-                           hipStream_t st);
+int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, hipStream_t st);
 // SGD / Momentum / Adam updates of theta and the three tables from grad + the row gradients in ws (CFFM.py:519-529)
 int cffm_apply_opt(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
-                   float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, int64_t step, hipStream_t st);
+                   float* th1, float* th2, const float* grad, int64_t n_rows, int64_t step, hipStream_t st);
 
 // ---- wide shapes (Pp > 64): rows consumed where they are fetched, nothing materialised (RowSrc, common.hpp) ---------------
 bool cffm_wide_regather_ok(const cffm_shape_t* s);

@@ -73,22 +73,70 @@ __device__ __forceinline__ float late_scale(const LateScale& ls) {
     return ls.on ? 1.f / sqrtf(ls.sum[0] * ls.inv_Bg + 1e-10f) : 1.f;
 }
 
-__device__ __forceinline__ void dense_adagrad_body(int bid, float* __restrict__ v, float* __restrict__ acc,
-                                                   const float* __restrict__ grad, int64_t n, float lr, const LateScale& ls,
-                                                   float* __restrict__ loss_out) {
+// ---- the update rules: rule(w, s1, s2, g) moves one weight (in memory) and its slots by the gradient g ---------------------
+// A rule is a template parameter of every body and kernel below, so the Adagrad instantiations carry no branch on the optimizer.
+// slot(): the rule reads s1 (a NULL slot pointer is never formed from a table the caller did not pass).
+struct AdagradRule {
+    float lr;
+    __device__ __forceinline__ bool slot() const { return true; }
+    __device__ __forceinline__ void operator()(float& w, float* s1, float*, float g) const {
+        const float a = *s1 + g * g;
+        *s1 = a;
+        w -= lr * g / sqrtf(a);
+    }
+};
+
+// the other optimizers of CFFM.py:519-529 (TF-1.14 semantics), switched at run time on OptConst::opt
+struct OptConst { int opt; float lr, lr_t, b1, b2, omb1, omb2, eps, mom; };   // omb* = 1 - beta, rounded once from double
+
+__device__ __forceinline__ void opt_update(float& w, float* s1, float* s2, float g, const OptConst& c) {
+    if (c.opt == CFFM_OPT_SGD) {
+        w -= c.lr * g;
+    } else if (c.opt == CFFM_OPT_MOMENTUM) {
+        const float a = c.mom * (*s1) + g;
+        *s1 = a;
+        w -= c.lr * a;
+    } else {                                      // Adam
+        const float m = c.b1 * (*s1) + c.omb1 * g;
+        const float v = c.b2 * (*s2) + c.omb2 * g * g;
+        *s1 = m; *s2 = v;
+        w -= c.lr_t * m / (sqrtf(v) + c.eps);
+    }
+}
+
+struct OptRule {
+    OptConst c;
+    __device__ __forceinline__ bool slot() const { return c.opt == CFFM_OPT_MOMENTUM; }    // (Adam only runs in dense_opt_kernel)
+    __device__ __forceinline__ void operator()(float& w, float* s1, float* s2, float g) const {
+        float wv = w;                             // the weight is read before the slots are written
+        opt_update(wv, s1, s2, g, c);
+        w = wv;
+    }
+};
+
+// the constants of CFFM.py:519-529, for the single-GPU step and the multi-GPU apply alike (step >= 1; only Adam reads lr_t)
+static OptRule opt_rule(const cffm_shape_t* s, int64_t step) {
+    OptConst c;
+    c.opt = s->optimizer; c.lr = s->lr; c.b1 = 0.9f; c.b2 = 0.999f; c.omb1 = (float)(1.0 - 0.9); c.omb2 = (float)(1.0 - 0.999); c.eps = 1e-8f; c.mom = 0.95f;
+    c.lr_t = (float)((double)s->lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
+    return OptRule{c};
+}
+
+// dense rule on theta with the late 1/L; thread 0 also writes the loss of the global batch
+template <class Rule>
+__device__ __forceinline__ void dense_late_body(int bid, float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                int64_t n, const Rule& rule, const LateScale& ls, float* __restrict__ loss_out) {
     const int64_t i = (int64_t)bid * 256 + threadIdx.x;
     if (i == 0 && loss_out != nullptr) loss_out[0] = ls.on ? sqrtf(ls.sum[0] * ls.inv_Bg + 1e-10f) : ls.sum[0] * ls.inv_Bg;
     if (i >= n) return;
     const float g = grad[i] * late_scale(ls);
-    const float a = acc[i] + g * g;
-    acc[i] = a;
-    v[i] -= lr * g / sqrtf(a);
+    rule(v[i], rule.slot() ? s1 + i : nullptr, nullptr, g);
 }
 
-__global__ __launch_bounds__(256) void dense_adagrad_kernel(float* __restrict__ v, float* __restrict__ acc,
-                                                            const float* __restrict__ grad, int64_t n, float lr,
-                                                            LateScale ls, float* __restrict__ loss_out) {
-    dense_adagrad_body(blockIdx.x, v, acc, grad, n, lr, ls, loss_out);
+template <class Rule>
+__global__ __launch_bounds__(256) void dense_late_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                         int64_t n, Rule rule, LateScale ls, float* __restrict__ loss_out) {
+    dense_late_body(blockIdx.x, v, s1, grad, n, rule, ls, loss_out);
 }
 
 // Sorted order of n <= 8192 unique keys (id << 32 | slot) without a sort: the place of a key is the number of keys below
@@ -171,21 +219,24 @@ __device__ __forceinline__ void merge_runs_body(int wg, const MergeArgs& a, unsi
     a.out[rank] = ((unsigned long long)id << 32) | (unsigned long long)(unsigned)(r * a.m + (int)(k & 0xffffffffull));
 }
 
-__global__ __launch_bounds__(256) void dp_head_merge_kernel(float* __restrict__ v, float* __restrict__ acc, const float* __restrict__ grad,
-                                                            int64_t n, float lr, LateScale ls, float* __restrict__ loss_out,
+// first launch of the data-parallel apply, sorted runs: dense rule with the late 1/L ∥ merge of the per-rank runs
+template <class Rule>
+__global__ __launch_bounds__(256) void dp_head_merge_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                            int64_t n, Rule rule, LateScale ls, float* __restrict__ loss_out,
                                                             int n_dense, MergeArgs ma) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < n_dense) dense_adagrad_body(blockIdx.x, v, acc, grad, n, lr, ls, loss_out);
+    if ((int)blockIdx.x < n_dense) dense_late_body(blockIdx.x, v, s1, grad, n, rule, ls, loss_out);
     else merge_runs_body(blockIdx.x - n_dense, ma, reinterpret_cast<unsigned*>(smem));
 }
 
-// first launch of cffm_dp_apply: dense Adagrad with the late 1/L ∥ placement of the gathered keys
-__global__ __launch_bounds__(256) void dp_head_kernel(float* __restrict__ v, float* __restrict__ acc, const float* __restrict__ grad,
-                                                      int64_t n, float lr, LateScale ls, float* __restrict__ loss_out, int n_dense,
+// first launch of the data-parallel apply, n_rows <= 8192 without runs: dense rule with the late 1/L ∥ placement of the gathered keys
+template <class Rule>
+__global__ __launch_bounds__(256) void dp_head_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
+                                                      int64_t n, Rule rule, LateScale ls, float* __restrict__ loss_out, int n_dense,
                                                       const int32_t* __restrict__ ids, int64_t id_stride, int n_keys, int n_rank,
                                                       unsigned long long* __restrict__ keys_out) {
     __shared__ float cnt[4 * RANK_KPW_MAX];
-    if ((int)blockIdx.x < n_dense) dense_adagrad_body(blockIdx.x, v, acc, grad, n, lr, ls, loss_out);
+    if ((int)blockIdx.x < n_dense) dense_late_body(blockIdx.x, v, s1, grad, n, rule, ls, loss_out);
     else rank_place_body(blockIdx.x - n_dense, n_rank, ids, id_stride, n_keys, keys_out, cnt);
 }
 
@@ -270,34 +321,40 @@ __global__ __launch_bounds__(256) void small_sort_kernel(const unsigned long lon
     small_sort_body(in, nullptr, out, n, id_bits, smem);
 }
 
-// one wavefront per sorted position; only segment heads do work
+// ---- the segment walk ---------------------------------------------------------------------------------------------------------
+// One wavefront per sorted position of the keys (id << 32 | slot); only segment heads work.  Each lane owns the columns lane,
+// lane + 64, ... of the row (inner | outer | bias; a disabled branch, dEi / dEo == NULL, has none) and sums each over the duplicates
+// of the id in slot order - ascending sorted position, one accumulator per column starting from 0.f: every "bitwise reproducible"
+// of DESIGN.md rests on this order - then hands (id, table, column within the table) and the sum to the sink: sink.at() locates the
+// element, under the walk's own column comparison so that the table is a constant there, and sink(at, sum) does the one thing
+// that is done with it.  Ids outside [0, M) (keyed as M, see pack_keys_kernel) are skipped.  Slot s reads its gradients at s * sE* of RowGrads; run_len > 0: slot s lives in block
+// s / run_len at local index s % run_len, and blocks are run_stride floats apart (the per-rank runs of the data-parallel apply).
 struct SparseArgs {
     const unsigned long long* keys;
     int64_t n;
     int M, K, D;
     const float *dEi, *dEo, *dfb;
-    float *inner, *outer, *fbias, *a_inner, *a_outer, *a_fbias;
-    float lr;
     int64_t sEi, sEo, sfb;
-    LateScale ls;
-    int run_len;            // > 0: slot s lives in block s / run_len at local index s % run_len; blocks are run_stride floats apart
+    int run_len;
     int64_t run_stride;
     float inv_run_len;
 };
+enum { T_INNER = 0, T_OUTER = 1, T_BIAS = 2 };
+static const cffm_tables_t NO_TABLES = {nullptr, nullptr, nullptr};
 
-__device__ __forceinline__ void sparse_adagrad_body(int bid, const SparseArgs& a) {
+template <class Sink>
+__device__ __forceinline__ void segment_walk(int bid, const SparseArgs& a, const Sink& sink) {
     const unsigned long long* __restrict__ keys = a.keys;
     const int64_t n = a.n;
     const int M = a.M, K = a.K, D = a.D;
     const float* __restrict__ dEi = a.dEi; const float* __restrict__ dEo = a.dEo; const float* __restrict__ dfb = a.dfb;
-    const float gscale = late_scale(a.ls);
     const int64_t pos = (int64_t)bid * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (pos >= n) return;
     const int id = (int)(keys[pos] >> 32);
     if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;          // not a segment head
     if (id < 0 || id >= M) return;
-    const int W = (dEi ? K : 0) + (dEo ? D : 0) + 1;     // columns: inner | outer | bias
+    const int W = (dEi ? K : 0) + (dEo ? D : 0) + 1;
     const int Ki = dEi ? K : 0;
     for (int c0 = 0; c0 < W; c0 += 64) {
         const int c = c0 + lane;
@@ -315,31 +372,89 @@ __device__ __forceinline__ void sparse_adagrad_body(int bid, const SparseArgs& a
                 }
                 g += c < Ki ? dEi[boff + sl * a.sEi + c] : (c < W - 1 ? dEo[boff + sl * a.sEo + (c - Ki)] : dfb[boff + sl * a.sfb]);
             }
-            g *= gscale;
-            float *vp, *ap;
-            if (c < Ki) { vp = a.inner + (int64_t)id * K + c; ap = a.a_inner + (int64_t)id * K + c; }
-            else if (c < W - 1) { vp = a.outer + (int64_t)id * D + (c - Ki); ap = a.a_outer + (int64_t)id * D + (c - Ki); }
-            else { vp = a.fbias + id; ap = a.a_fbias + id; }
-            const float acc = *ap + g * g;
-            *ap = acc;
-            *vp -= a.lr * g / sqrtf(acc);
+            typename Sink::At at;
+            if (c < Ki) at = sink.at(id, T_INNER, c);
+            else if (c < W - 1) at = sink.at(id, T_OUTER, c - Ki);
+            else at = sink.at(id, T_BIAS, 0);
+            sink(at, g);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void sparse_adagrad_kernel(SparseArgs a) { sparse_adagrad_body(blockIdx.x, a); }
+// the sinks: At at(id, table, col) and operator()(at, sum).  Element (id, col) of table t of a [M][K] | [M][D] | [M] triple is table_of(T, t)[row_off(..)]:
+__device__ __forceinline__ int64_t row_off(int K, int D, int id, int t, int col) {
+    if (t == T_INNER) return (int64_t)id * K + col;
+    if (t == T_OUTER) return (int64_t)id * D + col;
+    return id;
+}
+__device__ __forceinline__ float* table_of(const cffm_tables_t& T, int t) {
+    if (t == T_INNER) return T.inner_emb;
+    if (t == T_OUTER) return T.outer_emb;
+    return T.feat_bias;
+}
+// apply the rule to the row and its slot row (s.* is not read where the rule keeps no slot); LATE: the sum is first scaled by the late 1/L
+template <class Rule, bool LATE>
+struct ApplySink {
+    cffm_tables_t w, s;
+    int K, D;
+    Rule rule;
+    float gscale = 1.f;           // LATE only
+    struct At { float *w, *s; };
+    __device__ __forceinline__ At at(int id, int t, int col) const {
+        const int64_t o = row_off(K, D, id, t, col);
+        return {table_of(w, t) + o, rule.slot() ? table_of(s, t) + o : nullptr};
+    }
+    __device__ __forceinline__ void operator()(const At& a, float g) const {
+        if (LATE) g *= gscale;
+        rule(*a.w, a.s, nullptr, g);
+    }
+};
+// store into the dense [M][K] | [M][D] | [M] gradient image
+struct StoreSink {
+    cffm_tables_t G;
+    int K, D;
+    typedef float* At;
+    __device__ __forceinline__ At at(int id, int t, int col) const { return table_of(G, t) + row_off(K, D, id, t, col); }
+    __device__ __forceinline__ void operator()(At a, float g) const { *a = g; }
+};
+// the tables of store_mask (bit t = table t) have a dense gradient (Adam's non-lazy sparse apply; the regularised loss): their
+// sums go to G* and dense_opt_kernel sweeps every row; the others are applied here, with no late scale
+template <class Rule>
+struct MixSink {
+    ApplySink<Rule, false> apply;
+    StoreSink store;
+    int store_mask;
+    struct At { typename ApplySink<Rule, false>::At a; float* G; };
+    __device__ __forceinline__ At at(int id, int t, int col) const {
+        if ((store_mask >> t) & 1) return {{nullptr, nullptr}, store.at(id, t, col)};
+        return {apply.at(id, t, col), nullptr};
+    }
+    __device__ __forceinline__ void operator()(const At& a, float g) const {
+        if (a.G) store(a.G, g);
+        else apply(a.a, g);
+    }
+};
+
+// the tables and slots of a sparse update with the late 1/L (the host half of ApplySink<Rule, true>)
+struct ApplyArgs { cffm_tables_t w, s; LateScale ls; };
+template <class Rule>
+__device__ __forceinline__ void sparse_apply_body(int bid, const SparseArgs& a, const ApplyArgs& p, const Rule& rule) {
+    segment_walk(bid, a, ApplySink<Rule, true>{p.w, p.s, a.K, a.D, rule, late_scale(p.ls)});
+}
+template <class Rule>
+__global__ __launch_bounds__(256) void sparse_apply_kernel(SparseArgs a, ApplyArgs p, Rule rule) { sparse_apply_body(blockIdx.x, a, p, rule); }
 
 // The two halves of the update do not depend on each other (dense slabs vs table rows): one launch, two roles.
 __global__ __launch_bounds__(256) void update_all_kernel(const float* __restrict__ gpart, int64_t n, SlabPlan sp,
                                                          float* __restrict__ grad, float* __restrict__ theta,
-                                                         float* __restrict__ acc, float lr, int n_reduce, SparseArgs sa) {
+                                                         float* __restrict__ acc, float lr, int n_reduce, SparseArgs sa, ApplyArgs pa) {
     if ((int)blockIdx.x < n_reduce) {
         PHASE_MARKB(26, blockIdx.x);
         reduce_slabs_body(blockIdx.x, gpart, n, sp, grad, theta, acc, lr);
         PHASE_MARKB(27, blockIdx.x);
     } else {
         PHASE_MARKB(28, blockIdx.x - n_reduce);
-        sparse_adagrad_body(blockIdx.x - n_reduce, sa);
+        sparse_apply_body(blockIdx.x - n_reduce, sa, pa, AdagradRule{lr});
         PHASE_MARKB(29, blockIdx.x - n_reduce);
     }
 }
@@ -364,9 +479,8 @@ int cffm_reduce_slabs_impl(const StepCtx& c, float* grad, float* theta, float* a
 
 extern "C" int cffm_dense_adagrad(float* theta, float* acc, const float* grad, int64_t n, float lr, void* stream) {
     if (n <= 0) return 0;
-    LateScale ls = {nullptr, 0.f, 0};
-    hipLaunchKernelGGL(dense_adagrad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       theta, acc, grad, n, lr, ls, (float*)nullptr);
+    hipLaunchKernelGGL(dense_late_kernel<AdagradRule>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       theta, acc, grad, n, AdagradRule{lr}, LateScale::none(), (float*)nullptr);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -378,7 +492,7 @@ extern "C" int cffm_sparse_adagrad(const cffm_shape_t* s, const cffm_tables_t* t
     if (rc) return rc;
     const StepCtx c(s, B_ws, nullptr, ws);               // (the sort returns before it touches the workspace where B_ws < 1)
     if ((rc = cffm_sort_keys_impl(c, ids, n_rows, SortOpts(), (hipStream_t)stream))) return rc;
-    return cffm_sparse_apply(c, tab, acc, n_rows, RowGrads{dEi, dEo, dfb, s->K, s->D, 1}, LateScale{nullptr, 0.f, 0}, (hipStream_t)stream);
+    return cffm_sparse_apply(c, tab, acc, n_rows, RowGrads{dEi, dEo, dfb, s->K, s->D, 1}, LateScale::none(), (hipStream_t)stream);
 }
 
 int cffm_sort_keys_impl(const StepCtx& c, const int32_t* ids, int64_t n_rows, const SortOpts& o, hipStream_t st) {
@@ -412,23 +526,20 @@ int cffm_sort_keys_impl(const StepCtx& c, const int32_t* ids, int64_t n_rows, co
     return e == hipSuccess ? 0 : (int)e;
 }
 
-SparseArgs StepCtx::sparse_args(const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r,
-                                const LateScale& ls) const {
-    SparseArgs a{};                       // run_len = 0: the slots address one array (cffm_dp_apply sets the run members for its blocks)
+SparseArgs StepCtx::sparse_args(int64_t n_rows, const RowGrads& r) const {
+    SparseArgs a{};                       // run_len = 0: the slots address one array (dp_apply sets the run members for its blocks)
     a.keys = at<const unsigned long long>(wl.sort_vals);
     a.n = n_rows; a.M = s->M; a.K = s->K; a.D = s->D;
     a.dEi = r.dEi; a.dEo = r.dEo; a.dfb = r.dfb;
-    a.inner = tab->inner_emb; a.outer = tab->outer_emb; a.fbias = tab->feat_bias;
-    a.a_inner = acc->inner_emb; a.a_outer = acc->outer_emb; a.a_fbias = acc->feat_bias;
-    a.lr = s->lr; a.sEi = r.sEi; a.sEo = r.sEo; a.sfb = r.sfb; a.ls = ls;
+    a.sEi = r.sEi; a.sEo = r.sEo; a.sfb = r.sfb;
     return a;
 }
 
 int cffm_sparse_apply(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, const RowGrads& r,
                       const LateScale& ls, hipStream_t st) {
     if (n_rows <= 0) return 0;
-    const SparseArgs a = c.sparse_args(tab, acc, n_rows, r, ls);
-    hipLaunchKernelGGL(sparse_adagrad_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sparse_apply_kernel<AdagradRule>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, c.sparse_args(n_rows, r),
+                       ApplyArgs{*tab, *acc, ls}, AdagradRule{c.s->lr});
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -437,10 +548,69 @@ int cffm_sparse_apply(const StepCtx& c, const cffm_tables_t* tab, const cffm_tab
 int cffm_update_all(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta, float* theta_acc,
                     float* grad, hipStream_t st) {
     const int64_t n_rows = (int64_t)c.B * c.s->F;
-    const SparseArgs a = c.sparse_args(tab, tab_acc, n_rows, RowGrads::of_ws(c), LateScale{nullptr, 0.f, 0});
     const int n_reduce = reduce_slab_wgs(c.tl.n);
     hipLaunchKernelGGL(update_all_kernel, dim3((unsigned)(n_reduce + (n_rows + 3) / 4)), dim3(256), 0, st,
-                       c.at<const float>(c.wl.gpart), (int64_t)c.tl.n, c.sp, grad, theta, theta_acc, c.s->lr, n_reduce, a);
+                       c.at<const float>(c.wl.gpart), (int64_t)c.tl.n, c.sp, grad, theta, theta_acc, c.s->lr, n_reduce,
+                       c.sparse_args(n_rows, RowGrads::of_ws(c)), ApplyArgs{*tab, *tab_acc, LateScale::none()});
+    CFFM_CHECK_LAUNCH();
+    return 0;
+}
+
+// Data-parallel apply (cffm_amd/dist.py): grad_sum = all-reduced [theta.n gradients | pad | loss-term sum at index
+// theta.n], rows = all-gathered packed rows [n_rows][1 + K + D + 1] = (id bits | dEi | dEo | dfb).
+// What both entry points do after their own refusals, for a rule that is, like Adagrad, a dense rule on theta and a
+// duplicates-summed-first rule on the looked-up rows only (TF does not decay the Momentum accumulator of a row nobody looked up):
+// dense rule with the late 1/L ∥ key placement or run merge (or the radix sort), then the segment walk with the applying sink.
+// Every check comes before the first launch: a refused call has launched nothing.  slot / th1: the rule's first slot (NULL: none kept).
+template <class Rule>
+static int dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* slot, float* theta, float* th1,
+                    const float* grad_sum, int64_t B_global, const float* rows, int64_t n_rows, void* ws, int32_t B_ws, float* loss_out,
+                    int32_t n_runs, const Rule& rule, bool needs_slot, hipStream_t st) {
+    int rc;
+    if (n_runs > 0) {
+        // sorted runs (one per rank, from cffm_dp_local): merge by rank, rows addressed block-wise
+        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > CFFM_LDS_SHARED_CU) return CFFM_ERR_BAD_SHAPE;
+        const int64_t m = n_rows / n_runs;
+        if (m % s->F || !cffm_fwd_all_ok(s, (int32_t)(m / s->F))) return CFFM_ERR_UNSUPPORTED;      // the runs only exist on that path
+    } else if (n_rows > 0 && n_rows > (int64_t)B_ws * s->F) {
+        return CFFM_ERR_BAD_SHAPE;
+    }
+    if (!tab || !theta || !grad_sum || (n_rows > 0 && (!rows || !ws)) || (needs_slot && (!slot || !th1))) return CFFM_ERR_BAD_SHAPE;
+    // B_ws < 1: n_rows <= 0 here, and nothing below touches the workspace
+    const StepCtx c(s, B_ws, theta, ws);
+    const cffm_theta_layout_t& tl = c.tl;
+    const LateScale ls = {grad_sum + tl.n, 1.f / (float)B_global, s->loss == CFFM_LOSS_SQUARE_RMSE ? 1 : 0};
+    const int64_t W = 1 + s->K + s->D + 1;
+    const int n_dense = (int)((tl.n + 255) / 256);
+    SparseArgs a = c.sparse_args(n_rows, RowGrads::packed(s, rows, W));
+    if (n_runs > 0) {
+        const int m = (int)(n_rows / n_runs);
+        MergeArgs ma;
+        ma.rows = rows; ma.block_floats = (int64_t)m * (W + 2); ma.keys_off = (int64_t)m * W; ma.m = m; ma.n_runs = n_runs;
+        ma.out = c.at<unsigned long long>(c.wl.sort_vals);
+        const size_t lds = (size_t)n_rows * 4;
+        if ((rc = set_lds(dp_head_merge_kernel<Rule>, lds))) return rc;
+        hipLaunchKernelGGL(dp_head_merge_kernel<Rule>, dim3(n_dense + (unsigned)((n_rows + 255) / 256)), dim3(256), lds, st, theta, th1,
+                           grad_sum, (int64_t)tl.n, rule, ls, loss_out, n_dense, ma);
+        CFFM_CHECK_LAUNCH();
+        a.run_len = m; a.run_stride = ma.block_floats; a.inv_run_len = 1.f / (float)m;
+    } else if (n_rows > 0 && n_rows <= 8192) {
+        // dense update and key placement are independent: one launch, two roles
+        const int n_rank = 256;                              // kpw = ceil(n_rows / 256) <= 32 keys per workgroup
+        hipLaunchKernelGGL(dp_head_kernel<Rule>, dim3(n_dense + n_rank), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, rule, ls,
+                           loss_out, n_dense, (const int32_t*)rows, W, (int)n_rows, n_rank, c.at<unsigned long long>(c.wl.sort_vals));
+        CFFM_CHECK_LAUNCH();
+    } else {
+        hipLaunchKernelGGL(dense_late_kernel<Rule>, dim3((unsigned)n_dense), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, rule,
+                           ls, loss_out);
+        CFFM_CHECK_LAUNCH();
+        if (n_rows <= 0) return 0;
+        SortOpts so;
+        so.id_stride = W;                                    // the id column of the rows
+        if ((rc = cffm_sort_keys_impl(c, (const int32_t*)rows, n_rows, so, st))) return rc;
+    }
+    hipLaunchKernelGGL(sparse_apply_kernel<Rule>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a,
+                       ApplyArgs{*tab, needs_slot ? *slot : NO_TABLES, ls}, rule);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -452,50 +622,24 @@ extern "C" int cffm_dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, co
                              int64_t n_rows, void* ws, int32_t B_ws, float* loss_out, int32_t n_runs, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
-    if (s->optimizer != CFFM_OPT_ADAGRAD) return CFFM_ERR_UNSUPPORTED;    // the data-parallel update is Adagrad only
-    hipStream_t st = (hipStream_t)stream;
-    // B_ws < 1: every path that touches the workspace refuses (n_rows > B_ws * F) or has nothing to do (n_rows <= 0) before it would
-    const StepCtx c(s, B_ws, theta, ws);
-    const cffm_theta_layout_t& tl = c.tl;
-    LateScale ls = {grad_sum + tl.n, 1.f / (float)B_global, s->loss == CFFM_LOSS_SQUARE_RMSE ? 1 : 0};
-    const int64_t W = 1 + s->K + s->D + 1;
-    const RowGrads rg = RowGrads::packed(s, rows, W);
-    const int n_dense = (int)((tl.n + 255) / 256);
-    if (n_runs > 0) {
-        // sorted runs (one per rank, from cffm_dp_local): merge by rank, rows addressed block-wise
-        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > CFFM_LDS_SHARED_CU) return CFFM_ERR_BAD_SHAPE;
-        const int m = (int)(n_rows / n_runs);
-        if (m % s->F || !cffm_fwd_all_ok(s, m / s->F)) return CFFM_ERR_UNSUPPORTED;      // the runs only exist on that path
-        MergeArgs ma;
-        ma.rows = rows; ma.block_floats = (int64_t)m * (W + 2); ma.keys_off = (int64_t)m * W; ma.m = m; ma.n_runs = n_runs;
-        ma.out = c.at<unsigned long long>(c.wl.sort_vals);
-        const size_t lds = (size_t)n_rows * 4;
-        if ((rc = set_lds(dp_head_merge_kernel, lds))) return rc;
-        hipLaunchKernelGGL(dp_head_merge_kernel, dim3(n_dense + (unsigned)((n_rows + 255) / 256)), dim3(256), lds, st, theta, theta_acc,
-                           grad_sum, (int64_t)tl.n, s->lr, ls, loss_out, n_dense, ma);
-        CFFM_CHECK_LAUNCH();
-        SparseArgs a = c.sparse_args(tab, acc, n_rows, rg, ls);
-        a.run_len = m; a.run_stride = ma.block_floats; a.inv_run_len = 1.f / (float)m;
-        hipLaunchKernelGGL(sparse_adagrad_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a);
-        CFFM_CHECK_LAUNCH();
-        return 0;
-    }
-    if (n_rows > 0 && n_rows <= 8192 && n_rows <= (int64_t)B_ws * s->F) {
-        // dense update and key placement are independent: one launch, two roles
-        const int n_rank = 256;                              // kpw = ceil(n_rows / 256) <= 32 keys per workgroup
-        hipLaunchKernelGGL(dp_head_kernel, dim3(n_dense + n_rank), dim3(256), 0, st, theta, theta_acc, grad_sum, (int64_t)tl.n,
-                           s->lr, ls, loss_out, n_dense, (const int32_t*)rows, W, (int)n_rows, n_rank,
-                           c.at<unsigned long long>(c.wl.sort_vals));
-        CFFM_CHECK_LAUNCH();
-    } else {
-        hipLaunchKernelGGL(dense_adagrad_kernel, dim3((unsigned)n_dense), dim3(256), 0, st, theta, theta_acc, grad_sum,
-                           (int64_t)tl.n, s->lr, ls, loss_out);
-        CFFM_CHECK_LAUNCH();
-        SortOpts so;
-        so.id_stride = W;                                    // the id column of the rows
-        if ((rc = cffm_sort_keys_impl(c, (const int32_t*)rows, n_rows, so, st))) return rc;
-    }
-    return cffm_sparse_apply(c, tab, acc, n_rows, rg, ls, st);
+    if (s->optimizer != CFFM_OPT_ADAGRAD) return CFFM_ERR_UNSUPPORTED;    // the other rules: cffm_dp_apply_opt
+    return dp_apply(s, tab, acc, theta, theta_acc, grad_sum, B_global, rows, n_rows, ws, B_ws, loss_out, n_runs, AdagradRule{s->lr}, true,
+                    (hipStream_t)stream);
+}
+
+// SGD and Momentum for the data-parallel and row-sharded steps (acc / theta_acc = the Momentum accumulators; SGD reads neither).
+// Adam is not here: TF's sparse Adam is non-lazy (every row of every table moves every step).
+extern "C" int cffm_dp_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, float* theta,
+                                 float* theta_acc, const float* grad_sum, int64_t B_global, const float* rows,
+                                 int64_t n_rows, void* ws, int32_t B_ws, float* loss_out, int32_t n_runs, void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (s->optimizer == CFFM_OPT_ADAGRAD)
+        return cffm_dp_apply(s, tab, acc, theta, theta_acc, grad_sum, B_global, rows, n_rows, ws, B_ws, loss_out, n_runs, stream);
+    if (s->optimizer == CFFM_OPT_ADAM) return CFFM_ERR_UNSUPPORTED;       // non-lazy: a dense sweep of every table, not this design
+    const bool mom = s->optimizer == CFFM_OPT_MOMENTUM;
+    return dp_apply(s, tab, acc, theta, mom ? theta_acc : nullptr, grad_sum, B_global, rows, n_rows, ws, B_ws, loss_out, n_runs,
+                    opt_rule(s, 1), mom, (hipStream_t)stream);
 }
 
 // ---- data-parallel step for SMALL vocabularies: the tables' gradients travel as one dense buffer --------------------
@@ -506,67 +650,37 @@ extern "C" int cffm_dp_apply(const cffm_shape_t* s, const cffm_tables_t* tab, co
 // semantics without a mask.  flat = [theta.n gradients | loss sum | pad to n4 | Gi M*K | Go M*D | Gfb M].
 static inline int64_t dp_dense_table_off(const cffm_theta_layout_t& tl) { return ((int64_t)tl.n + 4 + 3) / 4 * 4; }
 
-struct ScatterArgs {
-    const unsigned long long* keys;   // this rank's sorted keys
-    int64_t n;
-    int M, K, D, B;
-    const float *dEi, *dEo, *dfb, *sqerr;
-    float *Gi, *Go, *Gfb, *sum_dst, *scalars;
-};
-__device__ __forceinline__ void scatter_rows_body(int bid, const ScatterArgs& a, float* red) {
-    if (bid == 0) {                                  // role 0 of this range: loss-term sum of this rank, fixed order
-        float part = 0.f;
-        for (int i = threadIdx.x; i < a.B; i += 256) part += a.sqerr[i];
-        const float sum = block_sum(part, red);
-        if (threadIdx.x == 0) { a.sum_dst[0] = sum; a.scalars[0] = sum; }
-        return;
-    }
-    const int64_t pos = (int64_t)(bid - 1) * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pos >= a.n) return;
-    const int id = (int)(a.keys[pos] >> 32);
-    if (pos > 0 && (int)(a.keys[pos - 1] >> 32) == id) return;
-    if (id < 0 || id >= a.M) return;
-    const int K = a.K, D = a.D, W = K + D + 1;
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int c = c0 + lane;
-        if (c >= W) continue;
-        float g = 0.f;
-        for (int64_t q = pos; q < a.n; ++q) {
-            const unsigned long long kq = a.keys[q];
-            if ((int)(kq >> 32) != id) break;
-            const int64_t sl = (int64_t)(kq & 0xffffffffull);
-            g += c < K ? a.dEi[sl * K + c] : (c < K + D ? a.dEo[sl * D + (c - K)] : a.dfb[sl]);
-        }
-        if (c < K) a.Gi[(int64_t)id * K + c] = g;
-        else if (c < K + D) a.Go[(int64_t)id * D + (c - K)] = g;
-        else a.Gfb[id] = g;
-    }
-}
+struct LossSumArgs { const float* sqerr; int B; float *sum_dst, *scalars; };
 __global__ __launch_bounds__(256) void dp_tail_dense_kernel(const float* __restrict__ gpart, int64_t n, SlabPlan sp,
-                                                            float* __restrict__ grad, int n_reduce, ScatterArgs sa) {
+                                                            float* __restrict__ grad, int n_reduce, SparseArgs sa, StoreSink sink,
+                                                            LossSumArgs l) {
     __shared__ float red[4];
-    if ((int)blockIdx.x < n_reduce) reduce_slabs_body(blockIdx.x, gpart, n, sp, grad, nullptr, nullptr, 0.f);
-    else scatter_rows_body(blockIdx.x - n_reduce, sa, red);
+    const int bid = blockIdx.x - n_reduce;
+    if (bid < 0) {
+        reduce_slabs_body(blockIdx.x, gpart, n, sp, grad, nullptr, nullptr, 0.f);
+    } else if (bid == 0) {                           // loss-term sum of this rank, fixed order
+        float part = 0.f;
+        for (int i = threadIdx.x; i < l.B; i += 256) part += l.sqerr[i];
+        const float sum = block_sum(part, red);
+        if (threadIdx.x == 0) { l.sum_dst[0] = sum; l.scalars[0] = sum; }
+    } else {
+        segment_walk(bid - 1, sa, sink);
+    }
 }
 
 int cffm_dp_tail_dense(const StepCtx& c, float* flat, hipStream_t st) {
     const cffm_shape_t* s = c.s;
     const cffm_theta_layout_t& tl = c.tl;
     const cffm_ws_layout_t& wl = c.wl;
-    const int64_t toff = dp_dense_table_off(tl);
-    const RowGrads r = RowGrads::of_ws(c);           // both branches are on (cffm_fwd_all_ok)
-    ScatterArgs sa;
-    sa.keys = c.at<const unsigned long long>(wl.sort_vals); sa.n = (int64_t)c.B * s->F;
-    sa.M = s->M; sa.K = s->K; sa.D = s->D; sa.B = c.B;
-    sa.dEi = r.dEi; sa.dEo = r.dEo; sa.dfb = r.dfb;
-    sa.sqerr = c.at<const float>(wl.sqerr);
-    sa.Gi = flat + toff; sa.Go = sa.Gi + (int64_t)s->M * s->K; sa.Gfb = sa.Go + (int64_t)s->M * s->D;
-    sa.sum_dst = flat + tl.n; sa.scalars = c.at(wl.scalars);
+    const int64_t n_rows = (int64_t)c.B * s->F;
+    float* Gi = flat + dp_dense_table_off(tl);
+    float* Go = Gi + (int64_t)s->M * s->K;
+    const StoreSink sink = {{Gi, Go, Go + (int64_t)s->M * s->D}, s->K, s->D};
+    const LossSumArgs l = {c.at<const float>(wl.sqerr), c.B, flat + tl.n, c.at(wl.scalars)};
     const int n_reduce = reduce_slab_wgs(tl.n);
-    const int n_scatter = 1 + (int)((sa.n + 3) / 4);
+    const int n_scatter = 1 + (int)((n_rows + 3) / 4);
     hipLaunchKernelGGL(dp_tail_dense_kernel, dim3(n_reduce + n_scatter), dim3(256), 0, st, c.at<const float>(wl.gpart),
-                       (int64_t)tl.n, c.sp, flat, n_reduce, sa);
+                       (int64_t)tl.n, c.sp, flat, n_reduce, c.sparse_args(n_rows, RowGrads::of_ws(c)), sink, l);   // both branches are on (cffm_fwd_all_ok)
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -575,7 +689,8 @@ struct DenseTableArgs { float *w[3], *a[3]; float* g[3]; int64_t n[3]; };
 __global__ __launch_bounds__(256) void dp_apply_dense_kernel(float* __restrict__ v, float* __restrict__ acc, const float* __restrict__ grad,
                                                              int64_t n, float lr, LateScale ls, float* __restrict__ loss_out, int n_dense,
                                                              DenseTableArgs t) {
-    if ((int)blockIdx.x < n_dense) { dense_adagrad_body(blockIdx.x, v, acc, grad, n, lr, ls, loss_out); return; }
+    const AdagradRule rule = {lr};
+    if ((int)blockIdx.x < n_dense) { dense_late_body(blockIdx.x, v, acc, grad, n, rule, ls, loss_out); return; }
     int64_t i = (int64_t)(blockIdx.x - n_dense) * 256 + threadIdx.x;
     const float gs = late_scale(ls);
 #pragma unroll
@@ -583,9 +698,7 @@ __global__ __launch_bounds__(256) void dp_apply_dense_kernel(float* __restrict__
         if (i < t.n[k]) {
             const float g = t.g[k][i] * gs;
             t.g[k][i] = 0.f;                                 // zero on exit: the next step's scatter finds a clean image (no memset)
-            const float a = t.a[k][i] + g * g;               // g == 0 (row not looked up by any rank): a and w unchanged
-            t.a[k][i] = a;
-            t.w[k][i] -= lr * g / sqrtf(a);
+            rule(t.w[k][i], t.a[k] + i, nullptr, g);         // g == 0 (row not looked up by any rank): a and w unchanged
             return;
         }
         i -= t.n[k];
@@ -622,345 +735,71 @@ extern "C" int cffm_dp_apply_dense(const cffm_shape_t* s, const cffm_tables_t* t
     return 0;
 }
 
-// ---- regularised square loss (CFFM.py:489-491): the l2 terms make the table gradients dense ------------------------
-// 1) segment heads of the sorted keys write the duplicates-summed row gradients into zeroed dense buffers Gi/Go and
-//    apply the (still sparse) feature_bias update; 2) a dense sweep applies Adagrad with g = G + lamda * w to every row.
-__global__ __launch_bounds__(256) void scatter_rows_l2_kernel(const unsigned long long* __restrict__ keys, int64_t n, int M,
-                                                              int K, int D, const float* __restrict__ dEi,
-                                                              const float* __restrict__ dEo, const float* __restrict__ dfb,
-                                                              float* __restrict__ Gi, float* __restrict__ Go,
-                                                              float* __restrict__ fbias, float* __restrict__ a_fbias, float lr) {
-    const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pos >= n) return;
-    const int id = (int)(keys[pos] >> 32);
-    if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;
-    if (id < 0 || id >= M) return;
-    const int W = K + D + 1;
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int c = c0 + lane;
-        if (c >= W) continue;
-        float g = 0.f;
-        for (int64_t q = pos; q < n; ++q) {
-            const unsigned long long kq = keys[q];
-            if ((int)(kq >> 32) != id) break;
-            const int64_t sl = (int64_t)(kq & 0xffffffffull);
-            g += c < K ? dEi[sl * K + c] : (c < K + D ? dEo[sl * D + (c - K)] : dfb[sl]);
-        }
-        if (c < K) Gi[(int64_t)id * K + c] = g;
-        else if (c < K + D) Go[(int64_t)id * D + (c - K)] = g;
-        else {
-            const float a = a_fbias[id] + g * g;
-            a_fbias[id] = a;
-            fbias[id] -= lr * g / sqrtf(a);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void table_adagrad_l2_kernel(float* __restrict__ w, float* __restrict__ acc,
-                                                               const float* __restrict__ G, int64_t n, float lam, float lr) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float g = G[i] + lam * w[i];
-    const float a = acc[i] + g * g;
-    acc[i] = a;
-    w[i] -= lr * g / sqrtf(a);
-}
-
-int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, const int32_t* ids, int64_t n_rows,
-                           hipStream_t st) {
-    const cffm_shape_t* s = c.s;
-    const cffm_ws_layout_t& wl = c.wl;
-    float* Gi = c.at(wl.Gi);
-    float* Go = c.at(wl.Go);
-    const int64_t ni = (int64_t)s->M * s->K, no = (int64_t)s->M * s->D;
-    hipError_t e = hipMemsetAsync(Gi, 0, (size_t)ni * 4, st);
-    if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(Go, 0, (size_t)no * 4, st);
-    if (e != hipSuccess) return (int)e;
-    SortOpts so;
-    so.prepacked = true;
-    int rc = cffm_sort_keys_impl(c, ids, n_rows, so, st);
-    if (rc) return rc;
-    const RowGrads r = RowGrads::of_ws(c);           // both branches are on (cffm_train_step refuses the loss otherwise)
-    hipLaunchKernelGGL(scatter_rows_l2_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st,
-                       c.at<const unsigned long long>(wl.sort_vals), n_rows, s->M, s->K, s->D, r.dEi, r.dEo, r.dfb, Gi, Go,
-                       tab->feat_bias, acc->feat_bias, s->lr);
-    CFFM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(table_adagrad_l2_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, tab->inner_emb,
-                       acc->inner_emb, Gi, ni, s->lamda, s->lr);
-    CFFM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(table_adagrad_l2_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, st, tab->outer_emb,
-                       acc->outer_emb, Go, no, s->lamda_att, s->lr);       // quirk Q13: lamda_att scales the outer table
-    CFFM_CHECK_LAUNCH();
-    return 0;
-}
-
-// ---- the other optimizers of CFFM.py:519-529 (TF-1.14 semantics) ------------------------------------------------------
-struct OptConst { int opt; float lr, lr_t, b1, b2, omb1, omb2, eps, mom; };   // omb* = 1 - beta, rounded once from double
-
-__device__ __forceinline__ void opt_update(float& w, float* s1, float* s2, float g, const OptConst& c) {
-    if (c.opt == CFFM_OPT_SGD) {
-        w -= c.lr * g;
-    } else if (c.opt == CFFM_OPT_MOMENTUM) {
-        const float a = c.mom * (*s1) + g;
-        *s1 = a;
-        w -= c.lr * a;
-    } else {                                      // Adam
-        const float m = c.b1 * (*s1) + c.omb1 * g;
-        const float v = c.b2 * (*s2) + c.omb2 * g * g;
-        *s1 = m; *s2 = v;
-        w -= c.lr_t * m / (sqrtf(v) + c.eps);
-    }
-}
-
-// lam != 0: the l2_regularizer term of the regularised square loss (CFFM.py:489-491), g = grad + lam * w
+// ---- tables with a dense gradient: Adam's non-lazy sparse apply and the regularised square loss (CFFM.py:489-491) ----------------
+// lam != 0: the l2_regularizer term of the regularised square loss, g = grad + lam * w
+template <class Rule>
 __global__ __launch_bounds__(256) void dense_opt_kernel(float* __restrict__ w, float* __restrict__ s1, float* __restrict__ s2,
-                                                        const float* __restrict__ grad, int64_t n, OptConst c, float lam) {
+                                                        const float* __restrict__ grad, int64_t n, Rule rule, float lam) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float wv = w[i];
-    opt_update(wv, s1 ? s1 + i : nullptr, s2 ? s2 + i : nullptr, (grad ? grad[i] : 0.f) + lam * wv, c);
+    rule(wv, s1 ? s1 + i : nullptr, s2 ? s2 + i : nullptr, (grad ? grad[i] : 0.f) + lam * wv);
     w[i] = wv;
 }
 
-// SGD / Momentum on the touched rows (duplicates summed first, in slot order); Adam: the summed rows go to the dense
-// buffers G* and dense_opt_kernel then sweeps every row (TF's non-lazy sparse Adam moves all of them)
-__global__ __launch_bounds__(256) void sparse_opt_kernel(const unsigned long long* __restrict__ keys, int64_t n, int M, int K, int D,
-                                                         const float* __restrict__ dEi, const float* __restrict__ dEo,
-                                                         const float* __restrict__ dfb, cffm_tables_t tab, cffm_tables_t st1,
-                                                         float* __restrict__ Gi, float* __restrict__ Go, float* __restrict__ Gfb,
-                                                         OptConst c, int dense_tables) {
-    const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pos >= n) return;
-    const int id = (int)(keys[pos] >> 32);
-    if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;
-    if (id < 0 || id >= M) return;
-    const int W = K + D + 1;
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int col = c0 + lane;
-        if (col >= W) continue;
-        // a disabled branch (CFFM.py:301, :348) has no table variable: nothing to update
-        if ((col < K && dEi == nullptr) || (col >= K && col < K + D && dEo == nullptr)) continue;
-        float g = 0.f;
-        for (int64_t q = pos; q < n; ++q) {
-            const unsigned long long kq = keys[q];
-            if ((int)(kq >> 32) != id) break;
-            const int64_t sl = (int64_t)(kq & 0xffffffffull);
-            g += col < K ? dEi[sl * K + col] : (col < K + D ? dEo[sl * D + (col - K)] : dfb[sl]);
-        }
-        const int64_t off = col < K ? (int64_t)id * K + col : (col < K + D ? (int64_t)id * D + (col - K) : (int64_t)id);
-        float* wt = col < K ? tab.inner_emb : (col < K + D ? tab.outer_emb : tab.feat_bias);
-        // dense gradient of a table (Adam's non-lazy sparse apply; the regularised loss): the summed rows go to G*
-        if (c.opt == CFFM_OPT_ADAM || (dense_tables && col < K + D)) {
-            (col < K ? Gi : (col < K + D ? Go : Gfb))[off] = g;
-        } else {
-            float* s1 = c.opt == CFFM_OPT_MOMENTUM ? (col < K ? st1.inner_emb : (col < K + D ? st1.outer_emb : st1.feat_bias)) + off : nullptr;
-            float wv = wt[off];
-            opt_update(wv, s1, nullptr, g, c);
-            wt[off] = wv;
-        }
-    }
-}
+// the rule on the touched rows (duplicates summed first, in slot order), except the tables of MixSink::store_mask
+template <class Rule>
+__global__ __launch_bounds__(256) void sparse_mix_kernel(SparseArgs a, MixSink<Rule> sink) { segment_walk(blockIdx.x, a, sink); }
 
-// the constants of CFFM.py:519-529, for the single-GPU step and the multi-GPU apply alike (step >= 1; only Adam reads lr_t)
-static OptConst opt_const(const cffm_shape_t* s, int64_t step) {
-    OptConst c;
-    c.opt = s->optimizer; c.lr = s->lr; c.b1 = 0.9f; c.b2 = 0.999f; c.omb1 = (float)(1.0 - 0.9); c.omb2 = (float)(1.0 - 0.999); c.eps = 1e-8f; c.mom = 0.95f;
-    c.lr_t = (float)((double)s->lr * sqrt(1.0 - pow(0.999, (double)step)) / (1.0 - pow(0.9, (double)step)));
-    return c;
-}
-
-int cffm_apply_opt(const StepCtx& cx, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
-                   float* th1, float* th2, const float* grad, const int32_t* ids, int64_t n_rows, int64_t step, hipStream_t st) {
+// The table update of the single-GPU step from the packed keys in ws.sort_keys.  Adam: TF's sparse Adam is non-lazy, so the summed
+// rows of all three tables go to zeroed dense buffers G* and a dense sweep moves every row.  Regularised square loss: the l2 terms
+// make the gradients of the two embedding tables dense for every optimizer (IndexedSlices + dense aggregates to dense), g = G +
+// lamda * w; feature_bias stays sparse.  Otherwise: the rule on the touched rows only.
+template <class Rule>
+static int tables_apply(const StepCtx& cx, const cffm_tables_t* tab, const cffm_tables_t& t1, const cffm_tables_t& t2, int64_t n_rows,
+                        const Rule& rule, bool adam, hipStream_t st) {
     const cffm_shape_t* s = cx.s;
-    const cffm_theta_layout_t& tl = cx.tl;
     const cffm_ws_layout_t& wl = cx.wl;
-    const OptConst c = opt_const(s, step);
-    hipLaunchKernelGGL(dense_opt_kernel, dim3((unsigned)((tl.n + 255) / 256)), dim3(256), 0, st, theta, th1, th2, grad,
-                       (int64_t)tl.n, c, 0.f);
-    CFFM_CHECK_LAUNCH();
-    // regularised square loss (CFFM.py:489-491): the l2 terms make the gradients of the two embedding tables dense for
-    // every optimizer (IndexedSlices + dense aggregates to dense); feature_bias stays sparse (Adam: non-lazy, all rows)
     const bool l2 = s->loss == CFFM_LOSS_SQUARE_L2;
-    const bool adam = c.opt == CFFM_OPT_ADAM;
-    float *Gi = nullptr, *Go = nullptr, *Gfb = nullptr;
+    const int store_mask = adam ? 7 : (l2 ? 3 : 0);
+    const cffm_tables_t G = store_mask ? cffm_tables_t{cx.at(wl.Gi), cx.at(wl.Go), cx.at(wl.Gfb)} : NO_TABLES;
     const int64_t ni = (int64_t)s->M * s->K, no = (int64_t)s->M * s->D, nf = s->M;
-    if (adam || l2) {
-        Gi = cx.at(wl.Gi); Go = cx.at(wl.Go); Gfb = cx.at(wl.Gfb);
-        hipError_t e = hipMemsetAsync(Gi, 0, (size_t)(wl.Gfb + nf * 4 - wl.Gi), st);     // the three buffers are contiguous
+    if (store_mask) {
+        hipError_t e = hipMemsetAsync(G.inner_emb, 0, (size_t)(wl.Gfb + nf * 4 - wl.Gi), st);     // the three buffers are contiguous
         if (e != hipSuccess) return (int)e;
     }
     SortOpts so;
     so.prepacked = true;
-    int rc = cffm_sort_keys_impl(cx, ids, n_rows, so, st);
+    int rc = cffm_sort_keys_impl(cx, nullptr, n_rows, so, st);
     if (rc) return rc;
-    const RowGrads r = RowGrads::of_ws(cx);
-    cffm_tables_t t1 = st1 ? *st1 : cffm_tables_t{nullptr, nullptr, nullptr};
-    cffm_tables_t t2 = st2 ? *st2 : cffm_tables_t{nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(sparse_opt_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st,
-                       cx.at<const unsigned long long>(wl.sort_vals), n_rows, s->M, s->K, s->D, r.dEi, r.dEo, r.dfb, *tab, t1, Gi, Go,
-                       Gfb, c, l2 ? 1 : 0);
+    hipLaunchKernelGGL(sparse_mix_kernel<Rule>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, cx.sparse_args(n_rows, RowGrads::of_ws(cx)),
+                       MixSink<Rule>{{*tab, t1, s->K, s->D, rule}, {G, s->K, s->D}, store_mask});
     CFFM_CHECK_LAUNCH();
-    if (adam || l2) {      // dense sweeps; a disabled branch has no table variable and is left alone
+    if (store_mask) {      // dense sweeps; a disabled branch has no table variable and is left alone
         if (s->inner_conv)
-            hipLaunchKernelGGL(dense_opt_kernel, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, tab->inner_emb, t1.inner_emb,
-                               t2.inner_emb, (const float*)Gi, ni, c, l2 ? s->lamda : 0.f);
+            hipLaunchKernelGGL(dense_opt_kernel<Rule>, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, st, tab->inner_emb, t1.inner_emb,
+                               t2.inner_emb, (const float*)G.inner_emb, ni, rule, l2 ? s->lamda : 0.f);
         if (s->outer_conv)
-            hipLaunchKernelGGL(dense_opt_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, st, tab->outer_emb, t1.outer_emb,
-                               t2.outer_emb, (const float*)Go, no, c, l2 ? s->lamda_att : 0.f);    // quirk Q13: lamda_att scales the outer table
+            hipLaunchKernelGGL(dense_opt_kernel<Rule>, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, st, tab->outer_emb, t1.outer_emb,
+                               t2.outer_emb, (const float*)G.outer_emb, no, rule, l2 ? s->lamda_att : 0.f);    // quirk Q13: lamda_att scales the outer table
         if (adam)
-            hipLaunchKernelGGL(dense_opt_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, tab->feat_bias, t1.feat_bias,
-                               t2.feat_bias, (const float*)Gfb, nf, c, 0.f);
+            hipLaunchKernelGGL(dense_opt_kernel<Rule>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, tab->feat_bias, t1.feat_bias,
+                               t2.feat_bias, (const float*)G.feat_bias, nf, rule, 0.f);
         CFFM_CHECK_LAUNCH();
     }
     return 0;
 }
 
-// ---- SGD and Momentum for the data-parallel and row-sharded steps (cffm_dp_apply_opt) -------------------------------
-// The launch structure of cffm_dp_apply with opt_update in place of the Adagrad rule: both rules are, like Adagrad, a dense
-// rule on theta and a duplicates-summed-first rule on the looked-up rows only (TF does not decay the Momentum accumulator
-// of a row nobody looked up), so the late 1/L, the key placement / run merge and the segment walk carry over unchanged.
-// Adam is not here: TF's sparse Adam is non-lazy (every row of every table moves every step).
-__device__ __forceinline__ void dense_opt_late_body(int bid, float* __restrict__ v, float* __restrict__ s1,
-                                                    const float* __restrict__ grad, int64_t n, const OptConst& oc,
-                                                    const LateScale& ls, float* __restrict__ loss_out) {
-    const int64_t i = (int64_t)bid * 256 + threadIdx.x;
-    if (i == 0 && loss_out != nullptr) loss_out[0] = ls.on ? sqrtf(ls.sum[0] * ls.inv_Bg + 1e-10f) : ls.sum[0] * ls.inv_Bg;
-    if (i >= n) return;
-    const float g = grad[i] * late_scale(ls);
-    float wv = v[i];
-    opt_update(wv, oc.opt == CFFM_OPT_MOMENTUM ? s1 + i : nullptr, nullptr, g, oc);
-    v[i] = wv;
+// Adagrad under the regularised square loss (theta was updated with the slab reduction)
+int cffm_tables_adagrad_l2(const StepCtx& c, const cffm_tables_t* tab, const cffm_tables_t* acc, int64_t n_rows, hipStream_t st) {
+    return tables_apply(c, tab, *acc, NO_TABLES, n_rows, AdagradRule{c.s->lr}, false, st);
 }
 
-// one wavefront per sorted position, segment heads only: sparse_adagrad_body's walk (both addressings of SparseArgs) with
-// opt_update on the row and, for Momentum, on its slot row (a.a_* = the first slot; not read for SGD)
-__device__ __forceinline__ void sparse_opt_late_body(int bid, const SparseArgs& a, const OptConst& oc) {
-    const unsigned long long* __restrict__ keys = a.keys;
-    const int64_t n = a.n;
-    const int M = a.M, K = a.K, D = a.D;
-    const float* __restrict__ dEi = a.dEi; const float* __restrict__ dEo = a.dEo; const float* __restrict__ dfb = a.dfb;
-    const float gscale = late_scale(a.ls);
-    const int64_t pos = (int64_t)bid * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (pos >= n) return;
-    const int id = (int)(keys[pos] >> 32);
-    if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;          // not a segment head
-    if (id < 0 || id >= M) return;
-    const int W = (dEi ? K : 0) + (dEo ? D : 0) + 1;     // columns: inner | outer | bias (a disabled branch has none)
-    const int Ki = dEi ? K : 0;
-    const bool slot = oc.opt == CFFM_OPT_MOMENTUM;
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int c = c0 + lane;
-        if (c >= W) continue;
-        float g = 0.f;
-        for (int64_t q = pos; q < n; ++q) {
-            const unsigned long long kq = keys[q];
-            if ((int)(kq >> 32) != id) break;
-            int64_t sl = (int64_t)(kq & 0xffffffffull);
-            int64_t boff = 0;
-            if (a.run_len > 0) {
-                const int blk = fast_div((int)sl, a.inv_run_len);
-                boff = (int64_t)blk * a.run_stride;
-                sl -= (int64_t)blk * a.run_len;
-            }
-            g += c < Ki ? dEi[boff + sl * a.sEi + c] : (c < W - 1 ? dEo[boff + sl * a.sEo + (c - Ki)] : dfb[boff + sl * a.sfb]);
-        }
-        g *= gscale;
-        float *vp, *ap;
-        if (c < Ki) { const int64_t o = (int64_t)id * K + c; vp = a.inner + o; ap = slot ? a.a_inner + o : nullptr; }
-        else if (c < W - 1) { const int64_t o = (int64_t)id * D + (c - Ki); vp = a.outer + o; ap = slot ? a.a_outer + o : nullptr; }
-        else { vp = a.fbias + id; ap = slot ? a.a_fbias + id : nullptr; }
-        float wv = *vp;
-        opt_update(wv, ap, nullptr, g, oc);
-        *vp = wv;
-    }
-}
-
-__global__ __launch_bounds__(256) void dense_opt_late_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
-                                                             int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out) {
-    dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
-}
-
-__global__ __launch_bounds__(256) void sparse_opt_late_kernel(SparseArgs a, OptConst oc) { sparse_opt_late_body(blockIdx.x, a, oc); }
-
-// first launch of cffm_dp_apply_opt, sorted runs: dense rule with the late 1/L ∥ merge of the per-rank runs
-__global__ __launch_bounds__(256) void dp_opt_head_merge_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
-                                                                int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out,
-                                                                int n_dense, MergeArgs ma) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if ((int)blockIdx.x < n_dense) dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
-    else merge_runs_body(blockIdx.x - n_dense, ma, reinterpret_cast<unsigned*>(smem));
-}
-
-// first launch of cffm_dp_apply_opt, n_rows <= 8192 without runs: dense rule with the late 1/L ∥ placement of the keys
-__global__ __launch_bounds__(256) void dp_opt_head_kernel(float* __restrict__ v, float* __restrict__ s1, const float* __restrict__ grad,
-                                                          int64_t n, OptConst oc, LateScale ls, float* __restrict__ loss_out, int n_dense,
-                                                          const int32_t* __restrict__ ids, int64_t id_stride, int n_keys, int n_rank,
-                                                          unsigned long long* __restrict__ keys_out) {
-    __shared__ float cnt[4 * RANK_KPW_MAX];
-    if ((int)blockIdx.x < n_dense) dense_opt_late_body(blockIdx.x, v, s1, grad, n, oc, ls, loss_out);
-    else rank_place_body(blockIdx.x - n_dense, n_rank, ids, id_stride, n_keys, keys_out, cnt);
-}
-
-extern "C" int cffm_dp_apply_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* acc, float* theta,
-                                 float* theta_acc, const float* grad_sum, int64_t B_global, const float* rows,
-                                 int64_t n_rows, void* ws, int32_t B_ws, float* loss_out, int32_t n_runs, void* stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (s->optimizer == CFFM_OPT_ADAGRAD)
-        return cffm_dp_apply(s, tab, acc, theta, theta_acc, grad_sum, B_global, rows, n_rows, ws, B_ws, loss_out, n_runs, stream);
-    if (s->optimizer == CFFM_OPT_ADAM) return CFFM_ERR_UNSUPPORTED;       // non-lazy: a dense sweep of every table, not this design
-    // the checks of cffm_dp_apply, all of them before the first launch
-    if (n_runs > 0) {
-        if (n_rows <= 0 || n_rows % n_runs || n_rows > (int64_t)B_ws * s->F || n_rows * 4 > CFFM_LDS_SHARED_CU) return CFFM_ERR_BAD_SHAPE;
-        const int64_t m = n_rows / n_runs;
-        if (m % s->F || !cffm_fwd_all_ok(s, (int32_t)(m / s->F))) return CFFM_ERR_UNSUPPORTED;      // the runs only exist on that path
-    } else if (n_rows > 0 && n_rows > (int64_t)B_ws * s->F) {
-        return CFFM_ERR_BAD_SHAPE;
-    }
-    const bool mom = s->optimizer == CFFM_OPT_MOMENTUM;
-    if (!tab || !theta || !grad_sum || (n_rows > 0 && (!rows || !ws)) || (mom && (!acc || !theta_acc))) return CFFM_ERR_BAD_SHAPE;
-    hipStream_t st = (hipStream_t)stream;
-    const StepCtx c(s, B_ws, theta, ws);
-    const cffm_theta_layout_t& tl = c.tl;
-    const OptConst oc = opt_const(s, 1);
-    LateScale ls = {grad_sum + tl.n, 1.f / (float)B_global, s->loss == CFFM_LOSS_SQUARE_RMSE ? 1 : 0};
-    const int64_t W = 1 + s->K + s->D + 1;
-    const RowGrads rg = RowGrads::packed(s, rows, W);
-    const cffm_tables_t no_slot = {nullptr, nullptr, nullptr};             // SGD keeps no slot
-    const cffm_tables_t* slot = mom ? acc : &no_slot;
-    float* th1 = mom ? theta_acc : nullptr;
-    const int n_dense = (int)((tl.n + 255) / 256);
-    SparseArgs a = c.sparse_args(tab, slot, n_rows, rg, ls);
-    if (n_runs > 0) {
-        const int m = (int)(n_rows / n_runs);
-        MergeArgs ma;
-        ma.rows = rows; ma.block_floats = (int64_t)m * (W + 2); ma.keys_off = (int64_t)m * W; ma.m = m; ma.n_runs = n_runs;
-        ma.out = c.at<unsigned long long>(c.wl.sort_vals);
-        const size_t lds = (size_t)n_rows * 4;
-        if ((rc = set_lds(dp_opt_head_merge_kernel, lds))) return rc;
-        hipLaunchKernelGGL(dp_opt_head_merge_kernel, dim3(n_dense + (unsigned)((n_rows + 255) / 256)), dim3(256), lds, st, theta, th1,
-                           grad_sum, (int64_t)tl.n, oc, ls, loss_out, n_dense, ma);
-        CFFM_CHECK_LAUNCH();
-        a.run_len = m; a.run_stride = ma.block_floats; a.inv_run_len = 1.f / (float)m;
-    } else if (n_rows > 0 && n_rows <= 8192) {
-        const int n_rank = 256;                              // kpw = ceil(n_rows / 256) <= 32 keys per workgroup
-        hipLaunchKernelGGL(dp_opt_head_kernel, dim3(n_dense + n_rank), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, oc, ls,
-                           loss_out, n_dense, (const int32_t*)rows, W, (int)n_rows, n_rank, c.at<unsigned long long>(c.wl.sort_vals));
-        CFFM_CHECK_LAUNCH();
-    } else {
-        hipLaunchKernelGGL(dense_opt_late_kernel, dim3((unsigned)n_dense), dim3(256), 0, st, theta, th1, grad_sum, (int64_t)tl.n, oc, ls,
-                           loss_out);
-        CFFM_CHECK_LAUNCH();
-        if (n_rows <= 0) return 0;
-        SortOpts so;
-        so.id_stride = W;                                    // the id column of the rows
-        if ((rc = cffm_sort_keys_impl(c, (const int32_t*)rows, n_rows, so, st))) return rc;
-    }
-    hipLaunchKernelGGL(sparse_opt_late_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, st, a, oc);
+int cffm_apply_opt(const StepCtx& cx, const cffm_tables_t* tab, const cffm_tables_t* st1, const cffm_tables_t* st2, float* theta,
+                   float* th1, float* th2, const float* grad, int64_t n_rows, int64_t step, hipStream_t st) {
+    const OptRule rule = opt_rule(cx.s, step);
+    hipLaunchKernelGGL(dense_opt_kernel<OptRule>, dim3((unsigned)((cx.tl.n + 255) / 256)), dim3(256), 0, st, theta, th1, th2, grad,
+                       (int64_t)cx.tl.n, rule, 0.f);
     CFFM_CHECK_LAUNCH();
-    return 0;
+    return tables_apply(cx, tab, st1 ? *st1 : NO_TABLES, st2 ? *st2 : NO_TABLES, n_rows, rule, rule.c.opt == CFFM_OPT_ADAM, st);
 }

@@ -49,6 +49,12 @@ def test_sgd_and_momentum_make_the_shape_checks_of_cffm_dp_apply(lib, opt):
     assert _call(lib.cffm_dp_apply, s, 24, 0) == 10002                                     # the Adagrad entry point still refuses them
 
 
+def test_adagrad_makes_every_check_before_its_first_launch(lib):
+    s = hip.Shape(optimizer=0, **BASE)
+    assert _call(lib.cffm_dp_apply, s, 8 * 3 + 1, 0) == 10001                              # more rows than the workspace holds
+    assert _call(lib.cffm_dp_apply, s, 24, 0) == 10001                                     # NULL pointers
+
+
 def test_adagrad_forwards_to_cffm_dp_apply(lib):
     s = hip.Shape(optimizer=0, **BASE)
     for n_rows, n_runs in ((0, 3), (25, 2)):

@@ -110,7 +110,7 @@ CALL_SITES = {
     'inner_body.hpp': ['invK2', 'invK4', 'invK2'],
     'conv.hip': ['invD', 'invPp', 'invPp', 'invPp', 'invPp', 'invD', 'invF', 'invPp', 'invPp', 'invPp', 'invD', 'invD', 'invD', 'invF',
                  'invD(inline)'],                                # conv0_fact_tile_fwd2_kernel stages its rows the same way
-    'optim.hip': ['a.inv_run_len', 'a.inv_run_len'],
+    'optim.hip': ['a.inv_run_len'],
 }
 
 
