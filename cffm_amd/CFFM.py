@@ -587,6 +587,182 @@ class CFFM(object):
             raise ValueError('evaluate_ranking(): predictions contain NaN')
         return hits / rows, gains / rows
 
+    # ---- candidates that are tuples of ids, and a candidate list per context ----------------------------
+    # recommend / evaluate_ranking put ONE id at ONE column and leave the context's other ids alone.  Where an item's attributes are
+    # fields of their own (frappe: the app's cost next to the app id) that scores rows that cannot occur; the methods below replace
+    # several columns together, from one shared list or from a list per context.  The two methods above stay as they are.
+    def _tuple_fields(self, fields):
+        cols = [fields] if isinstance(fields, (int, np.integer)) else list(fields)
+        cols = [int(f) for f in cols]
+        if not cols or len(set(cols)) != len(cols) or not all(0 <= f < self.num_field for f in cols):
+            raise ValueError('fields must be a column or distinct columns of [0, %d), not %r' % (self.num_field, fields))
+        return cols
+
+    @staticmethod
+    def _tuple_array(candidates, nf, lead, what):
+        """candidates as int32 [..., nf] with `lead` leading axes; one field may come without the last axis."""
+        cand = np.asarray(candidates)
+        if nf == 1 and cand.ndim == lead:
+            cand = cand[..., None]
+        if cand.ndim != lead + 1 or cand.shape[-1] != nf or cand.size == 0 or cand.dtype.kind not in 'iu':
+            raise ValueError('%s must be integer ids of shape %s' % (what, ('[C, N' if lead == 2 else '[N') + (', %d]' % nf if nf > 1 else ']')))
+        return np.ascontiguousarray(cand.astype(np.int32))
+
+    @staticmethod
+    def _tuple_scorer(eng, sweep, fields, N, per_context):
+        """score(ctx, cand) for cand [N, nf] (shared) or [C, N, nf] (per context).  'expand': score_candidate_tuples, bit for bit
+        predict on the expanded rows.  'shared': the shared sweep, one field only (ValueError for tuples or a shape that is not
+        served).  'auto': the shared sweep for one field at a served shape with N >= SWEEP_MIN_N, else expand."""
+        if sweep not in ('expand', 'shared', 'auto'):
+            raise ValueError("sweep must be 'expand', 'shared' or 'auto', not %r" % (sweep,))
+        nf = len(fields)
+        if sweep == 'shared':
+            if nf > 1:
+                raise ValueError("sweep='shared': the shared sweep scores one field, not tuples of %d" % nf)
+            if not eng.sweep_ok():
+                raise ValueError("sweep='shared': the shared sweep does not serve this shape (both branches, D = 32, F <= 10)")
+        elif sweep == 'expand' or nf > 1 or SWEEP_MIN_N is None or N < SWEEP_MIN_N or not eng.sweep_ok():
+            return lambda ctx, cand: eng.score_candidate_tuples(ctx, fields, cand)
+        if per_context:
+            return lambda ctx, cand: eng.score_candidate_lists_shared(ctx, fields[0], cand.reshape(cand.shape[0], cand.shape[1]))
+        return lambda ctx, cand: eng.score_candidates_shared(ctx, fields[0], cand.reshape(-1))
+
+    def recommend_tuples(self, contexts, fields, candidates, per_context=False, counts=None, k=10, skip=None, score_rows=1 << 22,
+                         sweep='expand'):
+        """For every context row, the k candidates that score highest when their ids are put at the columns `fields` (an int or
+        distinct columns) TOGETHER.  candidates: [N] / [N, nf] (one list for every context) or, with per_context, [C, N] /
+        [C, N, nf] (a list per context); counts: optional [C] for per-context lists, list c holding counts[c] <= N candidates and
+        padding behind them (any id may sit there; it is merged into the skip mask); skip: optional boolean [C, N] over candidate
+        positions.  Returns host arrays (pos int32 [C, k] candidate POSITIONS in the caller's list, -1 padded - a tuple has no
+        single id to return; scores float32 [C, k], NaN padded).  sweep: 'expand' (default) is bit for bit predict on the expanded
+        rows; 'shared' serves one field at a served shape (ValueError otherwise); 'auto' takes it only there and for
+        N >= SWEEP_MIN_N.  Local to the calling rank: no collective."""
+        import torch
+        eng = self._ranking_engine()
+        cols = self._tuple_fields(fields)
+        if not 1 <= int(k) <= 1024:
+            raise ValueError('recommend_tuples(): k must be in [1, 1024]')
+        ctx = np.asarray(contexts)
+        if ctx.ndim != 2 or ctx.shape[1] != self.num_field:
+            raise ValueError('contexts must be [C, %d] feature ids' % self.num_field)
+        cand = self._tuple_array(candidates, len(cols), 2 if per_context else 1, 'candidates')
+        C, N, k = int(ctx.shape[0]), int(cand.shape[-2]), int(k)
+        if per_context and cand.shape[0] != C:
+            raise ValueError('per_context candidates must hold one list per context: [%d, N, ...], not %r' % (C, cand.shape))
+        mask = None
+        if skip is not None:
+            mask = np.asarray(skip) != 0
+            if mask.shape != (C, N):
+                raise ValueError('skip must be [%d, %d]: contexts x candidates' % (C, N))
+        if counts is not None:
+            if not per_context:
+                raise ValueError('counts belongs to per_context candidate lists')
+            cnt = np.asarray(counts)
+            if cnt.shape != (C,) or cnt.dtype.kind not in 'iu' or (cnt < 0).any() or (cnt > N).any():
+                raise ValueError('counts must be [%d] integers in [0, %d]' % (C, N))
+            pad = np.arange(N)[None, :] >= cnt[:, None]
+            mask = pad if mask is None else (mask | pad)
+        dev = eng.device
+        ctx = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(dev)
+        cand = torch.from_numpy(cand).to(dev)
+        if mask is not None:
+            mask = torch.from_numpy(np.ascontiguousarray(mask)).to(dev).to(torch.uint8)
+        pos_out = torch.empty((C, k), dtype=torch.int32, device=dev)
+        val_out = torch.empty((C, k), dtype=torch.float32, device=dev)
+        group = max(1, int(score_rows) // N)
+        score = self._tuple_scorer(eng, sweep, cols, N, per_context)
+        for c0 in range(0, C, group):
+            c1 = min(C, c0 + group)
+            scores = score(ctx[c0:c1], cand[c0:c1] if per_context else cand)
+            idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
+            pos_out[c0:c1] = idx
+            val_out[c0:c1] = val
+        return pos_out.cpu().numpy(), val_out.cpu().numpy()
+
+    @staticmethod
+    def _tuple_positions(cand, tgt):
+        """Position in cand [N, nf] of every row of tgt [P, nf] (the first one, should the list repeat a tuple); N where it is
+        missing.  On the device: one torch.unique(dim=0) over both."""
+        import torch
+        N = int(cand.shape[0])
+        inv = torch.unique(torch.cat([cand, tgt]), dim=0, return_inverse=True)[1]      # one number per distinct tuple
+        cs, order = torch.sort(inv[:N], stable=True)
+        at = torch.searchsorted(cs, inv[N:]).clamp(max=N - 1)
+        return torch.where(cs[at] == inv[N:], order[at], torch.full_like(at, N))
+
+    def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand'):
+        """(HR@k, NDCG@k) over the rows of `data` with a positive label, the target being the row's own tuple at `fields`.
+        negatives=None: one shared list - by default the distinct tuples at `fields` over the train split and `data`, sorted
+        (torch.unique(dim=0) on the device); explicit candidates [N] / [N, nf] that lack a target raise ValueError.  negatives=m:
+        the sampled protocol - every row is ranked in a list of its own: its target and m distinct tuples drawn without it from
+        the distinct tuples of that set, with np.random.RandomState(seed) on the host (one permutation of the set per row).  The
+        target's POSITION in its list is drawn from the same generator: ties go to the smaller position and CFFM scores tie often,
+        so a target fixed at position 0 would win every tie.  m >= the number of distinct tuples raises ValueError.  Under a process
+        group every rank draws all lists from the same seed and then takes its contiguous share of the rows.  The sums stay on the
+        device in float64 and are read once, as in evaluate_ranking."""
+        import torch
+        eng = self._ranking_engine()
+        cols = self._tuple_fields(fields)
+        ids, y, _ = self._device_split(data)
+        k = int(k)
+        if k < 1:
+            raise ValueError('evaluate_ranking_tuples(): k must be >= 1')
+        colt = torch.tensor(cols, dtype=torch.long, device=eng.device)
+        if candidates is None:
+            splits = [data] if self._train_split is None or self._train_split is data else [self._train_split, data]
+            cand = torch.unique(torch.cat([self._device_split(d)[0][:, colt] for d in splits]), dim=0).to(torch.int32)
+        else:
+            cand = torch.from_numpy(self._tuple_array(candidates, len(cols), 1, 'candidates')).to(eng.device)
+            if negatives is not None:
+                cand = torch.unique(cand, dim=0)
+        ctx = ids[y.reshape(-1) > 0]
+        P, U = int(ctx.shape[0]), int(cand.shape[0])
+        if P == 0:
+            raise ValueError('evaluate_ranking_tuples() needs at least one row with a positive label')
+        tgt = ctx[:, colt].to(torch.int32)
+        tpos = self._tuple_positions(cand, tgt)
+        missing = tpos == U
+        if bool(missing.any()):
+            raise ValueError('evaluate_ranking_tuples(): target %s at fields %s is not among the candidates'
+                             % (tuple(int(v) for v in tgt[missing][0]), tuple(cols)))
+        N, lists = U, None
+        if negatives is not None:
+            m = int(negatives)
+            if m < 1 or m >= U:
+                raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
+            rng = np.random.RandomState(seed)
+            at = tpos.cpu().numpy()
+            lists = np.empty((P, m + 1), dtype=np.int64)               # indices into the distinct set
+            for r in range(P):
+                neg = rng.permutation(U - 1)[:m]
+                lists[r, 1:] = neg + (neg >= at[r])                    # the set without the target
+            place = rng.randint(0, m + 1, size=P)
+            lists[:, 0] = lists[np.arange(P), place]
+            lists[np.arange(P), place] = at
+            lists = torch.from_numpy(lists).to(eng.device)
+            tpos, N = torch.from_numpy(place).to(eng.device), m + 1
+        tpos = tpos.to(torch.int32)
+        r0, r1 = 0, P
+        if self.world > 1:
+            share = -(-P // self.world)
+            r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
+        sums = torch.zeros(4, dtype=torch.float64, device=eng.device)      # [hits, gains, rows, NaN flag], read once
+        group = max(1, int(score_rows) // N)
+        score = self._tuple_scorer(eng, sweep, cols, N, lists is not None)
+        for c0 in range(r0, r1, group):
+            c1 = min(r1, c0 + group)
+            scores = score(ctx[c0:c1], cand if lists is None else cand[lists[c0:c1]])
+            rank = eng.rank_of(scores, tpos[c0:c1]).double()
+            hit = rank < k
+            sums[0] += hit.sum()
+            sums[1] += torch.where(hit, 1.0 / torch.log2(rank + 2.0), torch.zeros_like(rank)).sum()
+            sums[2] += c1 - c0
+            sums[3] += torch.isnan(scores).any()
+        hits, gains, rows, bad = (float(v) for v in self._all_reduce_sum(sums).cpu().numpy())
+        if bad:
+            raise ValueError('evaluate_ranking_tuples(): predictions contain NaN')
+        return hits / rows, gains / rows
+
     # ---- host-side helpers with the reference's list semantics (CFFM.py:556-635) -------------------------
     def shuffle_in_unison_scary(self, x, y):
         x_, y_ = shuffle(x, y, random_state=self.random_seed)

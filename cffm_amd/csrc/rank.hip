@@ -43,16 +43,21 @@ __device__ __forceinline__ void rank_cmpex(unsigned long long* lk, int tid, int 
     }
 }
 
-__global__ __launch_bounds__(256) void expand_candidates_kernel(const int32_t* __restrict__ ctx, const int32_t* __restrict__ cand, int F,
-                                                                int field, int N, int64_t first, int64_t total,
-                                                                int32_t* __restrict__ ids_out) {
+// slot[f] = a where column f is fields[a] of a candidate tuple, -1 where the context keeps its id: by value, so the host list
+// needs no device copy
+struct FieldSlots { int8_t slot[CFFM_MAX_FIELDS]; };
+
+__global__ __launch_bounds__(256) void expand_candidates_kernel(const int32_t* __restrict__ ctx, const int32_t* __restrict__ cand,
+                                                                int64_t cand_ctx_stride, FieldSlots fs, int F, int nf, int N,
+                                                                int64_t first, int64_t total, int32_t* __restrict__ ids_out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const int64_t r = i / F;
     const int f = (int)(i - r * F);
     const int64_t g = first + r;
     const int64_t c = g / N;
-    ids_out[i] = f == field ? cand[g - c * N] : ctx[c * F + f];
+    const int a = fs.slot[f];
+    ids_out[i] = a >= 0 ? cand[c * cand_ctx_stride + (g - c * N) * nf + a] : ctx[c * F + f];
 }
 
 // One chunk of one row: FROM_SCORES builds the keys of candidates [chunk * 8192, ...) from the scores and the skip mask, otherwise
@@ -212,19 +217,35 @@ inline int topk_plan(int64_t C, int64_t N, int64_t k, TopkPlan* p) {
 
 }  // namespace
 
-extern "C" int cffm_expand_candidates(const cffm_shape_t* s, const int32_t* ctx, int32_t C, int32_t field, const int32_t* cand, int32_t N,
-                                      int64_t first, int32_t rows, int32_t* ids_out, void* stream) {
+extern "C" int cffm_expand_candidates_ex(const cffm_shape_t* s, const int32_t* ctx, int32_t C, const int32_t* fields, int32_t nf,
+                                         const int32_t* cand, int64_t cand_ctx_stride, int32_t N, int64_t first, int32_t rows,
+                                         int32_t* ids_out, void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
-    if (field < 0 || field >= s->F || N < 1 || C < 0 || first < 0 || rows < 0) return CFFM_ERR_BAD_SHAPE;
+    if (nf < 1 || nf > s->F || !fields) return CFFM_ERR_BAD_SHAPE;
+    FieldSlots fs;
+    for (int f = 0; f < CFFM_MAX_FIELDS; ++f) fs.slot[f] = -1;
+    for (int a = 0; a < nf; ++a) {
+        const int f = fields[a];
+        if (f < 0 || f >= s->F || fs.slot[f] >= 0) return CFFM_ERR_BAD_SHAPE;      // outside [0, F), or the same field twice
+        fs.slot[f] = (int8_t)a;
+    }
+    if (N < 1 || C < 0 || first < 0 || rows < 0) return CFFM_ERR_BAD_SHAPE;
     if (first + (int64_t)rows > (int64_t)C * N) return CFFM_ERR_BAD_SHAPE;
+    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < (int64_t)N * nf)) return CFFM_ERR_BAD_SHAPE;
     if (C == 0 || rows == 0) return 0;
     if (!ctx || !cand || !ids_out) return CFFM_ERR_BAD_SHAPE;
     const int64_t total = (int64_t)rows * s->F;
     hipLaunchKernelGGL(expand_candidates_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ctx, cand,
-                       (int)s->F, (int)field, (int)N, first, total, ids_out);
+                       cand_ctx_stride, fs, (int)s->F, (int)nf, (int)N, first, total, ids_out);
     CFFM_CHECK_LAUNCH();
     return 0;
+}
+
+// one field, one list for every context: the same kernel
+extern "C" int cffm_expand_candidates(const cffm_shape_t* s, const int32_t* ctx, int32_t C, int32_t field, const int32_t* cand, int32_t N,
+                                      int64_t first, int32_t rows, int32_t* ids_out, void* stream) {
+    return cffm_expand_candidates_ex(s, ctx, C, &field, 1, cand, 0, N, first, rows, ids_out, stream);
 }
 
 extern "C" int64_t cffm_topk_scratch_bytes(int32_t C, int32_t N, int32_t k) {

@@ -251,6 +251,7 @@ struct SweepArgs {
     int loss;
     const float *inner, *outer, *fbias;
     const int32_t* cand;
+    int64_t cand_ctx_stride;               // elements between the lists of two contexts; 0: one list for all
     int N, field, nchunks;
     int64_t units;
     const float* blocks;
@@ -442,10 +443,11 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     sweep_load_w<NT>(w3r, a.W3);
 
     // this thread's piece of a candidate's rows: K/4 inner pieces, D/4 outer pieces, one feature_bias value
+    const int32_t* cand = a.cand;                                // the current unit's list
     auto fetch = [&](int n) -> float4 {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (tid <= K4 + D / 4) {
-            const int id = sweep_clamp(a.cand[n], g.M);
+            const int id = sweep_clamp(cand[n], g.M);
             if (tid < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + tid];
             else if (tid < K4 + D / 4) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)id * (D / 4) + tid - K4];
             else v.x = a.fbias[id];
@@ -464,6 +466,7 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
         const int n0 = (int)first;
         const int n1 = first + CFFM_SWEEP_CHUNK < a.N ? n0 + CFFM_SWEEP_CHUNK : a.N;
         const float* blk = a.blocks + c * a.block_floats;
+        cand = a.cand + c * a.cand_ctx_stride;
         __syncthreads();
         // ---- stage the context's block: Zctx + b in registers, the rest in LDS ----
         float4 Zr[ZR];
@@ -661,13 +664,15 @@ extern "C" int64_t cffm_sweep_scratch_bytes(const cffm_shape_t* s, int32_t C) {
     return 256 + (int64_t)C * sweep_block(g.Pp, g.F, g.K).floats * 4;
 }
 
-extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
-                                int32_t field, const int32_t* cand, int32_t N, float* scores, int64_t row_stride, void* scratch,
-                                void* stream) {
+// both entry points: cand_ctx_stride == 0 is the shared list of cffm_score_sweep
+static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C, int32_t field,
+                     const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores, int64_t row_stride, void* scratch,
+                     void* stream) {
     int rc = check_shape(s);
     if (rc) return rc;
     if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
     if (field < 0 || field >= s->F || N < 1 || C < 0 || row_stride < N) return CFFM_ERR_BAD_SHAPE;
+    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < N)) return CFFM_ERR_BAD_SHAPE;
     if (C == 0) return 0;
     if (!tab || !tab->inner_emb || !tab->outer_emb || !tab->feat_bias || !theta || !ctx || !cand || !scores || !scratch)
         return CFFM_ERR_BAD_SHAPE;
@@ -686,7 +691,7 @@ extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab,
     SweepArgs sa;
     sa.g = g; sa.loss = s->loss;
     sa.inner = tab->inner_emb; sa.outer = tab->outer_emb; sa.fbias = tab->feat_bias;
-    sa.cand = cand; sa.N = N; sa.field = field;
+    sa.cand = cand; sa.cand_ctx_stride = cand_ctx_stride; sa.N = N; sa.field = field;
     sa.nchunks = (int)(((int64_t)N + CFFM_SWEEP_CHUNK - 1) / CFFM_SWEEP_CHUNK);
     sa.units = (int64_t)C * sa.nchunks;
     sa.blocks = blocks; sa.block_floats = bo.floats;
@@ -710,4 +715,16 @@ extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab,
         case 3: return sweep_launch<3>(ca, sa, C, grid, st);
         default: return CFFM_ERR_UNSUPPORTED;
     }
+}
+
+extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
+                                int32_t field, const int32_t* cand, int32_t N, float* scores, int64_t row_stride, void* scratch,
+                                void* stream) {
+    return sweep_run(s, tab, theta, ctx, C, field, cand, 0, N, scores, row_stride, scratch, stream);
+}
+
+extern "C" int cffm_score_sweep_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
+                                      int32_t field, const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores,
+                                      int64_t row_stride, void* scratch, void* stream) {
+    return sweep_run(s, tab, theta, ctx, C, field, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
 }

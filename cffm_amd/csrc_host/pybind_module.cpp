@@ -83,12 +83,14 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_eval_scratch_bytes);
     CFFM_BIND(cffm_eval_sums);
     CFFM_BIND(cffm_expand_candidates);
+    CFFM_BIND(cffm_expand_candidates_ex);
     CFFM_BIND(cffm_topk_scratch_bytes);
     CFFM_BIND(cffm_topk);
     CFFM_BIND(cffm_rank_of);
     CFFM_BIND(cffm_sweep_ok);
     CFFM_BIND(cffm_sweep_scratch_bytes);
     CFFM_BIND(cffm_score_sweep);
+    CFFM_BIND(cffm_score_sweep_lists);
     CFFM_BIND(cffm_probe_copy);
     CFFM_BIND(cffm_probe_read);
     CFFM_BIND(cffm_probe_mfma);

@@ -395,6 +395,46 @@ class HipEngine(object):
             hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
         return scores
 
+    def _cand_lists(self, ctx, cand, nf, who):
+        """(ctx, cand, C, N, stride) of a candidate argument [N, nf] (one list, stride 0) or [C, N, nf] (a list per context)."""
+        ctx, F = self._ids(ctx), int(self.cfg.F)
+        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
+            raise ValueError('contexts must be [C, %d] feature ids' % F)
+        C = int(ctx.shape[0])
+        if cand.dim() not in (2, 3) or int(cand.shape[-1]) != nf or (cand.dim() == 3 and int(cand.shape[0]) != C):
+            raise ValueError('%s: candidates must be [N, %d] or [%d, N, %d]' % (who, nf, C, nf))
+        N = int(cand.shape[-2])
+        if N < 1:
+            raise ValueError('%s: needs a candidate' % who)
+        return ctx, self._ids(cand), C, N, (N * nf if cand.dim() == 3 else 0)
+
+    def score_candidate_tuples(self, ctx, fields, cand, block=8192):
+        """score_candidates for candidates that are tuples of ids: `fields` are nf distinct columns, cand int32 [N, nf] (one list
+        for every context) or [C, N, nf] (a list per context) on the device, row (c, n) being context c with its ids at `fields`
+        replaced together by candidate n -> fp32 [C, N] on the device.  Swept exactly as score_candidates is: one reused id buffer
+        (cffm_expand_candidates_ex), cffm_predict into the piece's slice of the result, nothing synchronises."""
+        F, block = int(self.cfg.F), int(block)
+        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        nf = len(fields)
+        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields) or block < 1:
+            raise ValueError('score_candidate_tuples: needs block >= 1 and 1 to %d distinct fields of [0, %d)' % (F, F))
+        ctx, cand, nctx, N, stride = self._cand_lists(ctx, cand, nf, 'score_candidate_tuples')
+        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
+        key = ('cand_ids', block)
+        ids = self._ws.get(key)
+        if ids is None:
+            ids = torch.empty((block, F), dtype=torch.int32, device=self.device)
+            self._ws[key] = ids
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        flat, st = scores.view(-1), self._stream()
+        for s0 in range(0, nctx * N, block):
+            m = min(block, nctx * N - s0)
+            buf, _ = self.workspace(m)
+            hip.check(self.lib.cffm_expand_candidates_ex(self._s, _ptr(ctx), nctx, C.addressof(host_fields), nf, _ptr(cand), stride, N,
+                                                         s0, m, _ptr(ids), st))
+            hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
+        return scores
+
     def sweep_ok(self):
         """True where score_candidates_shared serves this engine's shape (cffm_sweep_ok, include/cffm_hip.h)."""
         return bool(self.lib.cffm_sweep_ok(self._s))
@@ -416,14 +456,36 @@ class HipEngine(object):
         scores = torch.empty((C, N), dtype=torch.float32, device=self.device)
         if C == 0:
             return scores
-        key = 'sweep'
-        scratch = self._ws.get(key)
-        nbytes = int(self.lib.cffm_sweep_scratch_bytes(self._s, C))
+        hip.check(self.lib.cffm_score_sweep(self._s, self._t, _ptr(self.theta), _ptr(ctx), C, int(field), _ptr(cand), N, _ptr(scores),
+                                            N, _ptr(self._sweep_scratch(C)), self._stream()))
+        return scores
+
+    def _sweep_scratch(self, n_ctx):
+        """The grow-only per-context scratch of the two shared sweeps (cffm_sweep_scratch_bytes)."""
+        scratch = self._ws.get('sweep')
+        nbytes = int(self.lib.cffm_sweep_scratch_bytes(self._s, n_ctx))
         if scratch is None or int(scratch.numel()) < nbytes:
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[key] = scratch
-        hip.check(self.lib.cffm_score_sweep(self._s, self._t, _ptr(self.theta), _ptr(ctx), C, int(field), _ptr(cand), N, _ptr(scores),
-                                            N, _ptr(scratch), self._stream()))
+            self._ws['sweep'] = scratch
+        return scratch
+
+    def score_candidate_lists_shared(self, ctx, field, cand):
+        """score_candidates_shared with a candidate list per context: cand int32 [C, N] on the device, row c scored against its own
+        list (cffm_score_sweep_lists) -> fp32 [C, N].  A (context, id) pair gives the bits score_candidates_shared gives it.
+        ValueError for a shape the sweep does not serve (sweep_ok())."""
+        F = int(self.cfg.F)
+        if cand.dim() != 2:
+            raise ValueError('score_candidate_lists_shared: candidates must be [C, N]')
+        ctx, cand, nctx, N, _ = self._cand_lists(ctx, cand.unsqueeze(-1), 1, 'score_candidate_lists_shared')
+        if not 0 <= int(field) < F:
+            raise ValueError('score_candidate_lists_shared: needs 0 <= field < %d' % F)
+        if not self.sweep_ok():
+            raise ValueError('score_candidate_lists_shared: the shared sweep does not serve this shape (both branches, D = 32, F <= 10)')
+        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
+        if nctx == 0:
+            return scores
+        hip.check(self.lib.cffm_score_sweep_lists(self._s, self._t, _ptr(self.theta), _ptr(ctx), nctx, int(field), _ptr(cand), N, N,
+                                                  _ptr(scores), N, _ptr(self._sweep_scratch(nctx)), self._stream()))
         return scores
 
     def _rank_args(self, scores, skip):

@@ -392,6 +392,20 @@ int cffm_eval_sums(const float *pred, const float *y, int64_t n, float lo, float
  * Writes exactly rows * F int32 values and nothing else.  Ids are not validated: cffm_predict clamps them as it always does. */
 int cffm_expand_candidates(const cffm_shape_t *s, const int32_t *ctx, int32_t C, int32_t field, const int32_t *cand, int32_t N,
                            int64_t first, int32_t rows, int32_t *ids_out, void *stream);
+/* cffm_expand_candidates_ex: the same rows for candidates that are TUPLES of nf ids put at nf columns together, from one list for
+ * every context or from a list per context.  fields: HOST int32 [nf], distinct columns of [0, F), read before the launch like s (it
+ * reaches the kernel by value as a slot map of CFFM_MAX_FIELDS entries: no device copy, no synchronisation).  cand: device int32,
+ * id a (a < nf) of candidate n of context c at cand[c * cand_ctx_stride + n * nf + a] (indexed in 64 bits).  cand_ctx_stride == 0:
+ * one list [N][nf] for every context; otherwise the elements between the lists of two contexts, >= N * nf - what lies beyond
+ * N * nf of a context's block is never read.  For global row g in [first, first + rows), c = g / N, n = g % N:
+ * ids_out[g - first][f] = (f == fields[a]) ? cand[c * cand_ctx_stride + n * nf + a] : ctx[c][f].  Writes exactly rows * F int32
+ * values.  nf == 1 with stride 0 writes what cffm_expand_candidates writes (that entry point forwards here).
+ * CFFM_ERR_BAD_SHAPE, before any launch, for: nf < 1; nf > F; fields == NULL; a field outside [0, F); the same field twice; N < 1;
+ * C < 0; first < 0; rows < 0; first + rows > C * N; a negative stride; a non-zero stride below N * nf; a NULL pointer that would
+ * be read or written.  C == 0 or rows == 0 returns 0 without a launch. */
+int cffm_expand_candidates_ex(const cffm_shape_t *s, const int32_t *ctx, int32_t C, const int32_t *fields, int32_t nf,
+                              const int32_t *cand, int64_t cand_ctx_stride, int32_t N, int64_t first, int32_t rows,
+                              int32_t *ids_out, void *stream);
 /* cffm_topk: for every row c the m = min(k, N - skipped) best candidates in descending order: idx_out[c][j] = candidate position,
  * val_out[c][j] = its score bit for bit (j < m); idx_out[c][j] = -1 and val_out[c][j] = the bits 0x7fc00000 for m <= j < k;
  * count_out[c] = m.  1 <= k <= 1024.  scratch: cffm_topk_scratch_bytes(C, N, k) bytes (< 0 on bad arguments; never smaller for a
@@ -423,6 +437,15 @@ int cffm_sweep_ok(const cffm_shape_t *s);
 int64_t cffm_sweep_scratch_bytes(const cffm_shape_t *s, int32_t C);
 int cffm_score_sweep(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
                      int32_t field, const int32_t *cand, int32_t N, float *scores, int64_t row_stride, void *scratch, void *stream);
+/* cffm_score_sweep_lists: cffm_score_sweep with a candidate list per context: candidate n of context c is
+ * cand[c * cand_ctx_stride + n] (indexed in 64 bits); cand_ctx_stride == 0 is the one shared list, otherwise it is >= N and what lies
+ * beyond N of a context's block is never read.  The same two kernels, served domain (cffm_sweep_ok) and scratch
+ * (cffm_sweep_scratch_bytes).  A (context, id) pair gives the same bits under a shared list, under its own list, at any position
+ * and on every call.  One field only: tuples (cffm_expand_candidates_ex with nf > 1) are not served by the sweep.  Refusals: those
+ * of cffm_score_sweep, in the same order, plus CFFM_ERR_BAD_SHAPE for a negative stride or a non-zero stride below N. */
+int cffm_score_sweep_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
+                           int32_t field, const int32_t *cand, int64_t cand_ctx_stride, int32_t N, float *scores, int64_t row_stride,
+                           void *scratch, void *stream);
 
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
