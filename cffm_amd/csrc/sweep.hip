@@ -39,6 +39,7 @@
 #define SWEEP_D 32                     // served outer dimension: C_0 16x16, C_1 8x8, C_2 4x4, C_3 2x2 (live = 4)
 #define SWEEP_S 16
 #define SWEEP_MAXPP 48                 // F <= 10
+#define SWEEP_HEADER 256               // bytes of the scratch in front of the first context's block
 
 namespace {
 
@@ -661,7 +662,21 @@ extern "C" int cffm_sweep_ok(const cffm_shape_t* s) {
 extern "C" int64_t cffm_sweep_scratch_bytes(const cffm_shape_t* s, int32_t C) {
     if (C < 0 || !cffm_sweep_ok(s)) return -1;
     const Geo g = make_geo(s);
-    return 256 + (int64_t)C * sweep_block(g.Pp, g.F, g.K).floats * 4;
+    return SWEEP_HEADER + (int64_t)C * sweep_block(g.Pp, g.F, g.K).floats * 4;
+}
+
+extern "C" int cffm_sweep_block_layout(const cffm_shape_t* s, cffm_sweep_block_t* out) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (!out) return CFFM_ERR_BAD_SHAPE;
+    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
+    const Geo g = make_geo(s);
+    const SweepBlock b = sweep_block(g.Pp, g.F, g.K);
+    out->header_floats = SWEEP_HEADER / 4;
+    out->block_floats = b.floats;
+    out->Z = b.Z; out->U = b.U; out->V = b.V; out->Ei = b.Ei;
+    out->s0fix = b.s0fix; out->A = b.A; out->fb = b.fb; out->scal = b.scal;
+    return 0;
 }
 
 // both entry points: cand_ctx_stride == 0 is the shared list of cffm_score_sweep
@@ -681,7 +696,7 @@ static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const floa
     rc = cffm_theta_layout(s, &tl);
     if (rc) return rc;
     const SweepBlock bo = sweep_block(g.Pp, g.F, g.K);
-    float* blocks = reinterpret_cast<float*>((char*)scratch + 256);
+    float* blocks = reinterpret_cast<float*>((char*)scratch + SWEEP_HEADER);
     SweepCtxArgs ca;
     ca.g = g;
     ca.inner = tab->inner_emb; ca.outer = tab->outer_emb; ca.fbias = tab->feat_bias;

@@ -91,6 +91,7 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_sweep_scratch_bytes);
     CFFM_BIND(cffm_score_sweep);
     CFFM_BIND(cffm_score_sweep_lists);
+    CFFM_BIND(cffm_sweep_block_layout);
     CFFM_BIND(cffm_probe_copy);
     CFFM_BIND(cffm_probe_read);
     CFFM_BIND(cffm_probe_mfma);

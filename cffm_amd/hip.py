@@ -67,6 +67,10 @@ class ConvChoice(C.Structure):
                 ('top_wgrad_deferred', C.c_int32)]
 
 
+class SweepBlock(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ('header_floats', 'block_floats', 'Z', 'U', 'V', 'Ei', 's0fix', 'A', 'fb', 'scal')]
+
+
 class Tables(C.Structure):
     _fields_ = [('inner_emb', C.c_void_p), ('outer_emb', C.c_void_p), ('feat_bias', C.c_void_p)]
 
@@ -127,6 +131,7 @@ PROTOTYPES = {
     'cffm_sweep_scratch_bytes': (C.c_int64, [_SH, C.c_int32]),
     'cffm_score_sweep': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, _P]),
     'cffm_score_sweep_lists': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
+    'cffm_sweep_block_layout': (C.c_int, [_SH, _P]),
     'cffm_probe_copy': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_read': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_mfma': (C.c_int, [_P, C.c_int32, _P, _P]),
@@ -222,6 +227,13 @@ def ws_layout(shape, B):
     check(load().cffm_ws_layout(C.byref(shape), int(B), C.byref(wl)))
     return wl
 
+
+
+def sweep_block_layout(shape):
+    """Where the shared sweep leaves its per-context intermediates in its scratch (cffm_sweep_block_layout, include/cffm_hip.h)."""
+    bl = SweepBlock()
+    check(load().cffm_sweep_block_layout(C.byref(shape), C.byref(bl)))
+    return bl
 
 
 def conv_choice(shape, B, layer):

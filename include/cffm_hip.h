@@ -446,6 +446,19 @@ int cffm_score_sweep(const cffm_shape_t *s, const cffm_tables_t *tab, const floa
 int cffm_score_sweep_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
                            int32_t field, const int32_t *cand, int64_t cand_ctx_stride, int32_t N, float *scores, int64_t row_stride,
                            void *scratch, void *stream);
+/* Where the sweep's intermediates lie in the scratch, for the per-stage tests (host only, reads nothing but *s): context c's block
+ * starts header_floats + c * block_floats floats into the scratch, and every other member is the offset, in floats from the start
+ * of a block, of one tensor the context kernel leaves there (Pp = pairs padded to 16, f = the swept field):
+ *   Z [16][16][Pp]  U [2][16][Pp] (dw, y, q)  V [2][16][Pp] (dh, x, q)  Ei [F][K] (row f zero)  s0fix [32]  A [32]
+ *   fb [16] (slot f and slots >= F zero)  scal [16] ([0] the inner sum of the pairs without f, [1] R; the rest is never written)
+ * What lies between the end of scal and block_floats is never written either.  (header_floats + C * block_floats) * 4 ==
+ * cffm_sweep_scratch_bytes(s, C).  Refusals as cffm_sweep_scratch_bytes: CFFM_ERR_BAD_SHAPE for a NULL pointer or a shape the shape
+ * check refuses, CFFM_ERR_UNSUPPORTED for a shape that is not served; *out is then untouched.  Additive: the version stays 9. */
+typedef struct cffm_sweep_block {
+    int64_t header_floats, block_floats;
+    int64_t Z, U, V, Ei, s0fix, A, fb, scal;
+} cffm_sweep_block_t;
+int cffm_sweep_block_layout(const cffm_shape_t *s, cffm_sweep_block_t *out);
 
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */

@@ -1,4 +1,4 @@
-"""The shared candidate sweep's entry points (cffm_sweep_ok, cffm_sweep_scratch_bytes, cffm_score_sweep): what they return before any
+"""The shared candidate sweep's entry points (cffm_sweep_ok, cffm_sweep_scratch_bytes, cffm_sweep_block_layout, cffm_score_sweep): what they return before any
 device work, through both bindings.  Every refusal include/cffm_hip.h lists comes back ahead of the first launch or HIP call, so
 the pointers here are dummies that are never read - a case that got any further would fault on them - and no GPU is needed."""
 import ctypes as C
@@ -30,7 +30,7 @@ def shape(**kw):
 
 
 def test_the_entry_points_are_declared_in_both_bindings():
-    for name in ('cffm_sweep_ok', 'cffm_sweep_scratch_bytes', 'cffm_score_sweep'):
+    for name in ('cffm_sweep_ok', 'cffm_sweep_scratch_bytes', 'cffm_score_sweep', 'cffm_sweep_block_layout'):
         assert name in hip.PROTOTYPES and hasattr(hip.load(), name) and hasattr(hip.fast(), name), name
     assert hip.load().cffm_abi_version() == 9                              # additive: the version stays
     header = open(os.path.join(ROOT, 'include', 'cffm_hip.h')).read()
@@ -77,6 +77,39 @@ def test_scratch_bytes(lib):
             last = b
     # a context's block holds at least Zctx [16][16][Pp], U [2][16][Pp] and V [2][16][Pp]
     assert f(C.addressof(good), 3) - f(C.addressof(good), 2) >= (256 + 64) * 48 * 4
+
+
+MEMBERS = ('Z', 'U', 'V', 'Ei', 's0fix', 'A', 'fb', 'scal')
+
+
+def test_block_layout(lib):
+    f, nbytes = lib.cffm_sweep_block_layout, lib.cffm_sweep_scratch_bytes
+    good = shape(F=10, K=32)
+    untouched = hip.SweepBlock(*([-7] * 10))
+    # refused where the scratch-bytes call refuses: no shape, a shape the shape check refuses, a shape that is not served, no result
+    assert f(0, C.addressof(untouched)) == BAD and f(C.addressof(good), 0) == BAD
+    for kw, want in ((dict(F=1), BAD), (dict(K=6), BAD), (dict(inner_conv=0), UNSUPPORTED), (dict(D=64), UNSUPPORTED), (dict(F=11), UNSUPPORTED),
+                     (dict(D=8), UNSUPPORTED), (dict(F=10, K=4096), UNSUPPORTED)):
+        s = shape(**kw)
+        assert nbytes(C.addressof(s), 4) < 0, kw
+        assert f(C.addressof(s), C.addressof(untouched)) == want, kw
+    assert all(getattr(untouched, n) == -7 for n, _ in hip.SweepBlock._fields_)          # a refusal writes nothing
+    for F in range(2, 11):
+        for K in (4, 8, 16, 32, 64):
+            s, bl = shape(F=F, K=K), hip.SweepBlock()
+            assert f(C.addressof(s), C.addressof(bl)) == 0, (F, K)
+            offs = [getattr(bl, n) for n in MEMBERS]
+            assert offs[0] == 0 and all(a < b for a, b in zip(offs, offs[1:])) and all(o % 4 == 0 for o in offs), (F, K, offs)
+            assert bl.header_floats * 4 == 256 and bl.block_floats % 4 == 0 and bl.block_floats >= bl.scal + 16, (F, K)
+            Pp = (F * (F - 1) // 2 + 15) // 16 * 16
+            # every tensor has room in front of the next one
+            sizes = dict(Z=256 * Pp, U=32 * Pp, V=32 * Pp, Ei=F * K, s0fix=32, A=32, fb=16)
+            for a, b in zip(MEMBERS, MEMBERS[1:]):
+                assert getattr(bl, b) - getattr(bl, a) >= sizes[a], (F, K, a)
+            for C_ in (0, 1, 3, 260, 1 << 20):
+                assert (bl.header_floats + C_ * bl.block_floats) * 4 == nbytes(C.addressof(s), C_), (F, K, C_)
+    bl = hip.sweep_block_layout(good)                                            # the helper the tests read the scratch through
+    assert (bl.header_floats + 2 * bl.block_floats) * 4 == nbytes(C.addressof(good), 2)
 
 
 def sweep(lib, s, tab=None, theta=P, ctx=P, C_=2, field=1, cand=P, N=5, scores=P, row_stride=5, scratch=P):
