@@ -100,8 +100,11 @@ static inline int check_shape(const cffm_shape_t* s) {
 //   head forward    t1s [1024] + hpart [8][32] + rs [CFFM_MAX_FIELDS] + sc [4] + Et [F][D] + aW [F][F]
 //   inner forward   E [F][K] + pair lut [Pp] + up to 16 wavefront partials
 //   inner backward  E [F][K] + dE [4][F][K] + pair lut [Pp] + red [8]
-static inline size_t head_fwd_lds(const Geo& g) { return (size_t)(1024 + 8 * CFFM_HEAD_UNITS + CFFM_MAX_FIELDS + 4 + g.F * g.D + g.F * g.F) * 4 + 16; }
-static inline size_t inner_fwd_lds(const Geo& g) { return ((size_t)g.F * g.K + g.Pp + 16) * 4; }   // size_t: K has no upper bound
+// (the constexpr forms also size the LDS plan of the compiled-shape fused forward at compile time, conv.hip)
+static constexpr size_t head_fwd_lds(int F, int D) { return (size_t)(1024 + 8 * CFFM_HEAD_UNITS + CFFM_MAX_FIELDS + 4 + F * D + F * F) * 4 + 16; }
+static constexpr size_t inner_fwd_lds(int F, int K, int Pp) { return ((size_t)F * K + Pp + 16) * 4; }   // size_t: K has no upper bound
+static inline size_t head_fwd_lds(const Geo& g) { return head_fwd_lds(g.F, g.D); }
+static inline size_t inner_fwd_lds(const Geo& g) { return inner_fwd_lds(g.F, g.K, g.Pp); }
 static inline size_t inner_bwd_lds(const Geo& g) { return ((size_t)5 * g.F * g.K + g.Pp + 8) * 4; }
 // check_shape() bounds F and D but not K, so a shape it accepts can ask the inner-branch kernels for more LDS than a CU has (the
 // backward from F * K ~ 7,560 .. 8,160 on).  The head tops out at 152,864 bytes (F = 64 at D = 512) and always fits.  Such a shape is

@@ -1355,10 +1355,12 @@ extern "C" int cffm_debug_phase_times(unsigned long long* host16) {
 // whose rows lie beyond m_hi only helps staging the filter and keeps the barriers.
 // inL / outL (fused forward only): LDS copies of this example's input / output activations, [rows][PP], rows counted
 // from m_base; the A operand then never touches global memory and the output is left where the next phase reads it.
-template <int NT, int RM, bool GEN, int G = 1, int ACTC = -1>
+// LGSO >= 0 (compiled-shape fused forward): log2 of the layer's output side as a constant, so that the row arithmetic folds
+template <int NT, int RM, bool GEN, int G = 1, int ACTC = -1, int LGSO = -1>
 __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0_wg, int64_t m_hi, char* smem,
                                                    const float* inL = nullptr, float* outL = nullptr, int64_t m_base = 0) {
     const int act = ACTC >= 0 ? ACTC : a.act;           // ACTC >= 0: compile-time activation id (README shapes)
+    const int lgSo = LGSO >= 0 ? LGSO : a.lgSo;
     constexpr int PP = NT * 16, LDW = PP + 4, BM = 16 * RM;
     float* Wl = reinterpret_cast<float*>(smem);                // [4][PP/4 row groups][4*PP + 16]; reused as the reduction buffer
     uint32_t* lut = reinterpret_cast<uint32_t*>(Wl + 4 * PP * LDW);      // [PP]            (GEN)
@@ -1366,8 +1368,8 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
     const int tid = threadIdx.x, lane = tid & 63, tap = (tid >> 6) & 3, grp = tid >> 8, r = lane & 15, kk = lane >> 4;
     const int64_t m0 = m0_wg + (int64_t)grp * BM;
     const bool work = m0 < m_hi;
-    const int So = 1 << a.lgSo, Sin = 2 * So, Dp = a.D + 1, dh = tap >> 1, dw = tap & 1;
-    const int b0 = (int)(m0 >> (2 * a.lgSo));
+    const int So = 1 << lgSo, Sin = 2 * So, Dp = a.D + 1, dh = tap >> 1, dw = tap & 1;
+    const int b0 = (int)(m0 >> (2 * lgSo));
 
     PHASE_MARK2(0);
     // ---- issue every global load of this wave ----------------------------------------------------------
@@ -1396,7 +1398,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
         for (int rm = 0; rm < RM; ++rm) {
             int64_t m = m0 + rm * 16 + r;
             if (m >= m_hi) m = m_hi - 1;
-            const RowPos rp = row_pos(m, a.lgSo);
+            const RowPos rp = row_pos(m, lgSo);
             const float* src = inL ? inL + ((2 * rp.y + dh) * Sin + 2 * rp.x + dw) * PP + 4 * kk
                                    : a.in + (((int64_t)rp.b * Sin + 2 * rp.y + dh) * Sin + 2 * rp.x + dw) * PP + 4 * kk;
 #pragma unroll
@@ -1428,7 +1430,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
         for (int rm = 0; rm < RM; ++rm) {
             int64_t m = m0 + rm * 16 + r;
             if (m >= m_hi) m = m_hi - 1;
-            const RowPos rp = row_pos(m, a.lgSo);
+            const RowPos rp = row_pos(m, lgSo);
             const int eoff = (rp.b - b0) * a.F * Dp;
             const int iy = eoff + 2 * rp.y + dh, jx = eoff + 2 * rp.x + dw;
 #pragma unroll
@@ -1643,11 +1645,12 @@ __global__ __launch_bounds__(256) void conv_fwd_rows_kernel(ConvArgs a) {
 //                             A fragment = one ds_read of E, B fragment = one ds_read of the staged filter.
 //   step 2, wave w owns x = w, w+4, ...: rows y, k = (dh, i), B fragment = T[(dh,i)][x][q] (row pitch padded by
 //                             16 floats so the two k rows of a half-wave hit disjoint banks).
-template <int NT, int NW = 4>
+template <int NT, int NW = 4, int F_ = 0, int D_ = 0>
 // staged (fused forward): the caller has put the filter and the embedding tile into LDS and passed the barrier
+// F_ / D_ != 0: the shape compiled in (as conv0_fact_bwd_body does it): pair indexing, divisions and loop bounds fold
 __device__ __forceinline__ void conv0_fact_fwd_body(const ConvArgs& a, int b, char* smem, float* outL = nullptr, bool staged = false) {
     constexpr int PP = NT * 16, NTH = 64 * NW, XQ = 16 / NW;      // NW wavefronts; step 2 gives each XQ columns at a time
-    const int F = a.F, D = a.D, S = D / 2, Dp = D + 1, RT = S / 16;
+    const int F = F_ ? F_ : a.F, D = D_ ? D_ : a.D, S = D / 2, Dp = D + 1, RT = S / 16;
     const int TP = S * PP + 16;                                 // pitch of one (dh, i) plane of T
     float* Wl = reinterpret_cast<float*>(smem);                // [4*PP][PP]
     float* T = Wl + 4 * PP * PP;                                // [2F][TP]
@@ -1756,6 +1759,57 @@ __global__ __launch_bounds__(256) void conv0_fact_fwd_kernel(ConvArgs a) {
 // the packed (id, slot) keys of the sparse update straight from the ids, so the sort costs no launch either.
 // At the frappe shape this replaces 7 launches (~4 us of dispatch + drain each) by one.
 // =================================================================================================
+#define RANK_MAXF 12        // fields whose keys rank_keys_body can place
+// ---- dynamic LDS of the fused forward: one formula for the host (cffm_fwd_all_impl) and for the compiled-shape instance ----------
+// conv_fwd_taps_kernel: the four filter taps (row pitch PP + 4), reused for the cross-wave reduction of RM row tiles
+static constexpr size_t conv_fwd_taps_scratch(int PP, int RM) {
+    const size_t taps = (size_t)4 * PP * (PP + 4) * 4, red = (size_t)4 * RM * (PP / 16) * 64 * 16;
+    return red > taps ? red : taps;
+}
+// conv0_fact_fwd_kernel: filter [4][Pp][Pp] | T planes [2F][S*Pp + 16] | embedding tile [F][D+1]
+static constexpr size_t conv0_fact_t_off(int Pp) { return (size_t)4 * Pp * Pp * 4; }
+static constexpr size_t conv0_fact_t_bytes(int Pp, int F, int D) { return (size_t)2 * F * (D / 2 * Pp + 16) * 4; }
+static constexpr size_t conv0_fact_fwd_lds(int Pp, int F, int D) {
+    return conv0_fact_t_off(Pp) + conv0_fact_t_bytes(Pp, F, D) + (size_t)F * (D + 1) * 4 + 16;
+}
+// Every phase's scratch starts at 0 and the launch gets the largest.  LDS-resident activations: C_0 above every phase's scratch, C_1..
+// above the scratch of the tap kernels / the head (c0_off < 0: they do not fit and go through global memory).  The inner branch and
+// the key placement work in the T planes of layer 0, below the embedding tile, if they fit there (early_fits).
+struct FwdAllLds { int c0_off, c1_off, t_off, es_off; size_t lds; bool early_fits; int live, lgS0; };   // lgS0: log2 of the output side D / 2 of layer 0
+static constexpr FwdAllLds fwd_all_lds_plan(int F, int K, int D, int Pp) {
+    FwdAllLds p{};
+    int live = -1;
+    for (int d = D; d > 1; d >>= 1) ++live;                   // make_geo: live = log2(D) - 1
+    const size_t l_taps = conv_fwd_taps_scratch(Pp, 4) + 64, head = head_fwd_lds(F, D), inner = inner_fwd_lds(F, K, Pp);
+    size_t lds = inner;
+    if (conv0_fact_fwd_lds(Pp, F, D) > lds) lds = conv0_fact_fwd_lds(Pp, F, D);
+    if (l_taps > lds) lds = l_taps;
+    if (head > lds) lds = head;
+    const int S = D / 2;
+    const size_t c0 = (size_t)S * S * Pp * 4;
+    size_t small = 0;
+    for (int l = 1; l < live; ++l) small += (size_t)(D >> (l + 1)) * (D >> (l + 1)) * Pp * 4;
+    size_t low = l_taps > head ? l_taps : head;               // scratch of the phases that run while C_1.. live
+    low = (low + 255) / 256 * 256;
+    size_t base0 = lds > low + small ? lds : low + small;
+    base0 = (base0 + 255) / 256 * 256;
+    p.c0_off = -1; p.c1_off = 0;
+    if (base0 + c0 <= (size_t)CFFM_LDS_WHOLE_CU) {
+        p.c0_off = (int)base0;
+        p.c1_off = (int)low;
+        lds = base0 + c0;
+    }
+    p.lds = lds;
+    const size_t t_off = conv0_fact_t_off(Pp), t_bytes = conv0_fact_t_bytes(Pp, F, D);
+    size_t need = inner;
+    if (need < (size_t)8 * RANK_MAXF * 4) need = (size_t)8 * RANK_MAXF * 4;
+    p.early_fits = need <= t_bytes;
+    p.t_off = (int)t_off;
+    p.es_off = (int)(t_off + t_bytes);
+    p.live = live; p.lgS0 = live;                              // D / 2 = 2^live
+    return p;
+}
+
 struct FwdAllArgs {
     InnerFwdArgs inner;
     ConvArgs conv[CFFM_MAX_LAYERS];
@@ -1774,24 +1828,26 @@ struct FwdAllArgs {
 // Stable sort of the B*F sparse-update keys (id << 32 | slot) without a sort: the keys are unique, so the place of a key
 // is the number of keys below it.  The workgroup of example b places its own F keys - n*F/256 compares per thread,
 // every workgroup in parallel, no extra launch and no serial tail.
-#define RANK_MAXF 12
 // An id outside [0, M) is keyed as M, like every other producer of these keys (gather.hip, inner_body.hpp, pack_keys_kernel): all
 // bad ids form one segment behind the valid ones, which every update kernel skips.
 __device__ __forceinline__ unsigned rank_key_id(int raw, int M) { return min((unsigned)raw, (unsigned)M); }   // raw < 0 wraps above M
-template <int NW>
-__device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, int n, int b, int F, int M,
+// F_ != 0: the field count compiled in: F_ counters and compare chains instead of RANK_MAXF (the ranks are integers: same result)
+template <int NW, int F_ = 0>
+__device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, int n, int b, int F_rt, int M,
                                                unsigned long long* __restrict__ out, char* smem) {
+    constexpr int MAXF = F_ ? F_ : RANK_MAXF;
+    const int F = F_ ? F_ : F_rt;
     float* cnt = reinterpret_cast<float*>(smem);              // [NW waves][RANK_MAXF]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned long long mine[RANK_MAXF];
+    unsigned long long mine[MAXF];
 #pragma unroll
-    for (int f = 0; f < RANK_MAXF; ++f) {
+    for (int f = 0; f < MAXF; ++f) {
         const int slot = b * F + (f < F ? f : 0);
         mine[f] = f < F ? (((unsigned long long)rank_key_id(ids[slot], M) << 32) | (unsigned)slot) : 0ull;
     }
-    int c[RANK_MAXF];
+    int c[MAXF];
 #pragma unroll
-    for (int f = 0; f < RANK_MAXF; ++f) c[f] = 0;
+    for (int f = 0; f < MAXF; ++f) c[f] = 0;
     // n <= 4096 candidates: this thread's ids are fetched in groups of 8 independent loads (one L2 latency per group
     // instead of one per candidate: 10 in a row at the frappe shape)
     constexpr int GRP = 8;
@@ -1807,11 +1863,11 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
             const int j = j0 + 64 * NW * u;
             const unsigned long long kj = j < n ? (((unsigned long long)idj[u] << 32) | (unsigned)j) : ~0ull;   // ~0: below no key
 #pragma unroll
-            for (int f = 0; f < RANK_MAXF; ++f) c[f] += kj < mine[f] ? 1 : 0;
+            for (int f = 0; f < MAXF; ++f) c[f] += kj < mine[f] ? 1 : 0;
         }
     }
 #pragma unroll
-    for (int f = 0; f < RANK_MAXF; ++f) {
+    for (int f = 0; f < MAXF; ++f) {
         const float t = wave_sum((float)c[f]);               // counts <= 4096: exact in fp32
         if (lane == 0) cnt[wave * RANK_MAXF + f] = t;
     }
@@ -1855,55 +1911,107 @@ struct ParkFilter {
     }
 };
 
-template <int NT, int NW, int ACT = -1>
+template <int N> using IntC = std::integral_constant<int, N>;
+#define CV(x) decltype(x)::value
+// fn(IntC<L0>()), .., fn(IntC<L1 - 1>()): a loop whose index is a constant inside every iteration
+template <int L0, int L1, class Fn>
+__device__ __forceinline__ void static_for(Fn&& fn) {
+    if constexpr (L0 < L1) { fn(IntC<L0>()); static_for<L0 + 1, L1>(fn); }
+}
+
+// One conv layer l >= 1 of example b inside the fused forward: rows of this example only, tap-split over the G groups.
+// LGSO >= 0: the layer's output side compiled in - the one taps instance its row count needs is all that is left of the three.
+template <int NT, int G, int ACT, int LGSO = -1>
+__device__ __forceinline__ void fused_layer_fwd(const ConvArgs& ca, int b, char* smem, const float* inL, float* outL) {
+    const int lgSo = LGSO >= 0 ? LGSO : ca.lgSo;
+    const int64_t rows = 1ll << (2 * lgSo), m_lo = (int64_t)b * rows, m_hi = m_lo + rows;
+    if (rows >= 64) {
+        for (int64_t m0 = m_lo; m0 < m_hi; m0 += 64) {
+            if (m0 > m_lo) lds_barrier();
+            conv_fwd_taps_body<NT, 4 / G, false, G, ACT, LGSO>(ca, m0, m_hi, smem, inL, outL, m_lo);
+        }
+    } else if (rows >= 32) {
+        conv_fwd_taps_body<NT, (G >= 2 ? 1 : 2), false, G, ACT, LGSO>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
+    } else {
+        conv_fwd_taps_body<NT, 1, false, G, ACT, LGSO>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
+    }
+}
+
+// F_ / K_ / D_ != 0: the shape compiled in (the frappe command, frappe_shape()).  Field count, row lengths, `live`, the output side of
+// every layer and every LDS offset are constants of the instance (fwd_all_lds_plan at compile time), the layer loop is unrolled,
+// and what the argument block still supplies is pointers, B, M and the two flags.  0: all of it at run time, from the block.
+template <int NT, int NW, int ACT = -1, int F_ = 0, int K_ = 0, int D_ = 0>
 __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
     constexpr int G = NW / 4, PP = NT * 16;
+    constexpr bool CS = F_ != 0;                               // compiled shape
+    constexpr FwdAllLds PL = fwd_all_lds_plan(CS ? F_ : 2, CS ? K_ : 4, CS ? D_ : 4, PP);
+    static_assert(!CS || (F_ * (F_ - 1) / 2 + 15) / 16 * 16 == PP, "NT is the column tile count of F_ fields");
+    static_assert(!CS || (PL.c0_off >= 0 && PL.early_fits), "the compiled shape keeps its activations in LDS and gathers early");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c0_off = CS ? PL.c0_off : fa.c0_off, c1_off = CS ? PL.c1_off : fa.c1_off, es_off = CS ? PL.es_off : fa.es_off;
+    const int D = CS ? D_ : fa.inner.g.D;
+    int live = fa.live;
+    if (CS) { live = -1; for (int d = D_; d > 1; d >>= 1) ++live; }
     // LDS copies of the conv outputs of this example (fa.c_off[l] >= 0): layer l+1 and the head read them there, the
     // global copies (needed by the backward) are written behind the LDS-only barriers and drain in the background
     auto CL = [&](int l) -> float* {
-        return fa.c0_off >= 0 ? reinterpret_cast<float*>(smem + fused_c_off(l, fa.c0_off, fa.c1_off, fa.inner.g.D, PP)) : nullptr;
+        return c0_off >= 0 ? reinterpret_cast<float*>(smem + fused_c_off(l, c0_off, c1_off, D, PP)) : nullptr;
     };
-    const bool lds_act = fa.c0_off >= 0;
+    const bool lds_act = c0_off >= 0;
 #ifdef CFFM_PHASE_TIMERS
     if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x] = wall_clock64();
 #endif
-    for (int b = blockIdx.x; b < fa.B; b += gridDim.x) {
-        if (b != (int)blockIdx.x) __syncthreads();
+    auto example = [&](int b) __attribute__((always_inline)) {
         // early (fa.early_off > 0): the layer-0 filter is fetched first of all, the inner branch works in the LDS that the T
         // planes of layer 0 take later, so that W_0 reaches its LDS place while the gather is in flight, and the gather leaves
         // the outer rows in the embedding tile: layer 0 then starts on LDS-resident operands
         ParkFilter<(4 * PP * PP / 4 + 64 * NW - 1) / (64 * NW), 64 * NW> park;
         const bool early = fa.early_off > 0;
         park.fetch(early ? reinterpret_cast<const float4*>(fa.conv[0].W) : nullptr, reinterpret_cast<float4*>(smem), 4 * PP * PP / 4);
-        char* smem_i = smem + fa.early_off;
-        if (fa.rank_keys) rank_keys_body<NW>(fa.ids, fa.n_rows, b, fa.inner.g.F, fa.inner.g.M, fa.keys_sorted, smem_i);
+        char* smem_i = smem + (CS ? (early ? PL.t_off : 0) : fa.early_off);
+        if (fa.rank_keys) rank_keys_body<NW, F_>(fa.ids, fa.n_rows, b, fa.inner.g.F, fa.inner.g.M, fa.keys_sorted, smem_i);
         PHASE_MARK(0);
         // gathers Ei/Eo/fb of example b (full barrier inside), inner_out[b]
-        inner_fwd_body<ACT>(fa.inner, b, smem_i, early ? reinterpret_cast<float*>(smem + fa.es_off) : nullptr, fa.inner.g.D + 1, park);
+        inner_fwd_body<ACT, decltype(park), F_, K_, D_>(fa.inner, b, smem_i, early ? reinterpret_cast<float*>(smem + es_off) : nullptr,
+                                                        D + 1, park);
         if (lds_act) lds_barrier(); else __syncthreads();
         PHASE_MARK(1);
-        conv0_fact_fwd_body<NT, NW>(fa.conv[0], b, smem, CL(0), early);   // reads Eo[b], writes C_0[b]
-        for (int l = 1; l < fa.live; ++l) {
-            if (lds_act) lds_barrier(); else __syncthreads();
-            PHASE_MARK(1 + l);
-            const ConvArgs& ca = fa.conv[l];
-            const int64_t rows = 1ll << (2 * ca.lgSo), m_lo = (int64_t)b * rows, m_hi = m_lo + rows;
-            if (rows >= 64) {
-                for (int64_t m0 = m_lo; m0 < m_hi; m0 += 64) {
-                    if (m0 > m_lo) lds_barrier();
-                    conv_fwd_taps_body<NT, 4 / G, false, G, ACT>(ca, m0, m_hi, smem, CL(l - 1), CL(l), m_lo);
-                }
-            } else if (rows >= 32) {
-                conv_fwd_taps_body<NT, (G >= 2 ? 1 : 2), false, G, ACT>(ca, m_lo, m_hi, smem, CL(l - 1), CL(l), m_lo);
-            } else {
-                conv_fwd_taps_body<NT, 1, false, G, ACT>(ca, m_lo, m_hi, smem, CL(l - 1), CL(l), m_lo);
+        conv0_fact_fwd_body<NT, NW, F_, D_>(fa.conv[0], b, smem, CL(0), early);   // reads Eo[b], writes C_0[b]
+        if constexpr (CS) {
+            static_for<1, PL.live>([&](auto lc) __attribute__((always_inline)) {
+                constexpr int l = CV(lc), LGSO = PL.lgS0 - l;
+                lds_barrier();
+                PHASE_MARK(1 + l);
+                fused_layer_fwd<NT, G, ACT, LGSO>(fa.conv[l], b, smem, CL(l - 1), CL(l));
+            });
+        } else {
+            for (int l = 1; l < live; ++l) {
+                if (lds_act) lds_barrier(); else __syncthreads();
+                PHASE_MARK(1 + l);
+                fused_layer_fwd<NT, G, ACT>(fa.conv[l], b, smem, CL(l - 1), CL(l));
             }
         }
         if (lds_act) lds_barrier(); else __syncthreads();
-        PHASE_MARK(1 + fa.live);
-        head_fwd_body<NW, ACT>(fa.head, b, smem, lds_act, fa.c0_off, fa.c1_off);
-        PHASE_MARK(2 + fa.live);
+        PHASE_MARK(1 + live);
+        head_fwd_body<NW, ACT, false, F_, D_>(fa.head, b, smem, lds_act, c0_off, c1_off);
+        PHASE_MARK(2 + live);
+    };
+    if constexpr (CS) {
+        // No loop over the passes.  Around a loop the compiler hoists everything that does not depend on b - every per-lane address of
+        // every phase, ~200 registers - in front of it and keeps it alive through all phases: that, not any single phase, is what
+        // filled 256 VGPRs and spilled (the same body without the loop takes 88).  B * F <= 4096 (cffm_fwd_all_ok) bounds the
+        // compiled shape to two passes over a grid of 256, so they are written out; the second one runs for B > 256 only.
+        static_assert(!CS || 4096 / (CS ? F_ : 1) <= 2 * 256, "two passes over a grid of 256 workgroups cover every accepted B");
+        if ((int)blockIdx.x < fa.B) example((int)blockIdx.x);
+        if (const int b = blockIdx.x + gridDim.x; b < fa.B) {
+            __syncthreads();
+            example(b);
+        }
+    } else {
+        for (int b = blockIdx.x; b < fa.B; b += gridDim.x) {
+            if (b != (int)blockIdx.x) __syncthreads();
+            example(b);
+        }
     }
 #ifdef CFFM_PHASE_TIMERS
     if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x + 1] = wall_clock64();
@@ -2870,8 +2978,7 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
 // -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
-template <int N> using IntC = std::integral_constant<int, N>;
-#define CV(x) decltype(x)::value
+// (IntC<N> / CV(x): above static_for)
 // Run-time value -> template argument: go(IntC<V>()) for the V of the list that equals v.  Only the listed values are compiled, and
 // meeting another one is an error.
 template <int... Vs, class Go>
@@ -2900,17 +3007,7 @@ static inline int dgrad0_rows_per_wg(int BM, int lgSo) { const int S2 = 1 << (2 
 static inline int dgrad0_tile_examples(int BM, int lgSo) { return dgrad0_rows_per_wg(BM, lgSo) >> (2 * lgSo); }
 // floats of the pair table + the embedding tiles of n_ex examples (the GEN / L0 instances; 0 for the direct layers)
 static inline size_t emb_tile_floats(int Pp, int n_ex, int F, int D) { return (size_t)Pp + (size_t)n_ex * F * (D + 1); }
-// conv_fwd_taps_kernel: the four filter taps (row pitch PP + 4), reused for the cross-wave reduction of RM row tiles
-static inline size_t conv_fwd_taps_scratch(int PP, int RM) {
-    const size_t taps = (size_t)4 * PP * (PP + 4) * 4, red = (size_t)4 * RM * (PP / 16) * 64 * 16;
-    return red > taps ? red : taps;
-}
-// conv0_fact_fwd_kernel: filter [4][Pp][Pp] | T planes [2F][S*Pp + 16] | embedding tile [F][D+1]
-static inline size_t conv0_fact_t_off(int Pp) { return (size_t)4 * Pp * Pp * 4; }
-static inline size_t conv0_fact_t_bytes(int Pp, int F, int D) { return (size_t)2 * F * (D / 2 * Pp + 16) * 4; }
-static inline size_t conv0_fact_fwd_lds(int Pp, int F, int D) {
-    return conv0_fact_t_off(Pp) + conv0_fact_t_bytes(Pp, F, D) + (size_t)F * (D + 1) * 4 + 16;
-}
+// (conv_fwd_taps_scratch and the conv0_fact_* sizes: above fwd_all_lds_plan, which the compiled-shape fused forward evaluates at compile time)
 
 // The fused small-shape kernels get the activation of the README commands compiled in: frappe = selu at Pp 48 (NT 3), ml-tag =
 // elu and book-crossing = relu at Pp 16 (NT 1) (README.md:20-28); every other (NT, act) reads it at run time (-1).
@@ -2925,6 +3022,12 @@ static int with_readme_act(int act, Go&& go) {
     }
     return go(IntC<-1>());
 }
+
+// The frappe command (README.md:28) - F = 10 (Pp = 48, NT 3), K = D = 32, selu - is the shape bench.py measures: the fused step
+// kernels get it compiled in whole (fwd_all_kernel<3, 8, selu, 10, 32, 32>, conv01_bwd_kernel<3, 10, 32, selu>).  ONE predicate for
+// every launcher; K is part of it (the gather and the inner branch of the forward), so F = 10 with another K, or any other F,
+// keeps the generic instances.
+static inline bool frappe_shape(const Geo& g) { return g.F == 10 && g.K == 32 && g.D == 32 && g.act == CFFM_ACT_SELU; }
 
 // bf16x3 K loop for the 128 x 128 instance of the direct layers (the one the wide shapes run); CFFM_CONV_FP32=1: the fp32 MFMA loop
 static inline bool conv_b3_on() {
@@ -4493,7 +4596,7 @@ int cffm_conv01_bwd_impl(const StepCtx& c, hipStream_t st) {
         hipLaunchKernelGGL((conv01_bwd_kernel<NTV, FV, DV, ACTV>), dim3(256), dim3(1024), lds, st, a);          \
     } while (0)
     const int nt = PP / 16;
-    if (nt == 3 && g.F == 10 && g.act == CFFM_ACT_SELU) CFFM_C01_LAUNCH(3, 10, 32, CFFM_ACT_SELU);     // frappe (README.md:28)
+    if (frappe_shape(g)) CFFM_C01_LAUNCH(3, 10, 32, CFFM_ACT_SELU);
     else if (nt == 3) CFFM_C01_LAUNCH(3, 0, 0, -1);
     else if (nt == 2) CFFM_C01_LAUNCH(2, 0, 0, -1);
     else CFFM_C01_LAUNCH(1, 0, 0, -1);
@@ -4508,9 +4611,24 @@ bool cffm_fwd_all_ok(const cffm_shape_t* s, int32_t B) {
     return s->inner_conv && s->outer_conv && g.Pp <= 64 && conv0_fact_ok(g) && (int64_t)B * s->F <= 4096 && s->F <= RANK_MAXF;
 }
 
+// Which launches of the fused step take the compiled-shape instance at (shape, B): host only, nothing is launched
+extern "C" int cffm_fused_instance(const cffm_shape_t* s, int32_t B) {
+    if (check_shape(s) || B < 1) return CFFM_ERR_BAD_SHAPE;
+    const Geo g = make_geo(s);
+    if (!frappe_shape(g)) return 0;
+    int bits = 0;
+    if (cffm_fwd_all_ok(s, B)) bits |= CFFM_FUSED_INSTANCE_FWD;
+    if (bwd_fused01_ok(s, B) && s->loss != CFFM_LOSS_SQUARE_L2 && g.live == 4 && conv0_fact_bwd_ok(g)) bits |= CFFM_FUSED_INSTANCE_CONV01;
+    return bits;
+}
+
 template <int NT>
 static int launch_fwd_all(const FwdAllArgs& fa, size_t lds, hipStream_t st) {
     constexpr int NW = 8;
+    const dim3 grid(fa.B < 256 ? fa.B : 256), block(64 * NW);
+    if constexpr (NT == 3) {
+        if (frappe_shape(fa.inner.g)) return launch(fwd_all_kernel<3, NW, CFFM_ACT_SELU, 10, 32, 32>, grid, block, lds, st, fa);
+    }
     return with_readme_act<NT>(fa.inner.g.act, [&](auto act) {
         constexpr int ACT = decltype(act)::value;
         int rc = set_lds(fwd_all_kernel<NT, NW, ACT>, lds);
@@ -4537,35 +4655,11 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
     fa.live = g.live; fa.n_rows = B * s->F; fa.B = B;
     fa.rank_keys = rank_keys ? 1 : 0;
     fa.id_bits = id_key_bits(s->M);
-    const int S = g.D / 2, PP = g.Pp;
-    // every phase's scratch starts at 0: the launch gets the largest
-    const size_t l_taps = conv_fwd_taps_scratch(PP, 4) + 64;
-    size_t lds = inner_fwd_lds(g);
-    if (conv0_fact_fwd_lds(PP, g.F, g.D) > lds) lds = conv0_fact_fwd_lds(PP, g.F, g.D);
-    if (l_taps > lds) lds = l_taps;
-    if (head_fwd_lds(g) > lds) lds = head_fwd_lds(g);
-    // LDS-resident activations: C_0 above every phase's scratch, C_1.. above the scratch of the tap kernels / the head
-    {
-        const size_t c0 = (size_t)S * S * PP * 4;
-        size_t small = 0;
-        for (int l = 1; l < g.live; ++l) small += (size_t)(g.D >> (l + 1)) * (g.D >> (l + 1)) * PP * 4;
-        size_t low = l_taps > head_fwd_lds(g) ? l_taps : head_fwd_lds(g);       // scratch of the phases that run while C_1.. live
-        low = (low + 255) / 256 * 256;
-        size_t base0 = lds > low + small ? lds : low + small;
-        base0 = (base0 + 255) / 256 * 256;
-        fa.c0_off = -1; fa.c1_off = 0;
-        if (base0 + c0 <= CFFM_LDS_WHOLE_CU) {
-            fa.c0_off = (int)base0;
-            fa.c1_off = (int)low;
-            lds = base0 + c0;
-        }
-    }
-    {   // the inner branch (and the key placement) must fit into the T planes, below the embedding tile
-        const size_t t_off = conv0_fact_t_off(PP), t_bytes = conv0_fact_t_bytes(PP, g.F, g.D);
-        size_t need = inner_fwd_lds(g);
-        if (need < (size_t)8 * RANK_MAXF * 4) need = (size_t)8 * RANK_MAXF * 4;
-        fa.early_off = (need <= t_bytes && ids != nullptr) ? (int)t_off : 0;
-        fa.es_off = (int)(t_off + t_bytes);
-    }
+    const int PP = g.Pp;
+    const FwdAllLds pl = fwd_all_lds_plan(g.F, g.K, g.D, PP);
+    const size_t lds = pl.lds;
+    fa.c0_off = pl.c0_off; fa.c1_off = pl.c1_off;
+    fa.early_off = (pl.early_fits && ids != nullptr) ? pl.t_off : 0;
+    fa.es_off = pl.es_off;
     return with_int<NT4>(PP / 16, [&](auto nt) { return launch_fwd_all<CV(nt)>(fa, lds, st); });
 }

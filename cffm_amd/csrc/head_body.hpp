@@ -44,7 +44,9 @@ __device__ __forceinline__ float loss_term(float out_raw, float y, int loss, flo
 // POOLS: the stand-alone head of the wide shapes takes s0 and the layer pools as left by earlier kernels (s0_ready, pool[]).  The
 // fused forward instantiates POOLS = false: a.pool[l] / a.pool_np[l] with a run-time l would be a dynamically indexed member of a
 // by-value kernel argument, i.e. a private copy in scratch memory inside the single-launch forward (it cost fwd_all 1.4 us).
-template <int NW = 4, int ACTC = -1, bool POOLS = false>
+// F_ / D_ != 0 (compiled-shape fused forward): field count and outer row length as constants - `live`, the pool sizes, the F loops and
+// the width of t1 fold
+template <int NW = 4, int ACTC = -1, bool POOLS = false, int F_ = 0, int D_ = 0>
 __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* smem, bool CL = false, int c0_off = 0, int c1_off = 0) {
     const int act = ACTC >= 0 ? ACTC : a.g.act;         // ACTC >= 0: compile-time activation id (README shapes)
     constexpr int NTH = 64 * NW, RPW = 16 / NW;                    // rows per wave in one pooling sweep
@@ -53,10 +55,13 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
     float* rs = t1s + 1024 + 8 * CFFM_HEAD_UNITS;                  // [CFFM_MAX_FIELDS]
     float* sc = rs + CFFM_MAX_FIELDS;                              // [4]
     float* Et = sc + 4;                                            // [F][D] embedding tile of this example
-    float* aW = Et + a.g.F * a.g.D;                                // [F][F] attention matrix, staged and used by one wave only
     const Geo& g = a.g;
+    const int F = F_ ? F_ : g.F, D = D_ ? D_ : g.D, Pp = F_ ? (F_ * (F_ - 1) / 2 + 15) / 16 * 16 : g.Pp;
+    int live = g.live;
+    if (D_) { live = -1; for (int d = D_; d > 1; d >>= 1) ++live; }  // make_geo: live = log2(D) - 1
+    float* aW = Et + F * D;                                        // [F][F] attention matrix, staged and used by one wave only
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t1w = 2 * g.D - 2;
+    const int t1w = 2 * D - 2;
     const int q = tid & 31, part = tid >> 5, kpp = (t1w + 7) / 8;
     PHASE_MARK3(0);
     // ---- phase 0: independent loads ------------------------------------------------------------------------
@@ -75,14 +80,14 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
     // the barrier behind the pools waited 1.9 us for wave 1 when it did both (phase timers, frappe)
     constexpr int FO = NW - 1;
     if (wave == FO) {
-        if (lane < g.F) {
-            fbv = a.fb[(int64_t)b * g.F + lane];
+        if (lane < F) {
+            fbv = a.fb[(int64_t)b * F + lane];
             linw = g.linear_att ? a.lin_w[lane] : 0.f;
             attb = g.linear_att ? a.att_b[lane] : 0.f;
         }
         if (g.linear_att) {
             linb = a.lin_b[0];
-            for (int e = lane; e < g.F * g.F; e += 64) aW[e] = a.att_W[e];
+            for (int e = lane; e < F * F; e += 64) aW[e] = a.att_W[e];
         }
     }
     if (wave == 0) {
@@ -95,26 +100,26 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
         }
     }
     if (a.outer_conv && !(POOLS && a.s0_ready)) {
-        const float4* E4 = reinterpret_cast<const float4*>(a.Eo + (int64_t)b * g.F * g.D);
-        for (int i = tid; i < g.F * g.D / 4; i += NTH) reinterpret_cast<float4*>(Et)[i] = E4[i];
+        const float4* E4 = reinterpret_cast<const float4*>(a.Eo + (int64_t)b * F * D);
+        for (int i = tid; i < F * D / 4; i += NTH) reinterpret_cast<float4*>(Et)[i] = E4[i];
     }
     float s0v = 0.f;                                                 // s0_ready: this thread's element of the pool, requested now
-    if (POOLS && a.outer_conv && a.s0_ready && tid < g.D) s0v = a.t1[(int64_t)b * t1w + tid];
+    if (POOLS && a.outer_conv && a.s0_ready && tid < D) s0v = a.t1[(int64_t)b * t1w + tid];
     if (wave == FO) {                                                // first-order term, :422-446 (needs nothing from the other waves)
         float lin;
         if (g.linear_att) {
             float z = attb;
-            for (int gI = 0; gI < g.F; ++gI) {
+            for (int gI = 0; gI < F; ++gI) {
                 const float fg = __shfl(fbv, gI, 64);
-                if (lane < g.F) z += fg * aW[gI * g.F + lane];          // staged by this wavefront above: no barrier needed
+                if (lane < F) z += fg * aW[gI * F + lane];          // staged by this wavefront above: no barrier needed
             }
-            z = lane < g.F ? z / g.lamda_att : -INFINITY;
+            z = lane < F ? z / g.lamda_att : -INFINITY;
             const float mx = wave_max(z);
-            const float e = lane < g.F ? expf(z - mx) : 0.f;
+            const float e = lane < F ? expf(z - mx) : 0.f;
             const float den = wave_sum(e);
             const float at = e / den;
-            if (lane < g.F) a.att[(int64_t)b * g.F + lane] = at;
-            lin = wave_sum(lane < g.F ? fbv * at * linw : 0.f) + linb;
+            if (lane < F) a.att[(int64_t)b * F + lane] = at;
+            lin = wave_sum(lane < F ? fbv * at * linw : 0.f) + linb;
         } else {
             lin = wave_sum(fbv);
         }
@@ -124,9 +129,9 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
     float o = 0.f;
     if (a.outer_conv) {
         // pools of the live layers: s_{l+1}[y] = sum_{x,q} act(C_l[b,y,x,q])                      (:390-391)
-        int off = g.D;
-        for (int l = 0; l < g.live; ++l) {                          // only s_1 .. s_{Lc-1} reach t1 (:394-396)
-            const int S = g.D >> (l + 1);
+        int off = D;
+        for (int l = 0; l < live; ++l) {                          // only s_1 .. s_{Lc-1} reach t1 (:394-396)
+            const int S = D >> (l + 1);
             if (POOLS && !CL && a.pool_np[l] > 0) {                 // the conv epilogue left the partials: add them up in index order
                 const int np = a.pool_np[l];
                 for (int y = tid; y < S; y += NTH) {
@@ -138,9 +143,9 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
                 off += S;
                 continue;
             }
-            const int n4 = S * g.Pp / 4;
-            const float4* base = CL ? reinterpret_cast<const float4*>(smem + fused_c_off(l, c0_off, c1_off, g.D, g.Pp))
-                                    : reinterpret_cast<const float4*>(a.C[l] + (int64_t)b * S * S * g.Pp);
+            const int n4 = S * Pp / 4;
+            const float4* base = CL ? reinterpret_cast<const float4*>(smem + fused_c_off(l, c0_off, c1_off, D, Pp))
+                                    : reinterpret_cast<const float4*>(a.C[l] + (int64_t)b * S * S * Pp);
             // wave w owns rows w, w+4, ...; four rows are swept together so that four loads are in flight per lane
             for (int y0 = wave; y0 < S; y0 += 16) {
                 float s4[RPW];
@@ -168,21 +173,23 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
         lds_barrier();                                             // Et (and the pools) are in LDS
         PHASE_MARK3(3);
         if (POOLS && a.s0_ready) {                                   // kernel-uniform: every thread takes the same side
-            if (tid < g.D) t1s[tid] = s0v;                           // (g.D <= 256 <= NTH on this path: the tiled layer 0 has D <= 64)
+            if (tid < D) t1s[tid] = s0v;                           // (D <= 256 <= NTH on this path: the tiled layer 0 has D <= 64)
         } else {
-        for (int f = wave; f < g.F; f += NW) {                      // row sums of the embedding tile
+        for (int f = wave; f < F; f += NW) {                      // row sums of the embedding tile
             float s = 0.f;
-            for (int d = lane; d < g.D; d += 64) s += Et[f * g.D + d];
+            for (int d = lane; d < D; d += 64) s += Et[f * D + d];
             s = wave_sum(s);
             if (lane == 0) rs[f] = s;
         }
         lds_barrier();
         // s0[h] = sum_{w,p} Eo[i_p][h] * Eo[j_p][w] = sum_i Eo[i][h] * sum_{j>i} rowsum(j)   (:381)
-        for (int h = tid; h < g.D; h += NTH) {
+        for (int h = tid; h < D; h += NTH) {
             float s = 0.f, R = 0.f;
-            for (int i = g.F - 2; i >= 0; --i) {
+            for (int i = F - 2; i >= 0; --i) {
                 R += rs[i + 1];
-                s += Et[i * g.D + h] * R;
+                s = fmaf(Et[i * D + h], R, s);                       // spelled out: with F a constant the loop is unrolled and the
+                                                                     // vectoriser pairs the products into v_pk_mul + add, unfused -
+                                                                     // other bits than the run-time loop's fused multiply-adds
             }
             t1s[h] = s;
         }
@@ -196,7 +203,7 @@ __device__ __forceinline__ void head_fwd_body(const HeadArgs& a, int b, char* sm
 #pragma unroll
                 for (int i = 0; i < HEAD_KPP; ++i) {
                     const int k = part * kpp + i;
-                    if (i < kpp && k < t1w) s += t1s[k] * w1r[i];
+                    if (i < kpp && k < t1w) s = fmaf(t1s[k], w1r[i], s);   // spelled out, as in the s0 pool below: the bound is a constant there
                 }
             } else {
                 for (int k = part * kpp; k < min(t1w, (part + 1) * kpp); ++k) s += t1s[k] * a.d1_w[k * CFFM_HEAD_UNITS + q];

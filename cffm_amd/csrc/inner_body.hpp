@@ -51,11 +51,15 @@ struct InnerFwdArgs {
 // mid(): called once by every thread between the first batch of gather loads and their use - the fused forward parks the
 // layer-0 filter in LDS there (its loads were issued before the gather's and return first).
 struct NoMid { __device__ __forceinline__ void operator()() const {} };
-template <int ACTC = -1, class Mid = NoMid>
+// F_ / K_ / D_ != 0 (compiled-shape fused forward): the field count and the two row lengths as constants - the piece arithmetic of
+// the gather, the unit count and the unit -> (pair, t) split fold
+struct InnerDims { int F, K, P, Pp, D; };
+template <int ACTC = -1, class Mid = NoMid, int F_ = 0, int K_ = 0, int D_ = 0>
 __device__ __forceinline__ void inner_fwd_body(const InnerFwdArgs& ia, int b, char* smem, float* EoL = nullptr, int EoLp = 0,
                                                Mid mid = Mid()) {
-    const Geo& g = ia.g;
-    const int act = ACTC >= 0 ? ACTC : g.act;
+    const InnerDims g = F_ ? InnerDims{F_, K_, F_ * (F_ - 1) / 2, (F_ * (F_ - 1) / 2 + 15) / 16 * 16, D_}
+                           : InnerDims{ia.g.F, ia.g.K, ia.g.P, ia.g.Pp, ia.fg.D};
+    const int act = ACTC >= 0 ? ACTC : ia.g.act;
     const float* Ei = ia.Ei; const float* cw_g = ia.cw; const float* cb_g = ia.cb; const float* wd = ia.wd;
     const float* bd = ia.bd; float* inner_out = ia.inner_out; const FusedGather& fg = ia.fg;
     float* E = reinterpret_cast<float*>(smem);                                   // [F*K]
@@ -63,7 +67,7 @@ __device__ __forceinline__ void inner_fwd_body(const InnerFwdArgs& ia, int b, ch
     float* red = reinterpret_cast<float*>(lut + g.Pp);                          // [4]
     const int FK4 = g.F * g.K / 4;
     if (fg.ids != nullptr) {
-        const int K4 = g.K / 4, D4 = fg.D / 4;
+        const int K4 = g.K / 4, D4 = g.D / 4;
         const int32_t* idb = fg.ids + (int64_t)b * g.F;
         const int n_piece = g.F * (K4 + D4);
         float4 v_first = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -89,7 +93,7 @@ __device__ __forceinline__ void inner_fwd_body(const InnerFwdArgs& ia, int b, ch
                 reinterpret_cast<float4*>(E)[j] = v;
                 reinterpret_cast<float4*>(fg.Ei + (int64_t)b * g.F * g.K)[j] = v;
             } else {
-                reinterpret_cast<float4*>(fg.Eo + (int64_t)b * g.F * fg.D)[j] = v;
+                reinterpret_cast<float4*>(fg.Eo + (int64_t)b * g.F * g.D)[j] = v;
                 if (EoL != nullptr) {
                     float* e = EoL + f * EoLp + 4 * c;
                     e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;

@@ -44,6 +44,7 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_theta_layout);
     CFFM_BIND(cffm_ws_layout);
     CFFM_BIND(cffm_conv_choice);
+    CFFM_BIND(cffm_fused_instance);
     CFFM_BIND(cffm_gather);
     CFFM_BIND(cffm_gather_inner_fwd_ok);
     CFFM_BIND(cffm_gather_inner_fwd);

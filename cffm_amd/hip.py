@@ -86,6 +86,7 @@ PROTOTYPES = {
     'cffm_theta_layout': (C.c_int, [_SH, _P]),
     'cffm_ws_layout': (C.c_int, [_SH, C.c_int32, _P]),
     'cffm_conv_choice': (C.c_int, [_SH, C.c_int32, C.c_int32, _P]),
+    'cffm_fused_instance': (C.c_int, [_SH, C.c_int32]),
     'cffm_gather': (C.c_int, [_SH, _TB, _P, C.c_int32, _P, _P, _P, _P]),
     'cffm_gather_inner_fwd_ok': (C.c_int, [_SH]),
     'cffm_gather_inner_fwd': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, _P, _P]),
@@ -227,6 +228,14 @@ def ws_layout(shape, B):
     check(load().cffm_ws_layout(C.byref(shape), int(B), C.byref(wl)))
     return wl
 
+
+
+def fused_instance(shape, B):
+    """Bit set of the fused step's launches that run the compiled-shape instance at (shape, B) (cffm_fused_instance, include/cffm_hip.h)."""
+    bits = load().cffm_fused_instance(C.byref(shape), int(B))
+    if bits < 0 or bits > 7:                          # an error code, not a bit set
+        check(bits)
+    return bits
 
 
 def sweep_block_layout(shape):

@@ -172,6 +172,14 @@ int cffm_ws_layout(const cffm_shape_t *s, int32_t B, cffm_ws_layout_t *out);
  * (0 <= layer < live) of shape s at batch B >= 1, with the slab count of the real slab plan: the one decision the stages
  * themselves switch on.  Launches nothing.  b3 reflects this process's CFFM_CONV_FP32 latch. */
 int cffm_conv_choice(const cffm_shape_t *s, int32_t B, int32_t layer, cffm_conv_choice_t *out);
+/* Which launches of the fused train step run the instance that has the shape compiled in (the frappe command: F = 10, K = D = 32,
+ * selu), as a bit set; 0 for every other shape and wherever (shape, B) does not take that launch at all.  The conv01 bit also needs
+ * a loss other than square_l2, as the launch does.  Launches nothing; CFFM_ERR_BAD_SHAPE for a shape the shape check refuses or
+ * B < 1.  Additive entry point: CFFM_ABI_VERSION stays 9. */
+#define CFFM_FUSED_INSTANCE_FWD 1     /* fwd_all_kernel<3, 8, selu, 10, 32, 32>                                                    */
+#define CFFM_FUSED_INSTANCE_BWD_TOP 2 /* reserved for bwd_top_kernel: no compiled-shape instance of it exists, the bit is never set */
+#define CFFM_FUSED_INSTANCE_CONV01 4  /* conv01_bwd_kernel<3, 10, 32, selu>                                                        */
+int cffm_fused_instance(const cffm_shape_t *s, int32_t B);
 
 /* ---- stage entry points ------------------------------------------------------------------------ */
 /* tf.nn.embedding_lookup x3 (CFFM.py:303, :354, :422): ids int32 [B*F] -> Ei [B,F,K], Eo [B,F,D],
