@@ -2030,7 +2030,10 @@ __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
 //   F  dEo[f][h] = dEi[(h&1,f)][h>>1] + dEj[(h&1,f)][h>>1] + ds0[h]*R_f + Q_f  (s0 pool gradient in closed form)
 // ~1640 MFMAs per example against 4608 for the direct wgrad + dgrad, no atomics, fixed summation order.
 // wg / nwg: this workgroup's slab and the number of slabs (= workgroups of the launch)
-template <int NT, int F_, int D_, int NW>
+// ONE: the caller guarantees a.B <= nwg, i.e. at most one example per workgroup.  The example loop then ends after its first trip,
+// which is what lets the compiler drop `first`, the read-modify-write arm of the slab stores and the values it otherwise hoists in
+// front of the loop and keeps alive through every phase.
+template <int NT, int F_, int D_, int NW, bool ONE = false>
 __device__ __forceinline__ void conv0_fact_bwd_body(const DgradArgs& a, float* __restrict__ slabW, float* __restrict__ slabB,
                                                     int64_t slab_stride, char* smem, int wg, int nwg) {
     constexpr int PP = NT * 16, S = 16, NTH = 64 * NW, XQ = 16 / NW;     // NW wavefronts (4, 8 or 16), XQ x columns per wave
@@ -2291,6 +2294,7 @@ __device__ __forceinline__ void conv0_fact_bwd_body(const DgradArgs& a, float* _
                                               + a.dt1[(int64_t)b * a.t1w + h] * R + Q;
         }
         first = false;
+        if constexpr (ONE) break;
     }
     PHASE_MARKB(20, wg);
     // ---- bias gradient and empty-slab zeros -----------------------------------------------------------------------------
@@ -2894,7 +2898,8 @@ __global__ __launch_bounds__(1024) void conv01_bwd_kernel(Conv01Args a) {
     }
     __syncthreads();                                         // the weight-gradient LDS is free, dC_0 is complete
     PHASE_MARKB(42, b);
-    conv0_fact_bwd_body<NT, F_, D_, 16>(a.d0, a.slabW0, a.slabB0, a.stride0, smem, b, (int)gridDim.x);
+    // single pass: the launcher refuses B > 256 = gridDim.x (cffm_conv01_bwd_impl), so workgroup b has example b or none
+    conv0_fact_bwd_body<NT, F_, D_, 16, true>(a.d0, a.slabW0, a.slabB0, a.stride0, smem, b, (int)gridDim.x);
 }
 
 // Top of the backward in ONE launch (B <= 256, Pp <= 64): workgroup b runs, for example b, the head backward and then
@@ -2935,7 +2940,8 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
             for (int b = bid; b < a.hb.B; b += a.n_inner) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.hb.g.M, a.keys_sorted, smem);
         }
         PHASE_MARKB(38, bid);
-        inner_bwd_body<ACT>(a.ib, bid, a.n_inner, smem, L);
+        // single pass: the launcher refuses B > n_inner (cffm_bwd_top_impl), so slab bid has example bid or none
+        inner_bwd_body<ACT, true>(a.ib, bid, a.n_inner, smem, L);
         PHASE_MARKB(39, bid);
 #ifdef CFFM_PHASE_TIMERS
         if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x + 1] = wall_clock64();
@@ -4428,6 +4434,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
         ++a.n_layers;
     }
     a.ib = c.inner_bwd_args(&a.n_inner);
+    if (B > a.n_inner || B > 256) return CFFM_ERR_UNSUPPORTED;   // one example per workgroup of either role (inner_bwd_body<ACT, true>)
     a.ib.dout = nullptr;                                     // recomputed from (out, y, L): no dependency on the head role
     a.ib.y = y; a.ib.invB = 1.f / (float)B_global;
     if (o.rank_ids != nullptr && s->F <= RANK_MAXF && (int64_t)B * s->F <= 4096) {
@@ -4571,6 +4578,7 @@ int cffm_conv01_bwd_impl(const StepCtx& c, hipStream_t st) {
     a.d1 = c.dgrad_args(1);
     a.w1 = c.wgrad_args(1); a.w2 = c.wgrad_args(2); a.w3 = c.wgrad_args(3);
     a.n2 = c.conv_slab(2).nslab; a.n3 = c.conv_slab(3).nslab;
+    if (B > 256) return CFFM_ERR_UNSUPPORTED;    // 256 workgroups, at most one example each (conv0_fact_bwd_body<.., true>)
     if (c.conv_slab(0).nslab != 256 || c.conv_slab(1).nslab != 256 || a.n2 > 256 || a.n3 > 256 ||
         (int64_t)a.n2 * CFFM_TOP_SLAB_ROWS < a.w2.Mtot || (int64_t)a.n3 * CFFM_TOP_SLAB_ROWS < a.w3.Mtot)
         return CFFM_ERR_UNSUPPORTED;             // one layer-0/1 slab per workgroup, the 64-row slabs cover layers 2 and 3

@@ -153,7 +153,8 @@ struct InnerBwdArgs {
 };
 // dynamic LDS: inner_bwd_lds(g), common.hpp
 
-template <int ACTC = -1>
+// ONE: the caller guarantees a.B <= nslab (at most one example per slab): the example loop ends after its first trip
+template <int ACTC = -1, bool ONE = false>
 __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, int nslab, char* smem, float L = 1.f) {
     const Geo& g = a.g;
     const int act = ACTC >= 0 ? ACTC : g.act;            // ACTC >= 0: compile-time activation id (README shapes)
@@ -242,6 +243,7 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
         for (int i = threadIdx.x; i < FK; i += blockDim.x)
             dEi[(int64_t)b * FK + i] = ((dE[i] + dE[FK + i]) + dE[2 * FK + i]) + dE[3 * FK + i];
         first = false;
+        if constexpr (ONE) break;
     }
     if (first) {   // this slab saw no example: it must still read as zeros
         for (int64_t i = threadIdx.x; i < (int64_t)g.P * g.K; i += blockDim.x) slab_dw[i] = 0.f;

@@ -10,6 +10,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 
 // One workgroup = 64 groups of four consecutive gradients (every member of theta and every slab range is 16-byte aligned,
@@ -17,8 +18,15 @@
 // meet in LDS and are added in wavefront order.  Bitwise reproducible, and four times the bytes in flight of the
 // one-thread-per-gradient loop it replaces (that one kept 16 x 4-byte loads per lane in flight on 161 workgroups and
 // reached 3 TB/s on the 26 MB of slabs of the frappe step: update_all 11.4 us; this form 9.8 us; an 8-way split over
-// half-wavefronts, twice the workgroups, was slower again at 10.8 us).
+// half-wavefronts, twice the workgroups, was slower again at 10.8 us).  That form asked for its slabs in batches of 8 loads, each
+// batch ending in vmcnt(0) before the next one was issued, behind two dependent vector loads of the dynamically indexed plan entry:
+// about ten serialized round trips.  Now the plan is read with scalar loads and selected with compares, and a quarter's slabs go
+// through a ring of REDUCE_RING loads that never drains (profiles/update_chains.md); the add order is what it was.
 #define REDUCE_GROUPS 64
+#define REDUCE_RING 16
+// The load that follows may not be moved in front of the add that precedes it (an empty statement that the compiler must assume
+// reads the sum and memory): without it the optimizer gathers the adds of a ring in front of its loads and the ring drains.
+#define REDUCE_PIN(s) asm volatile("" : "+v"((s).x), "+v"((s).y), "+v"((s).z), "+v"((s).w) : : "memory")
 static inline int reduce_slab_wgs(int64_t n) { return (int)((n / 4 + REDUCE_GROUPS - 1) / REDUCE_GROUPS); }
 __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restrict__ gpart, int64_t n, const SlabPlan& sp,
                                                   float* __restrict__ grad, float* __restrict__ theta,
@@ -28,17 +36,52 @@ __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restri
     const int64_t i = ((int64_t)bid * REDUCE_GROUPS + g) * 4;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (i < n) {
-        int hit = 0;
-        for (int r = 1; r < sp.n; ++r)
-            if (i >= sp.r[r].off) hit = r;
-        const SlabRange rg = sp.r[hit];
-        const float4* src = reinterpret_cast<const float4*>(gpart + rg.base + (i - rg.off));
-        const int64_t stride = rg.len / 4;
-        const int per = (rg.nslab + 3) / 4, k0 = q * per, k1 = min(rg.nslab, k0 + per);
-#pragma unroll 8
-        for (int k = k0; k < k1; ++k) {                       // independent loads, fixed add order
-            const float4 v = src[(int64_t)k * stride];
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        // the range of i: every entry of the plan is read at a constant index of the argument (scalar loads) and selected with a
+        // compare - a dynamically indexed by-value argument costs two dependent vector loads before the first slab byte is asked for
+        int64_t rel = sp.r[0].base - sp.r[0].off, len = sp.r[0].len;      // slab 0 of gradient i is gpart[rel + i]
+        int nslab = sp.r[0].nslab;
+#pragma unroll
+        for (int r = 1; r < CFFM_MAX_LAYERS + 3; ++r) {
+            const bool hit = r < sp.n && i >= sp.r[r].off;
+            rel = hit ? sp.r[r].base - sp.r[r].off : rel; len = hit ? sp.r[r].len : len; nslab = hit ? sp.r[r].nslab : nslab;
+        }
+        const int64_t stride = len / 4;
+        const int per = (nslab + 3) / 4, k0 = q * per, k1 = min(nslab, k0 + per);
+        if (k0 < k1) {
+            // A ring of REDUCE_RING loads: slab k is added and slab k + REDUCE_RING asked for in its place, so REDUCE_RING - 1 or
+            // REDUCE_RING 16-byte loads per lane are in flight from the first add to the last full ring.  p walks the slabs by the
+            // stride and stops at slab k1 - 1 (a load past the quarter re-reads that slab and is not added).  Add order: k ascending.
+            const float4* p = reinterpret_cast<const float4*>(gpart + rel + i) + (int64_t)k0 * stride;
+            float4 v[REDUCE_RING];
+#pragma unroll
+            for (int j = 0; j < REDUCE_RING; ++j) {
+                v[j] = *p;
+                p += k0 + j + 1 < k1 ? stride : 0;
+            }
+            int k = k0;
+            for (; k + 2 * REDUCE_RING <= k1; k += REDUCE_RING) {       // every slab of the next ring exists
+#pragma unroll
+                for (int j = 0; j < REDUCE_RING; ++j) {
+                    s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w;
+                    REDUCE_PIN(s);
+                    v[j] = *p;
+                    p += stride;
+                }
+            }
+            if (k + REDUCE_RING < k1) {                                  // a last, partial ring (p is at slab k + REDUCE_RING here)
+#pragma unroll
+                for (int j = 0; j < REDUCE_RING; ++j) {
+                    s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w;
+                    REDUCE_PIN(s);
+                    v[j] = *p;
+                    p += k + REDUCE_RING + j + 1 < k1 ? stride : 0;
+                }
+                k += REDUCE_RING;
+            }
+#pragma unroll
+            for (int j = 0; j < REDUCE_RING; ++j) {
+                if (k + j < k1) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
+            }
         }
     }
     part[q][g] = s;
@@ -342,46 +385,99 @@ struct SparseArgs {
 enum { T_INNER = 0, T_OUTER = 1, T_BIAS = 2 };
 static const cffm_tables_t NO_TABLES = {nullptr, nullptr, nullptr};
 
+//
+// The walk of a head: its 64 lanes read the next 64 keys of the run in one load, a ballot gives the number that carry the id (a
+// longer run goes on in chunks of 64), and slot j of the chunk is handed from lane j to all lanes (v_readlane) - no gradient load
+// waits for a key load.  A lane carries NCH columns (lane, lane + 64, ...) through the same walk, the lone bias column of
+// W = K + D + 1 = 65 included: a column past W - 1 reads column W - 1 again and is dropped at the end.  The sink's element (weight
+// and slot) is asked for before the first gradient (sink.pre).  The gradients of 8 / 4 / 2 / 1 slots are asked for together and then
+// added in slot order.
+template <int NCH, class Sink>
+__device__ __forceinline__ void segment_walk_cols(const SparseArgs& a, const Sink& sink, int64_t pos, unsigned long long kq, int id,
+                                                  int c0, int W, int Ki, int lane) {      // kq: key pos + lane
+    const unsigned long long* __restrict__ keys = a.keys;
+    const int64_t n = a.n;
+    const float* gp[NCH];              // column c of slot 0 of block 0
+    int64_t gs[NCH];                   // floats from slot to slot
+    typename Sink::At at[NCH];
+    typename Sink::Pre pre[NCH];
+    float g[NCH];
+    bool live[NCH];
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+        const int c = c0 + ch * 64 + lane;
+        live[ch] = c < W;
+        const int cc = live[ch] ? c : W - 1;
+        // each table is named by a constant where its pointer is read, and the lane's one is selected afterwards (a table number
+        // that depends on the lane indexes the argument struct, which then lives in scratch memory)
+        const bool in_i = cc < Ki, in_o = !in_i && cc < W - 1;
+        const typename Sink::At ai = sink.at(id, T_INNER, in_i ? cc : 0), ao = sink.at(id, T_OUTER, in_o ? cc - Ki : 0),
+                                ab = sink.at(id, T_BIAS, 0);
+        gp[ch] = in_i ? a.dEi + cc : (in_o ? a.dEo + (cc - Ki) : a.dfb);
+        gs[ch] = in_i ? a.sEi : (in_o ? a.sEo : a.sfb);
+        at[ch] = in_i ? ai : (in_o ? ao : ab);
+        pre[ch] = sink.pre(at[ch]);
+        g[ch] = 0.f;
+    }
+    for (int64_t q0 = pos;; q0 += 64) {
+        if (q0 != pos) kq = q0 + lane < n ? keys[q0 + lane] : ~0ull;  // (id -1: never the id of a head that works)
+        const unsigned long long in_run = __ballot((int)(kq >> 32) == id);
+        const int cnt = ~in_run == 0ull ? 64 : __builtin_ctzll(~in_run);     // the run is a prefix of the chunk (sorted keys)
+        int sl = (int)(unsigned)(kq & 0xffffffffull), blk = 0;
+        if (a.run_len > 0) {
+            blk = fast_div(sl, a.inv_run_len);
+            sl -= blk * a.run_len;
+        }
+        // slots j .. j + N - 1 of the chunk: N x NCH loads, then the adds in slot order
+        auto slots = [&](int j, auto N) {
+            float v[decltype(N)::value][NCH];
+#pragma unroll
+            for (int t = 0; t < decltype(N)::value; ++t) {
+                const int64_t s = __builtin_amdgcn_readlane(sl, j + t);
+                const int64_t boff = (int64_t)__builtin_amdgcn_readlane(blk, j + t) * a.run_stride;
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) v[t][ch] = gp[ch][boff + s * gs[ch]];
+            }
+#pragma unroll
+            for (int t = 0; t < decltype(N)::value; ++t)
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) g[ch] += v[t][ch];
+        };
+        int j = 0;
+        for (; j + 8 <= cnt; j += 8) slots(j, std::integral_constant<int, 8>());
+        if (cnt & 4) { slots(j, std::integral_constant<int, 4>()); j += 4; }
+        if (cnt & 2) { slots(j, std::integral_constant<int, 2>()); j += 2; }
+        if (cnt & 1) slots(j, std::integral_constant<int, 1>());
+        if (cnt < 64) break;
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch)
+        if (live[ch]) sink(at[ch], pre[ch], g[ch]);
+}
+
 template <class Sink>
 __device__ __forceinline__ void segment_walk(int bid, const SparseArgs& a, const Sink& sink) {
     const unsigned long long* __restrict__ keys = a.keys;
     const int64_t n = a.n;
-    const int M = a.M, K = a.K, D = a.D;
-    const float* __restrict__ dEi = a.dEi; const float* __restrict__ dEo = a.dEo; const float* __restrict__ dfb = a.dfb;
     const int64_t pos = (int64_t)bid * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (pos >= n) return;
-    const int id = (int)(keys[pos] >> 32);
-    if (pos > 0 && (int)(keys[pos - 1] >> 32) == id) return;          // not a segment head
-    if (id < 0 || id >= M) return;
-    const int W = (dEi ? K : 0) + (dEo ? D : 0) + 1;
-    const int Ki = dEi ? K : 0;
-    for (int c0 = 0; c0 < W; c0 += 64) {
-        const int c = c0 + lane;
-        float g = 0.f;
-        if (c < W) {
-            for (int64_t q = pos; q < n; ++q) {
-                const unsigned long long kq = keys[q];
-                if ((int)(kq >> 32) != id) break;
-                int64_t sl = (int64_t)(kq & 0xffffffffull);
-                int64_t boff = 0;
-                if (a.run_len > 0) {
-                    const int blk = fast_div((int)sl, a.inv_run_len);
-                    boff = (int64_t)blk * a.run_stride;
-                    sl -= (int64_t)blk * a.run_len;
-                }
-                g += c < Ki ? dEi[boff + sl * a.sEi + c] : (c < W - 1 ? dEo[boff + sl * a.sEo + (c - Ki)] : dfb[boff + sl * a.sfb]);
-            }
-            typename Sink::At at;
-            if (c < Ki) at = sink.at(id, T_INNER, c);
-            else if (c < W - 1) at = sink.at(id, T_OUTER, c - Ki);
-            else at = sink.at(id, T_BIAS, 0);
-            sink(at, g);
-        }
-    }
+    // the first 64 keys from pos on and the key in front of pos: one round trip
+    const unsigned long long kq = pos + lane < n ? keys[pos + lane] : ~0ull;
+    const int id_prev = (int)(keys[pos > 0 ? pos - 1 : 0] >> 32);
+    const int id = __builtin_amdgcn_readfirstlane((int)(kq >> 32));
+    if (pos > 0 && id_prev == id) return;                             // not a segment head
+    if (id < 0 || id >= a.M) return;
+    const int W = (a.dEi ? a.K : 0) + (a.dEo ? a.D : 0) + 1;
+    const int Ki = a.dEi ? a.K : 0;
+    if (W <= 64) segment_walk_cols<1>(a, sink, pos, kq, id, 0, W, Ki, lane);
+    else if (W <= 128) segment_walk_cols<2>(a, sink, pos, kq, id, 0, W, Ki, lane);
+    else
+        for (int c0 = 0; c0 < W; c0 += 256) segment_walk_cols<4>(a, sink, pos, kq, id, c0, W, Ki, lane);
 }
 
-// the sinks: At at(id, table, col) and operator()(at, sum).  Element (id, col) of table t of a [M][K] | [M][D] | [M] triple is table_of(T, t)[row_off(..)]:
+// the sinks: At at(id, table, col), Pre pre(at) - what of the element is read, asked for before the sum exists - and
+// operator()(at, pre, sum).  Element (id, col) of table t of a [M][K] | [M][D] | [M] triple is table_of(T, t)[row_off(..)]:
 __device__ __forceinline__ int64_t row_off(int K, int D, int id, int t, int col) {
     if (t == T_INNER) return (int64_t)id * K + col;
     if (t == T_OUTER) return (int64_t)id * D + col;
@@ -400,13 +496,18 @@ struct ApplySink {
     Rule rule;
     float gscale = 1.f;           // LATE only
     struct At { float *w, *s; };
+    struct Pre { float w, s; };
     __device__ __forceinline__ At at(int id, int t, int col) const {
         const int64_t o = row_off(K, D, id, t, col);
         return {table_of(w, t) + o, rule.slot() ? table_of(s, t) + o : nullptr};
     }
-    __device__ __forceinline__ void operator()(const At& a, float g) const {
+    __device__ __forceinline__ Pre pre(const At& a) const { return {*a.w, rule.slot() ? *a.s : 0.f}; }
+    __device__ __forceinline__ void operator()(const At& a, const Pre& p, float g) const {
         if (LATE) g *= gscale;
-        rule(*a.w, a.s, nullptr, g);
+        float wv = p.w, sv = p.s;
+        rule(wv, &sv, nullptr, g);                  // (a rule without a slot does not touch sv)
+        if (rule.slot()) *a.s = sv;
+        *a.w = wv;
     }
 };
 // store into the dense [M][K] | [M][D] | [M] gradient image
@@ -414,8 +515,10 @@ struct StoreSink {
     cffm_tables_t G;
     int K, D;
     typedef float* At;
+    struct Pre {};
     __device__ __forceinline__ At at(int id, int t, int col) const { return table_of(G, t) + row_off(K, D, id, t, col); }
-    __device__ __forceinline__ void operator()(At a, float g) const { *a = g; }
+    __device__ __forceinline__ Pre pre(At) const { return {}; }
+    __device__ __forceinline__ void operator()(At a, const Pre&, float g) const { *a = g; }
 };
 // the tables of store_mask (bit t = table t) have a dense gradient (Adam's non-lazy sparse apply; the regularised loss): their
 // sums go to G* and dense_opt_kernel sweeps every row; the others are applied here, with no late scale
@@ -429,9 +532,11 @@ struct MixSink {
         if ((store_mask >> t) & 1) return {{nullptr, nullptr}, store.at(id, t, col)};
         return {apply.at(id, t, col), nullptr};
     }
-    __device__ __forceinline__ void operator()(const At& a, float g) const {
-        if (a.G) store(a.G, g);
-        else apply(a.a, g);
+    typedef typename ApplySink<Rule, false>::Pre Pre;
+    __device__ __forceinline__ Pre pre(const At& a) const { return a.G ? Pre{0.f, 0.f} : apply.pre(a.a); }
+    __device__ __forceinline__ void operator()(const At& a, const Pre& p, float g) const {
+        if (a.G) store(a.G, StoreSink::Pre(), g);
+        else apply(a.a, p, g);
     }
 };
 
