@@ -412,9 +412,11 @@ __device__ __forceinline__ float row_group_sum(float v) {
 }
 
 // Block-wide sum in a fixed order (bitwise reproducible); red must hold >= blockDim/64 floats.
+// NTH != 0: the block size as a constant of the caller instead of a load from the dispatch packet
+template <int NTH = 0>
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int w = threadIdx.x >> 6, nw = NTH ? NTH >> 6 : (int)blockDim.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[w] = v;
     __syncthreads();
@@ -424,13 +426,15 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // pair p -> packed (i | j << 16) in the reference's row-major i<j order (CFFM.py:304-305)
+template <int NTH = 0>
 __device__ __forceinline__ void build_pair_lut(uint32_t* lut, int F, int Pp) {
-    for (int i = threadIdx.x; i < F; i += blockDim.x) {
+    const int nth = NTH ? NTH : (int)blockDim.x;
+    for (int i = threadIdx.x; i < F; i += nth) {
         int base = i * (2 * F - i - 1) / 2;
         for (int j = i + 1; j < F; ++j) lut[base + j - i - 1] = (uint32_t)i | ((uint32_t)j << 16);
     }
     const int P = F * (F - 1) / 2;
-    for (int p = P + threadIdx.x; p < Pp; p += blockDim.x) lut[p] = 0u;   // padded pairs -> (0,0), weights are 0
+    for (int p = P + threadIdx.x; p < Pp; p += nth) lut[p] = 0u;   // padded pairs -> (0,0), weights are 0
 }
 
 // n / d for 0 <= n < 2^19 and 1 <= d <= 4096 without the ~40-instruction integer division sequence:
@@ -440,4 +444,54 @@ __device__ __forceinline__ int fast_div(int n, float inv_d) { return (int)(((flo
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// loads first
+// ---------------------------------------------------------------------------------------------
+// A staging loop written as `for (e = tid; e < n; e += NTH) dst[e] = f(src[e])` is compiled to load, s_waitcnt vmcnt(0), use, branch:
+// every trip is a full memory round trip and trip k+1's load is not issued before trip k's has returned.  The two helpers below issue
+// a thread's loads together (static register indices only) and consume them afterwards.
+
+// A block of at most N * NTH float4 on its way to LDS: fetch() issues this thread's loads, operator() - called later, for example by
+// inner_fwd_body while the gathered rows are in flight - stores them at their LDS place.  Held by value.
+template <int N, int NTH>
+struct ParkFilter {
+    float4 w[N];
+    float4* dst;
+    int n4;
+    __device__ __forceinline__ void fetch(const float4* src, float4* dst_, int n4_) {
+        dst = dst_; n4 = src != nullptr ? n4_ : 0;
+#pragma unroll
+        for (int ii = 0; ii < N; ++ii) {
+            const int i = threadIdx.x + NTH * ii;
+            w[ii] = i < n4 ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+    __device__ __forceinline__ void operator()() const {
+#pragma unroll
+        for (int ii = 0; ii < N; ++ii) {
+            const int i = threadIdx.x + NTH * ii;
+            if (i < n4) dst[i] = w[ii];
+        }
+    }
+};
+
+// Elements tid, tid + NTH, .. < n of a run-time count: up to U loads of the thread are issued, then consumed in the same ascending
+// order; repeated for n > U * NTH.  Elements past n are predicated off (neither loaded nor consumed).  load(e) -> T, use(e, T).
+template <int U, int NTH, class T, class Load, class Use>
+__device__ __forceinline__ void loads_first(int tid, int n, Load&& load, Use&& use) {
+    for (int e0 = tid; e0 < n; e0 += U * NTH) {
+        T v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * NTH;
+            if (e < n) v[u] = load(e);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * NTH;
+            if (e < n) use(e, v[u]);
+        }
+    }
 }

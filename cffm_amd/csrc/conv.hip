@@ -1887,30 +1887,7 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
 // two wavefronts to switch between, which is what hides the LDS / MFMA / L2 latencies of the per-example phases.
 // ACT >= 0: the activation id compiled in (selu / elu / relu of the three README commands): the act switches of the inner
 // branch, of the A operands of the conv layers and of the pooling sweep fold into straight code
-// The layer-0 filter on its way to LDS: fetch() issues this thread's float4 loads (before the gather's), operator() - called by
-// inner_fwd_body while the gathered rows are in flight - stores them at their LDS place.  Held by value, static indices only.
-template <int N, int NTH>
-struct ParkFilter {
-    float4 w[N];
-    float4* dst;
-    int n4;
-    __device__ __forceinline__ void fetch(const float4* src, float4* dst_, int n4_) {
-        dst = dst_; n4 = src != nullptr ? n4_ : 0;
-#pragma unroll
-        for (int ii = 0; ii < N; ++ii) {
-            const int i = threadIdx.x + NTH * ii;
-            w[ii] = i < n4 ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    __device__ __forceinline__ void operator()() const {
-#pragma unroll
-        for (int ii = 0; ii < N; ++ii) {
-            const int i = threadIdx.x + NTH * ii;
-            if (i < n4) dst[i] = w[ii];
-        }
-    }
-};
-
+// (ParkFilter, the layer-0 filter on its way to LDS: common.hpp)
 template <int N> using IntC = std::integral_constant<int, N>;
 #define CV(x) decltype(x)::value
 // fn(IntC<L0>()), .., fn(IntC<L1 - 1>()): a loop whose index is a constant inside every iteration
@@ -2053,8 +2030,10 @@ __device__ __forceinline__ void conv0_fact_bwd_body(const DgradArgs& a, float* _
     float* sb = slabB + (int64_t)wg * slab_stride;
     PHASE_MARKB(12, wg);
     {
-        const float4* wsrc = reinterpret_cast<const float4*>(a.W);
-        for (int i = tid; i < 4 * PP * PP / 4; i += NTH) reinterpret_cast<float4*>(Wl)[i] = wsrc[i];
+        // the filter: this thread's float4 of it are all requested before the first one is stored
+        ParkFilter<(4 * PP * PP / 4 + NTH - 1) / NTH, NTH> park;
+        park.fetch(reinterpret_cast<const float4*>(a.W), reinterpret_cast<float4*>(Wl), 4 * PP * PP / 4);
+        park();
         // rows of padded pairs (p >= P) are never produced below: they must read as zeros in the reduction
         for (int e = tid; e < 4 * (PP - P) * PP; e += NTH) {
             const int tap = e / ((PP - P) * PP), o = e - tap * ((PP - P) * PP);
@@ -2071,10 +2050,10 @@ __device__ __forceinline__ void conv0_fact_bwd_body(const DgradArgs& a, float* _
         {
             const float* e = a.Cprev + (int64_t)b * F * D;      // Eo rows of this example
             const float invD = 1.f / (float)D;
-            for (int i = tid; i < F * D; i += NTH) {
+            loads_first<2, NTH, float>(tid, F * D, [&](int i) { return e[i]; }, [&](int i, float v) {
                 const int f = fast_div(i, invD), d = i - f * D;
-                Es[f * Dp + d] = e[i];
-            }
+                Es[f * Dp + d] = v;
+            });
         }
         __syncthreads();
         const float* dCb = a.dC + (int64_t)b * S * S * PP;
@@ -2638,10 +2617,14 @@ __device__ __forceinline__ void wgrad_taps_body(const WgradArgs& a, int slab, in
                 }
             __syncthreads();                                   // the caller's previous use of this LDS is over
             {
+                // <= 64 rows of PP / 4 float4 over 256 threads: at most NT per thread, all requested before the first one is stored;
+                // the rows that pad the last k-step are stored as zeros without a load
                 const float4* src = reinterpret_cast<const float4*>(a.dC + m_lo * PP);
-                for (int e = tid; e < nrow * (PP / 4); e += NTH) reinterpret_cast<float4*>(Bs)[e] = src[e];
-                for (int e = nrow * (PP / 4) + tid; e < 4 * nk * (PP / 4); e += NTH)
-                    reinterpret_cast<float4*>(Bs)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4* Bs4 = reinterpret_cast<float4*>(Bs);
+                const int nld = nrow * (PP / 4);
+                loads_first<NT, NTH, float4>(tid, 4 * nk * (PP / 4),
+                    [&](int e) { return e < nld ? src[e] : make_float4(0.f, 0.f, 0.f, 0.f); },
+                    [&](int e, const float4& v) { Bs4[e] = v; });
             }
             __syncthreads();
             PHASE_MARKB(33, dbgw);
@@ -2921,8 +2904,9 @@ struct BwdTopArgs {
     int n_rows;
 };
 
+// (NT <= 3: three workgroups per CU - with 256 + 2 x 256 workgroups at the frappe shape that is what lets every role start at once)
 template <int NT, int ACT = -1>
-__global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
+__global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float dh1s[CFFM_HEAD_UNITS];
     __shared__ float dt1s[1024];
@@ -2933,15 +2917,16 @@ __global__ __launch_bounds__(256) void bwd_top_kernel(BwdTopArgs a) {
 #endif
     if (bid < a.n_inner) {                                   // ---- role 1: inner branch
         PHASE_MARKB(36, bid);
-        const float L = head_bwd_loss(a.hb, false, red);
-        __syncthreads();
-        PHASE_MARKB(37, bid);
-        if (a.rank_ids != nullptr && a.n_keys == 0) {
-            for (int b = bid; b < a.hb.B; b += a.n_inner) rank_keys_body<4>(a.rank_ids, a.n_rows, b, a.hb.g.F, a.hb.g.M, a.keys_sorted, smem);
-        }
-        PHASE_MARKB(38, bid);
-        // single pass: the launcher refuses B > n_inner (cffm_bwd_top_impl), so slab bid has example bid or none
-        inner_bwd_body<ACT, true>(a.ib, bid, a.n_inner, smem, L);
+        // single pass: the launcher refuses B > n_inner (cffm_bwd_top_impl), so slab bid has example bid or none.  The loss sum runs
+        // inside the body, behind the requests for the example's rows, out and y.  (The key placement is never in this role: the
+        // launcher gives it workgroups of its own whenever there are keys to place.)
+        inner_bwd_body<ACT, true>(a.ib, bid, a.n_inner, smem, [&]() __attribute__((always_inline)) {
+            const float L = head_bwd_loss(a.hb, false, red);
+            __syncthreads();
+            PHASE_MARKB(37, bid);
+            PHASE_MARKB(38, bid);
+            return L;
+        });
         PHASE_MARKB(39, bid);
 #ifdef CFFM_PHASE_TIMERS
         if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x + 1] = wall_clock64();

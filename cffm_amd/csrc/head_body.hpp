@@ -288,16 +288,16 @@ __device__ __forceinline__ float head_bwd_loss(const HeadBwdArgs& a, bool publis
             p_sq += 0.5f * (yy - o) * (yy - o);
             p_log -= yy * logf(o + 1e-7f) + (1.f - yy) * logf(1.f - o + 1e-7f);
         }
-        sum = block_sum(p_sq, red);
+        sum = block_sum<256>(p_sq, red);
         __syncthreads();
-        hybrid_log = block_sum(p_log, red);
+        hybrid_log = block_sum<256>(p_log, red);
         __syncthreads();
     } else if (a.unscaled) {
         sum = 0.f;           // not known yet: the caller all-reduces it together with the gradients
     } else if (a.sqerr) {    // same fixed-order sum in every workgroup
         float part = 0.f;
         for (int i = tid; i < a.B; i += 256) part += a.sqerr[i];
-        sum = block_sum(part, red);
+        sum = block_sum<256>(part, red);
         __syncthreads();
     } else {
         sum = a.scalars[3];
@@ -346,10 +346,16 @@ __device__ __forceinline__ void head_bwd_example(const HeadBwdArgs& a, int slab,
             dt1s[k] = s;
             a.dt1[(int64_t)b * t1w + k] = s;
         }
-        for (int e = tid; e < t1w * CFFM_HEAD_UNITS; e += 256) {
-            const int k = e / CFFM_HEAD_UNITS, q = e % CFFM_HEAD_UNITS;
-            const float v = a.t1[(int64_t)b * t1w + k] * dh1s[q];
-            s_d1w[e] = first ? v : s_d1w[e] + v;
+        {   // dense(32) weight gradient, e = k * CFFM_HEAD_UNITS + q: a thread keeps its q while its k advances by 8 per trip; its t1
+            // values are requested in batches of 8, ahead of the multiplies and stores
+            static_assert(256 % CFFM_HEAD_UNITS == 0, "a thread's q does not change from trip to trip");
+            const float* t1b = a.t1 + (int64_t)b * t1w;
+            loads_first<8, 256, float>(tid, t1w * CFFM_HEAD_UNITS,
+                [&](int e) { return t1b[e / CFFM_HEAD_UNITS]; },
+                [&](int e, float t) {
+                    const float v = t * dh1s[e % CFFM_HEAD_UNITS];
+                    s_d1w[e] = first ? v : s_d1w[e] + v;
+                });
         }
         __syncthreads();
         // gradient wrt the top live conv output: only its sum pool feeds the head
@@ -369,12 +375,28 @@ __device__ __forceinline__ void head_bwd_example(const HeadBwdArgs& a, int slab,
             const float sda = wave_sum(da * at);
             const float dz = at * (da - sda) / g.lamda_att;
             float dfbv = dg * at;
-            for (int gI = 0; gI < g.F; ++gI) {
-                const float dzg = __shfl(dz, gI, 64);
+            // The lane's row of att_W is requested first (12 at a time; F <= 11 under the fused top), then come the shuffles and the
+            // sum with gI ascending, and the stores last: a store between two uses would make every use wait for it.
+            constexpr int AW = 12;
+            for (int g0 = 0; g0 < g.F; g0 += AW) {
+                float aw[AW], dzg[AW];
+#pragma unroll
+                for (int u = 0; u < AW; ++u)
+                    if (lane < g.F && g0 + u < g.F) aw[u] = a.att_W[lane * g.F + g0 + u];
+#pragma unroll
+                for (int u = 0; u < AW; ++u) dzg[u] = __shfl(dz, (g0 + u) & 63, 64);
                 if (lane < g.F) {
-                    dfbv += dzg * a.att_W[lane * g.F + gI];
-                    const float v = fbv * dzg;
-                    s_attW[lane * g.F + gI] = first ? v : s_attW[lane * g.F + gI] + v;
+#pragma unroll
+                    for (int u = 0; u < AW; ++u)
+                        if (g0 + u < g.F) dfbv += dzg[u] * aw[u];
+#pragma unroll
+                    for (int u = 0; u < AW; ++u) {
+                        const int gI = g0 + u;
+                        if (gI < g.F) {
+                            const float v = fbv * dzg[u];
+                            s_attW[lane * g.F + gI] = first ? v : s_attW[lane * g.F + gI] + v;
+                        }
+                    }
                 }
             }
             if (lane < g.F) a.dfb[(int64_t)b * g.F + lane] = dfbv;

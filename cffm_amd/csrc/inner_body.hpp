@@ -153,9 +153,14 @@ struct InnerBwdArgs {
 };
 // dynamic LDS: inner_bwd_lds(g), common.hpp
 
-// ONE: the caller guarantees a.B <= nslab (at most one example per slab): the example loop ends after its first trip
-template <int ACTC = -1, bool ONE = false>
-__device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, int nslab, char* smem, float L = 1.f) {
+// ONE: the caller guarantees a.B <= nslab (at most one example per slab): the example loop ends after its first trip.  before_loop()
+// -> L is then called between the requests for everything of the example that does not depend on L (its rows, out, y; dE is cleared
+// there too) and the first use of them: the fused top passes its loss sum, whose latency those requests then share.
+// Every caller launches 256 threads: the block size is a constant here, not a load from the dispatch packet.
+struct InnerNoLoss { __device__ __forceinline__ float operator()() const { return 1.f; } };
+template <int ACTC = -1, bool ONE = false, class BeforeLoop = InnerNoLoss>
+__device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, int nslab, char* smem, BeforeLoop&& before_loop = BeforeLoop()) {
+    constexpr int NTH = 256;
     const Geo& g = a.g;
     const int act = ACTC >= 0 ? ACTC : g.act;            // ACTC >= 0: compile-time activation id (README shapes)
     const int B = a.B;
@@ -170,7 +175,7 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
     uint32_t* lut = reinterpret_cast<uint32_t*>(dE + 4 * FK);  // [Pp]
     float* red = reinterpret_cast<float*>(lut + g.Pp);         // [4]
     const int wave = threadIdx.x >> 6;
-    build_pair_lut(lut, g.F, g.Pp);
+    build_pair_lut<NTH>(lut, g.F, g.Pp);
     // alignment gaps of this slab range must read as zeros in the reduction
     if (threadIdx.x < 8) slab_cw[threadIdx.x] = 0.f;          // inner_cw (4) + inner_cb (2 + 2 pad)
     if (threadIdx.x < 4) slab_db[threadIdx.x] = 0.f;          // inner_db (1 + 3 pad)
@@ -186,27 +191,40 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
     float2 w2p[UPRE];
 #pragma unroll
     for (int k = 0; k < UPRE; ++k) {
-        const int u = threadIdx.x + k * blockDim.x;
+        const int u = threadIdx.x + k * NTH;
         w2p[k] = u < units ? wd2[u] : make_float2(0.f, 0.f);
     }
+    // ONE: the first NTH float4 of the example's rows (all of them up to F*K = 1024), out and y
+    ParkFilter<1, NTH> erows;
+    float out1 = 0.f, y1 = 0.f;
+    const bool pre = ONE && a.idx == nullptr && slab < B;
+    if constexpr (ONE) {
+        erows.fetch(pre ? reinterpret_cast<const float4*>(Ei + (int64_t)slab * FK) : nullptr, reinterpret_cast<float4*>(E), FK / 4);
+        if (!dout && slab < B) { out1 = a.out[slab]; y1 = a.y[slab]; }
+        for (int i = threadIdx.x; i < 4 * FK; i += NTH) dE[i] = 0.f;
+    }
+    const float L = before_loop();
     bool first = true;
     for (int b = slab; b < B; b += nslab) {
         // dL/dout of the example: its loads are in flight together with the embedding rows
-        const float db = dout ? dout[b] : head_dout(a.loss, a.out[b], a.y[b], a.invB, L);
+        const float db = dout ? dout[b] : (ONE ? head_dout(a.loss, out1, y1, a.invB, L) : head_dout(a.loss, a.out[b], a.y[b], a.invB, L));
         __syncthreads();
         if (a.idx == nullptr) {
             const float4* src = reinterpret_cast<const float4*>(Ei + (int64_t)b * FK);
-            for (int i = threadIdx.x; i < FK / 4; i += blockDim.x) reinterpret_cast<float4*>(E)[i] = src[i];
+            if constexpr (ONE) erows();
+            for (int i = threadIdx.x + (ONE ? NTH : 0); i < FK / 4; i += NTH) reinterpret_cast<float4*>(E)[i] = src[i];
         } else {                                       // wide shapes: the rows were never materialised, fetch them from the table
             const int K4 = g.K >> 2;
             const float invK4 = 1.f / (float)K4;
-            for (int i = threadIdx.x; i < FK / 4; i += blockDim.x) {
+            for (int i = threadIdx.x; i < FK / 4; i += NTH) {
                 const int f = fast_div(i, invK4), c = i - f * K4;
                 reinterpret_cast<float4*>(E)[i] =
                     reinterpret_cast<const float4*>(row_ptr(Ei, a.idx, a.idxM, (int64_t)b * g.F + f, g.K, a.idxStride))[c];
             }
         }
-        for (int i = threadIdx.x; i < 4 * FK; i += blockDim.x) dE[i] = 0.f;
+        if constexpr (!ONE) {
+            for (int i = threadIdx.x; i < 4 * FK; i += NTH) dE[i] = 0.f;
+        }
         __syncthreads();
         float* myE = dE + wave * FK;
         auto unit_step = [&](int u, float2 w2) {
@@ -234,19 +252,20 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
         };
 #pragma unroll
         for (int k = 0; k < UPRE; ++k) {
-            const int u = threadIdx.x + k * blockDim.x;
+            const int u = threadIdx.x + k * NTH;
             if (u < units) unit_step(u, w2p[k]);
         }
-        for (int u = threadIdx.x + UPRE * blockDim.x; u < units; u += blockDim.x) unit_step(u, wd2[u]);
+#pragma unroll 1
+        for (int u = threadIdx.x + UPRE * NTH; u < units; u += NTH) unit_step(u, wd2[u]);
         if (threadIdx.x == 0) gdb += db;
         __syncthreads();
-        for (int i = threadIdx.x; i < FK; i += blockDim.x)
+        for (int i = threadIdx.x; i < FK; i += NTH)
             dEi[(int64_t)b * FK + i] = ((dE[i] + dE[FK + i]) + dE[2 * FK + i]) + dE[3 * FK + i];
         first = false;
         if constexpr (ONE) break;
     }
     if (first) {   // this slab saw no example: it must still read as zeros
-        for (int64_t i = threadIdx.x; i < (int64_t)g.P * g.K; i += blockDim.x) slab_dw[i] = 0.f;
+        for (int64_t i = threadIdx.x; i < (int64_t)g.P * g.K; i += NTH) slab_dw[i] = 0.f;
     }
     // the seven scalar gradients in ONE block reduction (wavefront partials through the idle dE planes, added in
     // wavefront order): two barriers instead of fourteen
@@ -260,7 +279,7 @@ __device__ __forceinline__ void inner_bwd_body(const InnerBwdArgs& a, int slab, 
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int nw = blockDim.x >> 6;
+        const int nw = NTH >> 6;
 #pragma unroll
         for (int q = 0; q < 7; ++q) {
             float t = 0.f;
