@@ -191,7 +191,10 @@ extern "C" int cffm_predict(const cffm_shape_t* s, const cffm_tables_t* tab, con
     const StepCtx c(s, B, theta, ws);
     FwdOpts fo;
     fo.no_materialise = true;
-    rc = forward_impl(c, step_rows(tab, ids), nullptr, (hipStream_t)stream, fo);
+    // Where the train step runs its forward in one launch (cffm_fwd_all_ok), predict runs that launch too, without labels and without
+    // the key placement: one launch instead of one per stage, and `out` is the train step's `out` on the same ids bit for bit.
+    if (tab && ids && cffm_fwd_all_ok(s, B)) rc = cffm_fwd_all_impl(c, tab, ids, nullptr, (hipStream_t)stream, false);
+    else rc = forward_impl(c, step_rows(tab, ids), nullptr, (hipStream_t)stream, fo);
     if (rc || !out) return rc;
     hipError_t e = hipMemcpyAsync(out, c.at(c.wl.out), (size_t)B * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     return e == hipSuccess ? 0 : (int)e;

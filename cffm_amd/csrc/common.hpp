@@ -412,13 +412,14 @@ __device__ __forceinline__ float row_group_sum(float v) {
 }
 
 // Block-wide sum in a fixed order (bitwise reproducible); red must hold >= blockDim/64 floats.
-// NTH != 0: the block size as a constant of the caller instead of a load from the dispatch packet
+// NTH != 0: the block size as a constant of the caller instead of a load from the dispatch packet.  A workgroup larger than NTH
+// sums its first NTH threads: the later wavefronts pass the barriers and contribute nothing, not even a + 0.f.
 template <int NTH = 0>
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
     const int w = threadIdx.x >> 6, nw = NTH ? NTH >> 6 : (int)blockDim.x >> 6;
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
+    if ((threadIdx.x & 63) == 0 && (NTH == 0 || w < nw)) red[w] = v;
     __syncthreads();
     float t = 0.f;
     for (int i = 0; i < nw; ++i) t += red[i];

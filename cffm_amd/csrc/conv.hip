@@ -1356,7 +1356,10 @@ extern "C" int cffm_debug_phase_times(unsigned long long* host16) {
 // inL / outL (fused forward only): LDS copies of this example's input / output activations, [rows][PP], rows counted
 // from m_base; the A operand then never touches global memory and the output is left where the next phase reads it.
 // LGSO >= 0 (compiled-shape fused forward): log2 of the layer's output side as a constant, so that the row arithmetic folds
-template <int NT, int RM, bool GEN, int G = 1, int ACTC = -1, int LGSO = -1>
+// GT > G (fused forward on more wavefronts than this layer wants): the workgroup has GT groups, the first G of them run the layer
+// exactly as a workgroup of G groups would, the others only pass its three barriers.  The split is by wavefront (a scalar branch);
+// the barriers stay in the straight-line code that every wavefront executes.
+template <int NT, int RM, bool GEN, int G = 1, int ACTC = -1, int LGSO = -1, int GT = G>
 __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0_wg, int64_t m_hi, char* smem,
                                                    const float* inL = nullptr, float* outL = nullptr, int64_t m_base = 0) {
     const int act = ACTC >= 0 ? ACTC : a.act;           // ACTC >= 0: compile-time activation id (README shapes)
@@ -1367,7 +1370,9 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
     float* Es = reinterpret_cast<float*>(lut + PP);           // [n_ex][F][Dp]   (GEN)
     const int tid = threadIdx.x, lane = tid & 63, tap = (tid >> 6) & 3, grp = tid >> 8, r = lane & 15, kk = lane >> 4;
     const int64_t m0 = m0_wg + (int64_t)grp * BM;
-    const bool work = m0 < m_hi;
+    static_assert(GT >= G && (GT == G || !GEN), "idle groups: the fused forward only");
+    const bool active = GT == G || __builtin_amdgcn_readfirstlane(tid >> 8) < G;
+    const bool work = active && m0 < m_hi;
     const int So = 1 << lgSo, Sin = 2 * So, Dp = a.D + 1, dh = tap >> 1, dw = tap & 1;
     const int b0 = (int)(m0 >> (2 * lgSo));
 
@@ -1390,7 +1395,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
 #pragma unroll
     for (int it = 0; it < EPI; ++it) {
         const int idx = tid + it * 256 * G, tile = idx >> 6;
-        bpre[it] = a.bias[(tile % NT) * 16 + (idx & 15)];       // (tile % NT < NT also for idx beyond the last tile)
+        bpre[it] = active ? a.bias[(tile % NT) * 16 + (idx & 15)] : 0.f;   // (tile % NT < NT also for idx beyond the last tile)
     }
     float4 av[RM][NT];
     if (!GEN && work) {
@@ -1414,7 +1419,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
     //  follows a global_load_lds, and in the fused forward the A operands are LDS reads)
     {
         const float4* wsrc = reinterpret_cast<const float4*>(a.W + tap * PP * PP);
-        if (lane < 16 * NT) {
+        if (active && lane < 16 * NT) {
 #pragma unroll
             for (int gI = grp; gI < NGRP; gI += G)
                 __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(wsrc + gI * (16 * NT) + lane),
@@ -1480,6 +1485,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
     lds_barrier();                                           // every wave is done with its W quarter
     PHASE_MARK2(4);
     f32x4* red = reinterpret_cast<f32x4*>(Wl);                 // [4 taps][RT*NT tiles][64 lanes]
+    if (active)
 #pragma unroll
     for (int rm = 0; rm < RM; ++rm)
 #pragma unroll
@@ -1488,7 +1494,7 @@ __device__ __forceinline__ void conv_fwd_taps_body(const ConvArgs& a, int64_t m0
 #pragma unroll
     for (int it = 0; it < EPI; ++it) {
         const int idx = tid + it * 256 * G;
-        if (idx >= RT * NT * 64) break;
+        if (!active || idx >= RT * NT * 64) break;
         const int tile = idx >> 6, ln = idx & 63, rm = tile / NT, nt = tile - rm * NT;
         f32x4 v = red[idx];
         v += red[RT * NT * 64 + idx];
@@ -1775,8 +1781,10 @@ static constexpr size_t conv0_fact_fwd_lds(int Pp, int F, int D) {
 // Every phase's scratch starts at 0 and the launch gets the largest.  LDS-resident activations: C_0 above every phase's scratch, C_1..
 // above the scratch of the tap kernels / the head (c0_off < 0: they do not fit and go through global memory).  The inner branch and
 // the key placement work in the T planes of layer 0, below the embedding tile, if they fit there (early_fits).
+// NW: wavefronts of the instance (fwd_all_wavefronts) - the key placement keeps one row of counters per wavefront; nothing else
+// of the plan depends on it.
 struct FwdAllLds { int c0_off, c1_off, t_off, es_off; size_t lds; bool early_fits; int live, lgS0; };   // lgS0: log2 of the output side D / 2 of layer 0
-static constexpr FwdAllLds fwd_all_lds_plan(int F, int K, int D, int Pp) {
+static constexpr FwdAllLds fwd_all_lds_plan(int F, int K, int D, int Pp, int NW) {
     FwdAllLds p{};
     int live = -1;
     for (int d = D; d > 1; d >>= 1) ++live;                   // make_geo: live = log2(D) - 1
@@ -1802,7 +1810,7 @@ static constexpr FwdAllLds fwd_all_lds_plan(int F, int K, int D, int Pp) {
     p.lds = lds;
     const size_t t_off = conv0_fact_t_off(Pp), t_bytes = conv0_fact_t_bytes(Pp, F, D);
     size_t need = inner;
-    if (need < (size_t)8 * RANK_MAXF * 4) need = (size_t)8 * RANK_MAXF * 4;
+    if (need < (size_t)NW * RANK_MAXF * 4) need = (size_t)NW * RANK_MAXF * 4;   // rank_keys_body: [NW][RANK_MAXF] counters
     p.early_fits = need <= t_bytes;
     p.t_off = (int)t_off;
     p.es_off = (int)(t_off + t_bytes);
@@ -1883,8 +1891,10 @@ __device__ __forceinline__ void rank_keys_body(const int32_t* __restrict__ ids, 
     __syncthreads();
 }
 
-// NW wavefronts per workgroup (8 at the README shapes): one example still owns one workgroup, but every SIMD now has
-// two wavefronts to switch between, which is what hides the LDS / MFMA / L2 latencies of the per-example phases.
+// NW wavefronts per workgroup (8 at the generic instances): one example still owns one workgroup, but every SIMD now has
+// two wavefronts to switch between, which is what hides the LDS / MFMA / L2 latencies of the per-example phases.  The compiled
+// shape runs 16 (four per SIMD): it needs fewer than the 128 VGPRs a 1024-thread workgroup leaves each thread, the generic
+// instances do not (fwd_all_wavefronts).
 // ACT >= 0: the activation id compiled in (selu / elu / relu of the three README commands): the act switches of the inner
 // branch, of the A operands of the conv layers and of the pooling sweep fold into straight code
 // (ParkFilter, the layer-0 filter on its way to LDS: common.hpp)
@@ -1898,30 +1908,42 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 
 // One conv layer l >= 1 of example b inside the fused forward: rows of this example only, tap-split over the G groups.
 // LGSO >= 0: the layer's output side compiled in - the one taps instance its row count needs is all that is left of the three.
-template <int NT, int G, int ACT, int LGSO = -1>
+// GT: groups of the workgroup, of which this layer uses G (conv_fwd_taps_body)
+template <int NT, int G, int ACT, int LGSO = -1, int GT = G>
 __device__ __forceinline__ void fused_layer_fwd(const ConvArgs& ca, int b, char* smem, const float* inL, float* outL) {
     const int lgSo = LGSO >= 0 ? LGSO : ca.lgSo;
     const int64_t rows = 1ll << (2 * lgSo), m_lo = (int64_t)b * rows, m_hi = m_lo + rows;
     if (rows >= 64) {
         for (int64_t m0 = m_lo; m0 < m_hi; m0 += 64) {
             if (m0 > m_lo) lds_barrier();
-            conv_fwd_taps_body<NT, 4 / G, false, G, ACT, LGSO>(ca, m0, m_hi, smem, inL, outL, m_lo);
+            conv_fwd_taps_body<NT, 4 / G, false, G, ACT, LGSO, GT>(ca, m0, m_hi, smem, inL, outL, m_lo);
         }
     } else if (rows >= 32) {
-        conv_fwd_taps_body<NT, (G >= 2 ? 1 : 2), false, G, ACT, LGSO>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
+        conv_fwd_taps_body<NT, (G >= 2 ? 1 : 2), false, G, ACT, LGSO, GT>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
     } else {
-        conv_fwd_taps_body<NT, 1, false, G, ACT, LGSO>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
+        conv_fwd_taps_body<NT, 1, false, G, ACT, LGSO, GT>(ca, m_lo, m_hi, smem, inL, outL, m_lo);
     }
 }
 
 // F_ / K_ / D_ != 0: the shape compiled in (the frappe command, frappe_shape()).  Field count, row lengths, `live`, the output side of
 // every layer and every LDS offset are constants of the instance (fwd_all_lds_plan at compile time), the layer loop is unrolled,
 // and what the argument block still supplies is pointers, B, M and the two flags.  0: all of it at run time, from the block.
+// Groups of four tap-wavefronts that a conv layer l >= 1 of the compiled shape runs on, of the G the workgroup has.  The last layer
+// (2 x 2 outputs: four rows, one tile) measured slower on four groups than on two - the filter DMA is 3 instructions per wavefront
+// instead of 6, and the three barriers wait for twice the wavefronts - so it keeps two and the other wavefronts only pass its
+// barriers (profiles/fwd_all_wavefronts.md has the phase table).
+static constexpr int fwd_all_layer_groups(int G, int lgSo) { return (G > 2 && lgSo <= 1) ? 2 : G; }
+
 template <int NT, int NW, int ACT = -1, int F_ = 0, int K_ = 0, int D_ = 0>
 __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
     constexpr int G = NW / 4, PP = NT * 16;
     constexpr bool CS = F_ != 0;                               // compiled shape
-    constexpr FwdAllLds PL = fwd_all_lds_plan(CS ? F_ : 2, CS ? K_ : 4, CS ? D_ : 4, PP);
+    constexpr FwdAllLds PL = fwd_all_lds_plan(CS ? F_ : 2, CS ? K_ : 4, CS ? D_ : 4, PP, NW);
+    // The compiled shape sums inner_out on 512 threads whatever its workgroup size: that is the grouping every earlier build of it
+    // used, so the value keeps its bits (inner_fwd_body, NTS).  Every other sum of the forward is laid out per wavefront, per thread or
+    // per tap and does not see NW.  0: the generic instances sum on their whole workgroup, as they always did.
+    constexpr int NTS = CS ? 512 : 0;
+    static_assert(!CS || 64 * NW >= NTS, "the workgroup holds the threads that sum inner_out");
     static_assert(!CS || (F_ * (F_ - 1) / 2 + 15) / 16 * 16 == PP, "NT is the column tile count of F_ fields");
     static_assert(!CS || (PL.c0_off >= 0 && PL.early_fits), "the compiled shape keeps its activations in LDS and gathers early");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1949,8 +1971,8 @@ __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
         if (fa.rank_keys) rank_keys_body<NW, F_>(fa.ids, fa.n_rows, b, fa.inner.g.F, fa.inner.g.M, fa.keys_sorted, smem_i);
         PHASE_MARK(0);
         // gathers Ei/Eo/fb of example b (full barrier inside), inner_out[b]
-        inner_fwd_body<ACT, decltype(park), F_, K_, D_>(fa.inner, b, smem_i, early ? reinterpret_cast<float*>(smem + es_off) : nullptr,
-                                                        D + 1, park);
+        inner_fwd_body<ACT, decltype(park), F_, K_, D_, NTS>(fa.inner, b, smem_i, early ? reinterpret_cast<float*>(smem + es_off) : nullptr,
+                                                             D + 1, park);
         if (lds_act) lds_barrier(); else __syncthreads();
         PHASE_MARK(1);
         conv0_fact_fwd_body<NT, NW, F_, D_>(fa.conv[0], b, smem, CL(0), early);   // reads Eo[b], writes C_0[b]
@@ -1959,7 +1981,7 @@ __global__ __launch_bounds__(64 * NW) void fwd_all_kernel(FwdAllArgs fa) {
                 constexpr int l = CV(lc), LGSO = PL.lgS0 - l;
                 lds_barrier();
                 PHASE_MARK(1 + l);
-                fused_layer_fwd<NT, G, ACT, LGSO>(fa.conv[l], b, smem, CL(l - 1), CL(l));
+                fused_layer_fwd<NT, fwd_all_layer_groups(G, LGSO), ACT, LGSO, G>(fa.conv[l], b, smem, CL(l - 1), CL(l));
             });
         } else {
             for (int l = 1; l < live; ++l) {
@@ -3015,10 +3037,15 @@ static int with_readme_act(int act, Go&& go) {
 }
 
 // The frappe command (README.md:28) - F = 10 (Pp = 48, NT 3), K = D = 32, selu - is the shape bench.py measures: the fused step
-// kernels get it compiled in whole (fwd_all_kernel<3, 8, selu, 10, 32, 32>, conv01_bwd_kernel<3, 10, 32, selu>).  ONE predicate for
+// kernels get it compiled in whole (fwd_all_kernel<3, 16, selu, 10, 32, 32>, conv01_bwd_kernel<3, 10, 32, selu>).  ONE predicate for
 // every launcher; K is part of it (the gather and the inner branch of the forward), so F = 10 with another K, or any other F,
 // keeps the generic instances.
 static inline bool frappe_shape(const Geo& g) { return g.F == 10 && g.K == 32 && g.D == 32 && g.act == CFFM_ACT_SELU; }
+// Wavefronts per workgroup of the fused forward.  The compiled shape takes 81 VGPRs and runs 1024 threads, four wavefronts per SIMD
+// to hide its LDS -> MFMA -> store chains behind; the generic instances take 256 VGPRs, which a 1024-thread workgroup cannot have.
+// The launch and the LDS plan (fwd_all_lds_plan) both ask here.
+constexpr int FWD_ALL_NW = 8, FWD_ALL_NW_FRAPPE = 16;
+static inline int fwd_all_wavefronts(const Geo& g) { return frappe_shape(g) ? FWD_ALL_NW_FRAPPE : FWD_ALL_NW; }
 
 // bf16x3 K loop for the 128 x 128 instance of the direct layers (the one the wide shapes run); CFFM_CONV_FP32=1: the fp32 MFMA loop
 static inline bool conv_b3_on() {
@@ -4617,10 +4644,11 @@ extern "C" int cffm_fused_instance(const cffm_shape_t* s, int32_t B) {
 
 template <int NT>
 static int launch_fwd_all(const FwdAllArgs& fa, size_t lds, hipStream_t st) {
-    constexpr int NW = 8;
-    const dim3 grid(fa.B < 256 ? fa.B : 256), block(64 * NW);
+    constexpr int NW = FWD_ALL_NW;
+    const dim3 grid(fa.B < 256 ? fa.B : 256);
     if constexpr (NT == 3) {
-        if (frappe_shape(fa.inner.g)) return launch(fwd_all_kernel<3, NW, CFFM_ACT_SELU, 10, 32, 32>, grid, block, lds, st, fa);
+        if (frappe_shape(fa.inner.g))
+            return launch(fwd_all_kernel<3, FWD_ALL_NW_FRAPPE, CFFM_ACT_SELU, 10, 32, 32>, grid, dim3(64 * FWD_ALL_NW_FRAPPE), lds, st, fa);
     }
     return with_readme_act<NT>(fa.inner.g.act, [&](auto act) {
         constexpr int ACT = decltype(act)::value;
@@ -4649,7 +4677,7 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
     fa.rank_keys = rank_keys ? 1 : 0;
     fa.id_bits = id_key_bits(s->M);
     const int PP = g.Pp;
-    const FwdAllLds pl = fwd_all_lds_plan(g.F, g.K, g.D, PP);
+    const FwdAllLds pl = fwd_all_lds_plan(g.F, g.K, g.D, PP, fwd_all_wavefronts(g));
     const size_t lds = pl.lds;
     fa.c0_off = pl.c0_off; fa.c1_off = pl.c1_off;
     fa.early_off = (pl.early_fits && ids != nullptr) ? pl.t_off : 0;

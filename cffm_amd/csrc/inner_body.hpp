@@ -53,8 +53,12 @@ struct InnerFwdArgs {
 struct NoMid { __device__ __forceinline__ void operator()() const {} };
 // F_ / K_ / D_ != 0 (compiled-shape fused forward): the field count and the two row lengths as constants - the piece arithmetic of
 // the gather, the unit count and the unit -> (pair, t) split fold
+// NTS != 0: the number of threads that carry the sum behind inner_out - its units are dealt to the first NTS threads of a workgroup
+// that may be larger, and those NTS / 64 wavefront sums are combined.  Which units share a thread and how many partial sums there
+// are is the operand grouping of that sum: an instance that changes its workgroup size keeps NTS, and with it every bit of inner_out.
+// The gather above the sum only moves data and uses every thread.  0: the workgroup size.
 struct InnerDims { int F, K, P, Pp, D; };
-template <int ACTC = -1, class Mid = NoMid, int F_ = 0, int K_ = 0, int D_ = 0>
+template <int ACTC = -1, class Mid = NoMid, int F_ = 0, int K_ = 0, int D_ = 0, int NTS = 0>
 __device__ __forceinline__ void inner_fwd_body(const InnerFwdArgs& ia, int b, char* smem, float* EoL = nullptr, int EoLp = 0,
                                                Mid mid = Mid()) {
     const InnerDims g = F_ ? InnerDims{F_, K_, F_ * (F_ - 1) / 2, (F_ * (F_ - 1) / 2 + 15) / 16 * 16, D_}
@@ -122,14 +126,15 @@ __device__ __forceinline__ void inner_fwd_body(const InnerFwdArgs& ia, int b, ch
     const float2 w2_first = (int)threadIdx.x < units ? wd2[threadIdx.x] : make_float2(0.f, 0.f);
     __syncthreads();
     const float invK2 = 1.f / (float)K2;
+    const int nts = NTS ? NTS : (int)blockDim.x;
     float part = 0.f;
-    for (int u = threadIdx.x; u < units; u += blockDim.x) {
+    for (int u = (NTS == 0 || (int)threadIdx.x < nts) ? (int)threadIdx.x : units; u < units; u += nts) {
         const int p = fast_div(u, invK2), t = u - p * K2;
         const InnerUnit v = inner_unit(E, lut, p, t, g.K, cw, cb, act);
         const float2 w2 = u == (int)threadIdx.x ? w2_first : wd2[u];
         part += v.s0 * w2.x + v.s1 * w2.y;
     }
-    const float tot = block_sum(part, red);
+    const float tot = block_sum<NTS>(part, red);
     if (threadIdx.x == 0) inner_out[b] = tot + bd[0];                            // :339
 }
 

@@ -176,7 +176,7 @@ int cffm_conv_choice(const cffm_shape_t *s, int32_t B, int32_t layer, cffm_conv_
  * selu), as a bit set; 0 for every other shape and wherever (shape, B) does not take that launch at all.  The conv01 bit also needs
  * a loss other than square_l2, as the launch does.  Launches nothing; CFFM_ERR_BAD_SHAPE for a shape the shape check refuses or
  * B < 1.  Additive entry point: CFFM_ABI_VERSION stays 9. */
-#define CFFM_FUSED_INSTANCE_FWD 1     /* fwd_all_kernel<3, 8, selu, 10, 32, 32>                                                    */
+#define CFFM_FUSED_INSTANCE_FWD 1     /* fwd_all_kernel<3, 16, selu, 10, 32, 32>                                                   */
 #define CFFM_FUSED_INSTANCE_BWD_TOP 2 /* reserved for bwd_top_kernel: no compiled-shape instance of it exists, the bit is never set */
 #define CFFM_FUSED_INSTANCE_CONV01 4  /* conv01_bwd_kernel<3, 10, 32, selu>                                                        */
 int cffm_fused_instance(const cffm_shape_t *s, int32_t B);
@@ -251,7 +251,8 @@ int cffm_sparse_adagrad(const cffm_shape_t *s, const cffm_tables_t *tab, const c
                         const float *dfb, void *ws, int32_t B_ws, void *stream);
 
 /* ---- composites: what CFFM.evaluate / CFFM.train call in place of the two sess.run()s ------------- */
-/* sess.run(self.out) CFFM.py:596: ids [B,F] -> out [B] (also left in ws.out) */
+/* sess.run(self.out) CFFM.py:596: ids [B,F] -> out [B] (also left in ws.out).  Where cffm_train_step runs its forward in one
+ * launch (narrow shapes, B * F <= 4096) this runs the same launch: out equals the train step's ws.out on the same ids bit for bit. */
 int cffm_predict(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ids,
                  int32_t B, void *ws, float *out, void *stream);
 /* forward half of a train step, through the per-example loss terms.  tab == NULL: the looked-up rows are already
