@@ -612,10 +612,16 @@ class CFFM(object):
     def _tuple_scorer(eng, sweep, fields, N, per_context):
         """score(ctx, cand) for cand [N, nf] (shared) or [C, N, nf] (per context).  'expand': score_candidate_tuples, bit for bit
         predict on the expanded rows.  'shared': the shared sweep, one field only (ValueError for tuples or a shape that is not
-        served).  'auto': the shared sweep for one field at a served shape with N >= SWEEP_MIN_N, else expand."""
-        if sweep not in ('expand', 'shared', 'auto'):
-            raise ValueError("sweep must be 'expand', 'shared' or 'auto', not %r" % (sweep,))
+        served).  'auto': the shared sweep for one field at a served shape with N >= SWEEP_MIN_N, else expand.  'tuples': the tuple
+        sweep (score_candidate_tuples_shared) for any nf >= 1, ValueError where (shape, nf) is not served; 'auto' never picks it."""
+        if sweep not in ('expand', 'shared', 'auto', 'tuples'):
+            raise ValueError("sweep must be 'expand', 'shared', 'auto' or 'tuples', not %r" % (sweep,))
         nf = len(fields)
+        if sweep == 'tuples':
+            if not eng.sweep_tuples_ok(nf):
+                raise ValueError("sweep='tuples': the tuple sweep does not serve this shape for tuples of %d (both branches, D = 32, "
+                                 "F <= 10, nf <= 4, the candidate kernel within a CU's LDS)" % nf)
+            return lambda ctx, cand: eng.score_candidate_tuples_shared(ctx, fields, cand)
         if sweep == 'shared':
             if nf > 1:
                 raise ValueError("sweep='shared': the shared sweep scores one field, not tuples of %d" % nf)
@@ -636,7 +642,11 @@ class CFFM(object):
         positions.  Returns host arrays (pos int32 [C, k] candidate POSITIONS in the caller's list, -1 padded - a tuple has no
         single id to return; scores float32 [C, k], NaN padded).  sweep: 'expand' (default) is bit for bit predict on the expanded
         rows; 'shared' serves one field at a served shape (ValueError otherwise); 'auto' takes it only there and for
-        N >= SWEEP_MIN_N.  Local to the calling rank: no collective."""
+        N >= SWEEP_MIN_N; 'tuples' is the tuple sweep (HipEngine.score_candidate_tuples_shared: everything without a swept field once
+        per context) for any nf >= 1, equal to 'expand' to rounding, ValueError naming 'tuples' where (shape, nf) is not served
+        (nf <= 4; nf = 3 at F = 10, K = 32 is not).  Measured at the frappe shape, nf = 2: 0.60 of expand's time for one shared list,
+        0.79 for lists of 100 per context (profiles/sweep_tuples.md, one box); 'auto' never picks it.  Local to the calling rank: no
+        collective."""
         import torch
         eng = self._ranking_engine()
         cols = self._tuple_fields(fields)
@@ -699,7 +709,8 @@ class CFFM(object):
         target's POSITION in its list is drawn from the same generator: ties go to the smaller position and CFFM scores tie often,
         so a target fixed at position 0 would win every tie.  m >= the number of distinct tuples raises ValueError.  Under a process
         group every rank draws all lists from the same seed and then takes its contiguous share of the rows.  The sums stay on the
-        device in float64 and are read once, as in evaluate_ranking."""
+        device in float64 and are read once, as in evaluate_ranking.  sweep: as in recommend_tuples ('tuples': the tuple sweep for the
+        shared list and for the sampled lists alike)."""
         import torch
         eng = self._ranking_engine()
         cols = self._tuple_fields(fields)

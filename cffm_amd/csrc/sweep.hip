@@ -32,6 +32,26 @@
 // straight-line code or in a loop whose trip count is workgroup-uniform (a kernel argument or derived from blockIdx); the
 // wave-uniform role branches between two barriers contain none.  Every reduction runs in a fixed order that depends on the
 // thread mapping alone: a candidate's score is the same bits at every position of every chunk, on every call.
+//
+// Tuples (cffm_score_sweep_tuples): a candidate replaces nf <= CFFM_SWEEP_MAX_NF fields f_0 < f_1 < ... together
+// (the host sorts the caller's list and hands the kernels the column permutation).  e_a = the candidate's outer row at f_a.  Every
+// layer-0 pair (i, j), i < j, is of one of three classes:
+//     neither swept     Zctx as above, with ALL swept rows of the embedding tile zero
+//     one swept, f_a    U_a / V_a as above over the fields that are not swept: with the swept rows zero the step-1 contraction yields
+//                       both, its T plane (dh, f_a) being V_a and its mirrored step 1 U_a
+//     both, f_a < f_b   X_ab[y][x][q] = sum_dh sum_dw e_a[2y+dh] * e_b[2x+dw] * W[dh][dw][(f_a,f_b)][q]: per candidate, rank one; its
+//                       4 Pp filter floats depend on theta alone and are staged once per workgroup
+//     Z = b + Zctx + sum_a (sum_dw e_a[2x+dw] U_a[dw][y] + sum_dh e_a[2y+dh] V_a[dh][x]) + sum_{a<b} X_ab
+//     s0[h] = s0fix[h] + sum_a (A_a[h] rowsum(e_a) + e_a[h] R_a) + sum_{a<b} e_a[h] rowsum(e_b),   A_a / R_a over the fields not swept
+// The fixed inner sum keeps the pairs with no swept field; the per-candidate part runs over the list of all pairs with at least one;
+// the first-order term takes the candidates' feature_bias at every swept slot.  The context role is one kernel for every nf (U_a
+// on 2 nf wave roles over its four wavefronts; the block grows by U_a, V_a and A_a per field).  The candidate role has a second
+// instance per Pp (TUP): it stages all U_a / V_a and the swept-swept filter slices in LDS, fetches nf inner rows, outer rows and
+// biases ahead (one 16-byte piece per thread, nf (K/4 + D/4 + 1) threads), forms C_0 with 4 nf multiply-adds plus 4 per
+// swept-swept pair and element - per field in sorted order, then the pairs (a < b) - and from C_0 on runs the code above.  Its sums
+// depend on the thread mapping and the sorted field order alone.  nf = 1 runs the single-field instance, which is compiled to what it
+// was.  The LDS of the tuple instance (sweep_tuples_lds) decides what is served: nf = 2 at every F <= 10 (at F = 10 up to K = 160),
+// nf <= 4 at Pp <= 32; nf = 3 at Pp = 48 does not fit a CU.
 #include "inner_body.hpp"
 #include "internal.hpp"
 
@@ -45,19 +65,19 @@ namespace {
 
 // per-context block of the scratch, offsets in floats (every one a multiple of 4)
 struct SweepBlock {
-    int Z, U, V, Ei, s0fix, A, fb, scal;    // scal: [0] fixed inner sum, [1] R = sum_{j>f} rowsum(E_j)
+    int Z, U, V, Ei, s0fix, A, fb, scal;    // scal: [0] fixed inner sum, [1 + a] R_a = sum_{j>f_a, j not swept} rowsum(E_j)
     int64_t floats;
 };
-__host__ __device__ inline SweepBlock sweep_block(int Pp, int F, int K) {
+__host__ __device__ inline SweepBlock sweep_block(int Pp, int F, int K, int nf = 1) {
     SweepBlock b;
     int o = 0;
     b.Z = o; o += SWEEP_S * SWEEP_S * Pp;   // [y][x][q]
-    b.U = o; o += 2 * SWEEP_S * Pp;         // [dw][y][q]
-    b.V = o; o += 2 * SWEEP_S * Pp;         // [dh][x][q]
-    b.Ei = o; o += F * K;                   // inner rows, row f zero
+    b.U = o; o += nf * 2 * SWEEP_S * Pp;    // [a][dw][y][q]
+    b.V = o; o += nf * 2 * SWEEP_S * Pp;    // [a][dh][x][q]
+    b.Ei = o; o += F * K;                   // inner rows, the swept rows zero
     b.s0fix = o; o += SWEEP_D;
-    b.A = o; o += SWEEP_D;
-    b.fb = o; o += 16;                      // feature_bias of the context's fields, slot f zero
+    b.A = o; o += nf * SWEEP_D;             // [a][h]
+    b.fb = o; o += 16;                      // feature_bias of the context's fields, the swept slots zero
     b.scal = o; o += 16;
     b.floats = (o + 63) / 64 * 64;
     return b;
@@ -65,6 +85,8 @@ __host__ __device__ inline SweepBlock sweep_block(int Pp, int F, int K) {
 
 __device__ __forceinline__ int sweep_clamp(int id, int M) { return id < 0 ? 0 : (id >= M ? M - 1 : id); }
 __device__ __forceinline__ int sweep_pair(int i, int j, int F) { return i * (2 * F - i - 1) / 2 + j - i - 1; }   // i < j
+// The swept fields travel by value, sorted, four bits each (F <= 10): a lane reads its own without indexing a kernel argument.
+__device__ __forceinline__ int sweep_field(uint32_t packed, int a) { return (int)((packed >> (4 * a)) & 15u); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // context role
@@ -73,7 +95,8 @@ struct SweepCtxArgs {
     Geo g;
     const float *inner, *outer, *fbias;
     const int32_t* ctx;
-    int field;
+    int nf;                                // swept fields f_0 < f_1 < ... (one for cffm_score_sweep / _lists)
+    uint32_t fields, swept;                // sweep_field(fields, a) = f_a; bit f of swept: field f is swept
     const float *W0, *cw, *cb, *wd;
     float* blocks;
     int64_t block_floats;
@@ -89,26 +112,27 @@ __global__ __launch_bounds__(256) void sweep_ctx_kernel(SweepCtxArgs a) {
     constexpr int PP = NT * 16, NW = 4, NTH = 64 * NW, D = SWEEP_D, S = SWEEP_S, Dp = D + 1, TP = S * PP + 16, XQ = 16 / NW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Geo& g = a.g;
-    const int F = g.F, K = g.K, f = a.field;
+    const int F = g.F, K = g.K, nf = a.nf;
+    const uint32_t sw = a.swept;
     const int EsN = (F * Dp + 3) / 4 * 4;
     float* Wl = reinterpret_cast<float*>(smem);                  // [4*PP][PP]
     float* T = Wl + 4 * PP * PP;                                 // [2F][TP]
-    float* Es = T + 2 * F * TP;                                  // [F][Dp], row f zero
-    float* Ein = Es + EsN;                                       // [F][K], row f zero
+    float* Es = T + 2 * F * TP;                                  // [F][Dp], the swept rows zero
+    float* Ein = Es + EsN;                                       // [F][K], the swept rows zero
     uint32_t* lut = reinterpret_cast<uint32_t*>(Ein + F * K);    // [PP]
     float* rs = reinterpret_cast<float*>(lut + PP);              // [16]
     float* red = rs + 16;                                        // [16]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, kk = lane >> 4;
     const int32_t* idb = a.ctx + (int64_t)blockIdx.x * F;
     float* blk = a.blocks + (int64_t)blockIdx.x * a.block_floats;
-    const SweepBlock bo = sweep_block(PP, F, K);
+    const SweepBlock bo = sweep_block(PP, F, K, nf);
 
-    // ---- stage the filter, gather the context's rows (row f of both tiles is zero: the candidate takes its place) ----
+    // ---- stage the filter, gather the context's rows (the swept rows of both tiles are zero: the candidate takes their place) ----
     for (int i = tid; i < PP * PP; i += NTH) reinterpret_cast<float4*>(Wl)[i] = reinterpret_cast<const float4*>(a.W0)[i];
     for (int i = tid; i < F * (D / 4); i += NTH) {
         const int fr = i / (D / 4), c4 = i - fr * (D / 4);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (fr != f) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)sweep_clamp(idb[fr], g.M) * (D / 4) + c4];
+        if (!((sw >> fr) & 1u)) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)sweep_clamp(idb[fr], g.M) * (D / 4) + c4];
         float* e = Es + fr * Dp + 4 * c4;
         e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
     }
@@ -116,11 +140,11 @@ __global__ __launch_bounds__(256) void sweep_ctx_kernel(SweepCtxArgs a) {
     for (int i = tid; i < F * K4; i += NTH) {
         const int fr = i / K4, c4 = i - fr * K4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (fr != f) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)sweep_clamp(idb[fr], g.M) * K4 + c4];
+        if (!((sw >> fr) & 1u)) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)sweep_clamp(idb[fr], g.M) * K4 + c4];
         reinterpret_cast<float4*>(Ein)[i] = v;
         reinterpret_cast<float4*>(blk + bo.Ei)[i] = v;
     }
-    if (tid < 16) blk[bo.fb + tid] = (tid < F && tid != f) ? a.fbias[sweep_clamp(idb[tid], g.M)] : 0.f;
+    if (tid < 16) blk[bo.fb + tid] = (tid < F && !((sw >> tid) & 1u)) ? a.fbias[sweep_clamp(idb[tid], g.M)] : 0.f;
     build_pair_lut(lut, F, PP);
     const float cw[4] = {a.cw[0], a.cw[1], a.cw[2], a.cw[3]};
     const float cb[2] = {a.cb[0], a.cb[1]};
@@ -154,17 +178,17 @@ __global__ __launch_bounds__(256) void sweep_ctx_kernel(SweepCtxArgs a) {
         const int dh = e / (S * PP), o = e - dh * (S * PP);
         T[(dh * F + F - 1) * TP + o] = 0.f;
     }
-    // row sums of the outer rows (row f: 0)
+    // row sums of the outer rows (a swept row: 0)
     for (int i = wave; i < F; i += NW) {
         const float s = wave_sum(lane < D ? Es[i * Dp + lane] : 0.f);
         if (lane == 0) rs[i] = s;
     }
     lds_barrier();
 
-    // ---- V = the T planes (dh, f) ----
-    for (int e = tid; e < 2 * S * PP; e += NTH) {
-        const int dh = e / (S * PP), o = e - dh * (S * PP);
-        blk[bo.V + e] = T[(dh * F + f) * TP + o];
+    // ---- V_a = the T planes (dh, f_a): with the swept rows zero they hold the pairs (f_a, j), j not swept, alone ----
+    for (int e = tid; e < nf * 2 * S * PP; e += NTH) {
+        const int ad = e / (S * PP), o = e - ad * (S * PP), dh = ad & 1;
+        blk[bo.V + e] = T[(dh * F + sweep_field(a.fields, ad >> 1)) * TP + o];
     }
     // ---- step 2 without bias and relu: Zctx (wave w owns x = 4w .. 4w+3) ----
     {
@@ -192,9 +216,10 @@ __global__ __launch_bounds__(256) void sweep_ctx_kernel(SweepCtxArgs a) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) blk[bo.Z + ((kk * 4 + j) * S + xg + q4) * PP + nt * 16 + r] = acc[q4][nt][j];
     }
-    // ---- U[dw]: the mirrored step 1, rows y, k = (dh, i < f), the candidate being the column operand (waves 0 and 1) ----
-    if (wave < 2) {
-        const int dw = wave, Kf = 2 * f;
+    // ---- U_a[dw]: the mirrored step 1, rows y, k = (dh, i < f_a), the candidate being the column operand: 2 nf wave roles over the
+    // four wavefronts (a swept i < f_a contributes exact zeros) ----
+    for (int role = wave; role < 2 * nf; role += NW) {
+        const int dw = role & 1, f = sweep_field(a.fields, role >> 1), Kf = 2 * f;
         f32x4 acc[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -210,32 +235,36 @@ __global__ __launch_bounds__(256) void sweep_ctx_kernel(SweepCtxArgs a) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) blk[bo.U + (dw * S + kk * 4 + j) * PP + nt * 16 + r] = acc[nt][j];
+            for (int j = 0; j < 4; ++j) blk[bo.U + (role * S + kk * 4 + j) * PP + nt * 16 + r] = acc[nt][j];
     }
-    // ---- the s0 pool: s0fix[h] = sum_{i<j, both != f} E_i[h] * rowsum(E_j) (row f of Es is zero), A[h], R ----
+    // ---- the s0 pool: s0fix[h] = sum_{i<j, neither swept} E_i[h] * rowsum(E_j) (the swept rows of Es are zero), A_a[h], R_a ----
     if (tid < D) {
-        float s = 0.f, R = 0.f, A = 0.f;
+        float s = 0.f, R = 0.f;
         for (int i = F - 2; i >= 0; --i) {
             R += rs[i + 1];
             s += Es[i * Dp + tid] * R;
         }
-        for (int i = 0; i < f; ++i) A += Es[i * Dp + tid];
         blk[bo.s0fix + tid] = s;
-        blk[bo.A + tid] = A;
+        for (int sa = 0; sa < nf; ++sa) {
+            const int f = sweep_field(a.fields, sa);
+            float A = 0.f;
+            for (int i = 0; i < f; ++i) A += Es[i * Dp + tid];
+            blk[bo.A + sa * D + tid] = A;
+        }
     }
-    if (tid == 0) {
+    if (tid < nf) {
         float R = 0.f;
-        for (int j = f + 1; j < F; ++j) R += rs[j];
-        blk[bo.scal + 1] = R;
+        for (int j = sweep_field(a.fields, tid) + 1; j < F; ++j) R += rs[j];
+        blk[bo.scal + 1 + tid] = R;
     }
-    // ---- the inner-branch terms of the pairs without f ----
+    // ---- the inner-branch terms of the pairs without a swept field ----
     const int K2i = K / 2, nun = g.P * K2i;
     const float2* wd2 = reinterpret_cast<const float2*>(a.wd);
     float part = 0.f;
     for (int u = tid; u < nun; u += NTH) {
         const int p = u / K2i, t = u - p * K2i;
         const uint32_t ij = lut[p];
-        if ((int)(ij & 0xffff) == f || (int)(ij >> 16) == f) continue;
+        if (((sw >> (ij & 0xffff)) | (sw >> (ij >> 16))) & 1u) continue;
         const InnerUnit v = inner_unit(Ein, lut, p, t, K, cw, cb, g.act);
         const float2 w2 = wd2[u];
         part += v.s0 * w2.x + v.s1 * w2.y;
@@ -262,10 +291,15 @@ struct SweepArgs {
     const float *d1_w, *d1_b, *d2_w, *d2_b, *att_W, *att_b, *lin_w, *lin_b, *bias;
     float* scores;
     int64_t row_stride;
+    // the tuple instance: the swept fields, sorted as in SweepCtxArgs (field = f_0); sweep_field(perm, a) = the caller's tuple column
+    // that holds the id of field f_a; W0: the layer-0 filter (its swept-swept pairs)
+    int nf;
+    uint32_t fields, swept, perm;
+    const float* W0;
 };
 
 // LDS of the candidate role, in floats: C_0 | W_1 (padded image of conv_fwd_taps_body) | red | C_1 | C_2 | C_3 | U | V | small | rows
-struct SweepLds { int C0, W1, red, C1, C2, C3, U, V, t1s, hpart, s0fix, A, fbrow, sc, wpart, lutf, aW, eo, Eall, wdp, floats; };
+struct SweepLds { int C0, W1, red, C1, C2, C3, U, V, t1s, hpart, s0fix, A, fbrow, sc, wpart, lutf, aW, eo, Eall, wdp, Wx, floats; };
 __host__ __device__ inline SweepLds sweep_lds(int Pp, int F, int K) {
     SweepLds l;
     int o = 0;
@@ -289,6 +323,41 @@ __host__ __device__ inline SweepLds sweep_lds(int Pp, int F, int K) {
     l.eo = o; o += SWEEP_D;                  // the candidate's outer row
     l.Eall = o; o += F * K;                  // the context's inner rows with the candidate's row at f
     l.wdp = o; o += (F - 1) * K;             // dense(1) weights of the pairs that contain f, by partner slot
+    l.Wx = o;                                // (tuples only)
+    l.floats = o;
+    return l;
+}
+// pairs with at least one of nf swept fields / with both
+__host__ __device__ inline int sweep_live_pairs(int F, int nf) { return F * (F - 1) / 2 - (F - nf) * (F - nf - 1) / 2; }
+__host__ __device__ inline int sweep_cross_pairs(int nf) { return nf * (nf - 1) / 2; }
+// The tuple instance of the candidate role: the same regions, U / V / A / eo once per swept field, the pair list of the inner branch
+// by live pair, and the layer-0 filter slices of the swept-swept pairs.  This one formula sizes the launch and answers
+// cffm_sweep_tuples_ok.  Bytes at (Pp, K, nf), F the largest of that Pp: (48, 32, 2) 149,184; (48, 64, 2) 152,640; (48, 32, 3)
+// 164,160 (832 over CFFM_LDS_WHOLE_CU: not served, nor is F = 9 at 163,648); (32, 32, 4) 113,216; (16, 32, 4) 54,848.
+__host__ __device__ inline SweepLds sweep_tuples_lds(int Pp, int F, int K, int nf) {
+    SweepLds l;
+    int o = 0;
+    l.C0 = o; o += 256 * Pp;
+    l.W1 = o; o += 4 * Pp * (Pp + 4);
+    l.red = o; o += 64 * Pp;
+    l.C1 = o; o += 64 * Pp;
+    l.C2 = o; o += 16 * Pp;
+    l.C3 = o; o += 4 * Pp;
+    l.U = o; o += nf * 2 * SWEEP_S * Pp;     // [a][dw][y][q]
+    l.V = o; o += nf * 2 * SWEEP_S * Pp;     // [a][dh][x][q]
+    l.t1s = o; o += 64;
+    l.hpart = o; o += 8 * CFFM_HEAD_UNITS;
+    l.s0fix = o; o += SWEEP_D;
+    l.A = o; o += nf * SWEEP_D;
+    l.fbrow = o; o += 16;                    // feature_bias by field: the context's, the candidate's at the swept slots
+    l.sc = o; o += 16;                       // [1] first-order term, [3] fixed inner sum, [4 + a] R_a
+    l.wpart = o; o += 16;
+    l.lutf = o; o += 2 * 32;                 // the live pairs (i | j << 16), then their pair indices: at most 30 (F = 10, nf = 4)
+    l.aW = o; o += 128;
+    l.eo = o; o += nf * SWEEP_D;             // the candidate's outer rows, by sorted field
+    l.Eall = o; o += F * K;
+    l.wdp = o; o += sweep_live_pairs(F, nf) * K;
+    l.Wx = o; o += sweep_cross_pairs(nf) * 4 * Pp;   // [pair (a < b)][dh][dw][q]
     l.floats = o;
     return l;
 }
@@ -391,7 +460,10 @@ __device__ __forceinline__ void sweep_conv_reduce(const float* red2, const float
     }
 }
 
-template <int NT>
+// TUP: the tuple instance (cffm_score_sweep_tuples, nf >= 2 swept fields).  It differs from the single-field one in what a candidate
+// brings (nf inner rows, outer rows and biases) and in how layer 0, the live inner pairs, s0 and the first-order term are put
+// together from the block; from C_0 on the two run the same code.  The single-field instance compiles to what it was.
+template <int NT, bool TUP>
 __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     constexpr int PP = NT * 16, PQ = PP / 4, NTH = SWEEP_NTH, NWV = NTH / 64, D = SWEEP_D, S = SWEEP_S;
     constexpr int ZR = S * S * PQ / NTH;                         // float4 of Zctx per thread: 2 * NT
@@ -399,8 +471,9 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Geo& g = a.g;
     const int F = g.F, K = g.K, f = a.field, act = g.act, K4 = K / 4, K2 = K / 2;
-    const SweepLds L = sweep_lds(PP, F, K);
-    const SweepBlock bo = sweep_block(PP, F, K);
+    const int nf = TUP ? a.nf : 1;
+    const SweepLds L = TUP ? sweep_tuples_lds(PP, F, K, nf) : sweep_lds(PP, F, K);
+    const SweepBlock bo = sweep_block(PP, F, K, nf);
     float* sm = reinterpret_cast<float*>(smem);
     float *C0 = sm + L.C0, *W1s = sm + L.W1, *red = sm + L.red, *C1 = sm + L.C1, *C2 = sm + L.C2, *C3 = sm + L.C3;
     float *Us = sm + L.U, *Vs = sm + L.V, *t1s = sm + L.t1s, *s0fix = sm + L.s0fix, *As = sm + L.A, *fbrow = sm + L.fbrow;
@@ -416,11 +489,44 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
         *reinterpret_cast<float4*>(W1s + tap * PP * (PP + 4) + krow * PP + (krow >> 2) * 16 + 4 * c4) =
             reinterpret_cast<const float4*>(a.W1)[i];
     }
-    for (int i = tid; i < (F - 1) * K; i += NTH) {               // partner slot sl: field sl below f, sl + 1 from f on
-        const int sl = i / K, c = i - sl * K, pi = sl < f ? sl : sl + 1;
-        wdp[i] = a.wd[(int64_t)(pi < f ? sweep_pair(pi, f, F) : sweep_pair(f, pi, F)) * K + c];
+    if constexpr (TUP) {
+        // the live pairs (at least one swept field) in pair order: pair p on lane p of wave 0 (P <= 45), compacted by ballot
+        uint32_t* pidx = lutf + 32;
+        if (wave == 0) {
+            int i = 0, base = 0;
+            while (i < F - 2 && lane >= base + F - 1 - i) { base += F - 1 - i; ++i; }
+            const int j = lane < g.P ? i + 1 + lane - base : i;
+            const bool live = lane < g.P && (((a.swept >> i) | (a.swept >> j)) & 1u);
+            const unsigned long long m = __ballot(live);
+            if (live) {
+                const int q = __popcll(m & ((1ull << lane) - 1ull));
+                lutf[q] = (uint32_t)i | ((uint32_t)j << 16);
+                pidx[q] = (uint32_t)lane;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < sweep_live_pairs(F, nf) * K; i += NTH) {
+            const int q = i / K, c = i - q * K;
+            wdp[i] = a.wd[(int64_t)pidx[q] * K + c];
+        }
+        // the layer-0 filter of the swept-swept pairs (f_a, f_b), a < b in that order: [dh][dw][q] each
+        float* Wx = sm + L.Wx;
+        int pr = 0;
+        for (int sa = 0; sa < nf; ++sa)
+            for (int sb = sa + 1; sb < nf; ++sb, ++pr) {
+                const int prow = sweep_pair(sweep_field(a.fields, sa), sweep_field(a.fields, sb), F);
+                for (int i = tid; i < 4 * PP; i += NTH) {
+                    const int tap = i / PP, q = i - tap * PP;
+                    Wx[pr * 4 * PP + i] = a.W0[(tap * PP + prow) * PP + q];
+                }
+            }
+    } else {
+        for (int i = tid; i < (F - 1) * K; i += NTH) {           // partner slot sl: field sl below f, sl + 1 from f on
+            const int sl = i / K, c = i - sl * K, pi = sl < f ? sl : sl + 1;
+            wdp[i] = a.wd[(int64_t)(pi < f ? sweep_pair(pi, f, F) : sweep_pair(f, pi, F)) * K + c];
+        }
+        if (tid < 16) lutf[tid] = tid < F - 1 ? ((uint32_t)(tid < f ? tid : tid + 1) | ((uint32_t)f << 16)) : 0u;
     }
-    if (tid < 16) lutf[tid] = tid < F - 1 ? ((uint32_t)(tid < f ? tid : tid + 1) | ((uint32_t)f << 16)) : 0u;
     if (g.linear_att)
         for (int i = tid; i < F * F; i += NTH) aW[i] = a.att_W[i];
     const float cw[4] = {a.cw[0], a.cw[1], a.cw[2], a.cw[3]};
@@ -438,15 +544,26 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     if (lane < CFFM_HEAD_UNITS) { d1b = a.d1_b[lane]; d2w = a.d2_w[lane]; }
     if (lane < F && g.linear_att) { linw = a.lin_w[lane]; attb = a.att_b[lane]; }
     const float d2b = a.d2_b[0], linb = g.linear_att ? a.lin_b[0] : 0.f, biasv = a.bias[0], bdv = a.bd[0];
-    const int nun = (F - 1) * K2;
+    const int nun = (TUP ? sweep_live_pairs(F, nf) : F - 1) * K2;
     float w2r[NT][2][NT], w3r[NT][2][NT];                        // this lane's filter fragments of layers 2 and 3, for the whole launch
     sweep_load_w<NT>(w2r, a.W2);
     sweep_load_w<NT>(w3r, a.W3);
 
     // this thread's piece of a candidate's rows: K/4 inner pieces, D/4 outer pieces, one feature_bias value
     const int32_t* cand = a.cand;                                // the current unit's list
+    // (tuples: the same pieces once per swept field, field f_a's on threads [a * per, (a + 1) * per))
+    const int per = K4 + D / 4 + 1, fa_slot = TUP ? tid / per : 0, fa_piece = tid - fa_slot * per;
     auto fetch = [&](int n) -> float4 {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (TUP) {
+            if (tid < nf * per) {
+                const int id = sweep_clamp(cand[(int64_t)n * nf + sweep_field(a.perm, fa_slot)], g.M);
+                if (fa_piece < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + fa_piece];
+                else if (fa_piece < K4 + D / 4) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)id * (D / 4) + fa_piece - K4];
+                else v.x = a.fbias[id];
+            }
+            return v;
+        }
         if (tid <= K4 + D / 4) {
             const int id = sweep_clamp(cand[n], g.M);
             if (tid < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + tid];
@@ -456,6 +573,15 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
         return v;
     };
     auto put = [&](const float4& v) {
+        if constexpr (TUP) {
+            if (tid < nf * per) {
+                const int fa = sweep_field(a.fields, fa_slot);
+                if (fa_piece < K4) reinterpret_cast<float4*>(Eall + fa * K)[fa_piece] = v;
+                else if (fa_piece < K4 + D / 4) reinterpret_cast<float4*>(eo + fa_slot * D)[fa_piece - K4] = v;
+                else fbrow[fa] = v.x;
+            }
+            return;
+        }
         if (tid < K4) reinterpret_cast<float4*>(Eall + f * K)[tid] = v;
         else if (tid < K4 + D / 4) reinterpret_cast<float4*>(eo)[tid - K4] = v;
         else if (tid == K4 + D / 4) sc[2] = v.x;
@@ -478,15 +604,24 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
             const float4 b = reinterpret_cast<const float4*>(a.b0)[i4 % PQ];
             Zr[k] = make_float4(z.x + b.x, z.y + b.y, z.z + b.z, z.w + b.w);
         }
-        for (int i = tid; i < 2 * S * PQ; i += NTH) {
+        for (int i = tid; i < nf * 2 * S * PQ; i += NTH) {
             reinterpret_cast<float4*>(Us)[i] = reinterpret_cast<const float4*>(blk + bo.U)[i];
             reinterpret_cast<float4*>(Vs)[i] = reinterpret_cast<const float4*>(blk + bo.V)[i];
         }
-        for (int i = tid; i < F * K4; i += NTH)
-            if (i / K4 != f) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
-        if (tid < D) { s0fix[tid] = blk[bo.s0fix + tid]; As[tid] = blk[bo.A + tid]; }
-        if (tid < 16) fbrow[tid] = blk[bo.fb + tid];
-        if (tid < 2) sc[3 + tid] = blk[bo.scal + tid];
+        if constexpr (TUP) {                                     // the swept rows and slots are the candidate's: put() writes them
+            for (int i = tid; i < F * K4; i += NTH)
+                if (!((a.swept >> (i / K4)) & 1u)) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
+            if (tid < D) s0fix[tid] = blk[bo.s0fix + tid];
+            if (tid < nf * D) As[tid] = blk[bo.A + tid];
+            if (tid < 16 && !((a.swept >> tid) & 1u)) fbrow[tid] = blk[bo.fb + tid];
+            if (tid < 1 + nf) sc[3 + tid] = blk[bo.scal + tid];
+        } else {
+            for (int i = tid; i < F * K4; i += NTH)
+                if (i / K4 != f) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
+            if (tid < D) { s0fix[tid] = blk[bo.s0fix + tid]; As[tid] = blk[bo.A + tid]; }
+            if (tid < 16) fbrow[tid] = blk[bo.fb + tid];
+            if (tid < 2) sc[3 + tid] = blk[bo.scal + tid];
+        }
         float4 pre = fetch(n0);
         put(pre);
         __syncthreads();
@@ -498,6 +633,37 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
 #pragma unroll
             for (int k = 0; k < ZR; ++k) {
                 const int i4 = tid + NTH * k, q4 = i4 % PQ, pix = i4 / PQ, y = pix >> 4, x = pix & 15;
+                if constexpr (TUP) {
+                    // per swept field, in sorted order, the four terms of the single-field sweep; then the swept-swept pairs
+                    // (a < b), each X_ab = sum_dh sum_dw (e_a[2y+dh] * e_b[2x+dw]) * W[dh][dw][(f_a, f_b)]
+                    float4 z = Zr[k];
+                    for (int sa = 0; sa < nf; ++sa) {
+                        const float* ea = eo + sa * D;
+                        const float ex0 = ea[2 * x], ex1 = ea[2 * x + 1], ey0 = ea[2 * y], ey1 = ea[2 * y + 1];
+                        const float4 u0 = reinterpret_cast<const float4*>(Us)[((2 * sa) * S + y) * PQ + q4];
+                        const float4 u1 = reinterpret_cast<const float4*>(Us)[((2 * sa + 1) * S + y) * PQ + q4];
+                        const float4 v0 = reinterpret_cast<const float4*>(Vs)[((2 * sa) * S + x) * PQ + q4];
+                        const float4 v1 = reinterpret_cast<const float4*>(Vs)[((2 * sa + 1) * S + x) * PQ + q4];
+                        z.x = fmaf(ey1, v1.x, fmaf(ey0, v0.x, fmaf(ex1, u1.x, fmaf(ex0, u0.x, z.x))));
+                        z.y = fmaf(ey1, v1.y, fmaf(ey0, v0.y, fmaf(ex1, u1.y, fmaf(ex0, u0.y, z.y))));
+                        z.z = fmaf(ey1, v1.z, fmaf(ey0, v0.z, fmaf(ex1, u1.z, fmaf(ex0, u0.z, z.z))));
+                        z.w = fmaf(ey1, v1.w, fmaf(ey0, v0.w, fmaf(ex1, u1.w, fmaf(ex0, u0.w, z.w))));
+                    }
+                    const float4* wx = reinterpret_cast<const float4*>(sm + L.Wx) + q4;
+                    for (int sa = 0; sa < nf; ++sa)
+                        for (int sb = sa + 1; sb < nf; ++sb, wx += 4 * PQ) {
+                            const float *ea = eo + sa * D, *eb = eo + sb * D;
+                            const float p00 = ea[2 * y] * eb[2 * x], p01 = ea[2 * y] * eb[2 * x + 1];
+                            const float p10 = ea[2 * y + 1] * eb[2 * x], p11 = ea[2 * y + 1] * eb[2 * x + 1];
+                            const float4 w00 = wx[0], w01 = wx[PQ], w10 = wx[2 * PQ], w11 = wx[3 * PQ];
+                            z.x = fmaf(p11, w11.x, fmaf(p10, w10.x, fmaf(p01, w01.x, fmaf(p00, w00.x, z.x))));
+                            z.y = fmaf(p11, w11.y, fmaf(p10, w10.y, fmaf(p01, w01.y, fmaf(p00, w00.y, z.y))));
+                            z.z = fmaf(p11, w11.z, fmaf(p10, w10.z, fmaf(p01, w01.z, fmaf(p00, w00.z, z.z))));
+                            z.w = fmaf(p11, w11.w, fmaf(p10, w10.w, fmaf(p01, w01.w, fmaf(p00, w00.w, z.w))));
+                        }
+                    reinterpret_cast<float4*>(C0)[i4] = make_float4(fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f));
+                    continue;
+                }
                 const float ex0 = eo[2 * x], ex1 = eo[2 * x + 1], ey0 = eo[2 * y], ey1 = eo[2 * y + 1];
                 const float4 u0 = reinterpret_cast<const float4*>(Us)[y * PQ + q4];
                 const float4 u1 = reinterpret_cast<const float4*>(Us)[(S + y) * PQ + q4];
@@ -521,13 +687,24 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
                 part = wave_sum(part);
                 if (lane == 0) wpart[wave] = part;
             }
-            if (wave == 0) {                                     // s0[h] = s0fix[h] + A[h] * rowsum(e) + e[h] * R
+            if (TUP && wave == 0) {      // s0[h] = s0fix[h] + sum_a (A_a[h] * rowsum(e_a) + e_a[h] * R_a) + sum_{a<b} e_a[h] * rowsum(e_b)
+                float s = lane < D ? s0fix[lane] : 0.f, below = 0.f;                 // below: sum of e_a'[h] over a' < a
+                for (int sa = 0; sa < nf; ++sa) {
+                    const float ev = lane < D ? eo[sa * D + lane] : 0.f;
+                    const float rse = wave_sum(ev);
+                    s += (lane < D ? As[sa * D + lane] : 0.f) * rse + ev * sc[4 + sa];
+                    s += below * rse;
+                    below += ev;
+                }
+                if (lane < D) t1s[lane] = s;
+            }
+            if (!TUP && wave == 0) {                             // s0[h] = s0fix[h] + A[h] * rowsum(e) + e[h] * R
                 const float ev = lane < D ? eo[lane] : 0.f;
                 const float rse = wave_sum(ev);
                 if (lane < D) t1s[lane] = s0fix[lane] + As[lane] * rse + ev * sc[4];
             }
             if (wave == NWV - 1) {                               // first-order term (head_fwd_body), CFFM.py:422-446
-                const float fbv = lane < F ? (lane == f ? sc[2] : fbrow[lane]) : 0.f;
+                const float fbv = lane < F ? ((!TUP && lane == f) ? sc[2] : fbrow[lane]) : 0.f;
                 float lin;
                 if (g.linear_att) {
                     float z = attb;
@@ -631,17 +808,22 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     }
 }
 
-template <int NT>
+// LDS of the candidate role for nf swept fields, in bytes: what the launcher asks for and what the served-domain queries compare
+static inline size_t sweep_cand_lds(int Pp, int F, int K, int nf) {
+    return (size_t)(nf > 1 ? sweep_tuples_lds(Pp, F, K, nf) : sweep_lds(Pp, F, K)).floats * 4;
+}
+
+template <int NT, bool TUP>
 int sweep_launch(const SweepCtxArgs& ca, const SweepArgs& sa, int C, int grid, hipStream_t st) {
     const Geo& g = sa.g;
-    const size_t lds_c = sweep_ctx_lds(g.Pp, g.F, g.K), lds_k = (size_t)sweep_lds(g.Pp, g.F, g.K).floats * 4;
+    const size_t lds_c = sweep_ctx_lds(g.Pp, g.F, g.K), lds_k = sweep_cand_lds(g.Pp, g.F, g.K, sa.nf);
     int rc = set_lds(sweep_ctx_kernel<NT>, lds_c);
     if (rc) return rc;
-    rc = set_lds(sweep_cand_kernel<NT>, lds_k);
+    rc = set_lds(sweep_cand_kernel<NT, TUP>, lds_k);
     if (rc) return rc;
     hipLaunchKernelGGL(sweep_ctx_kernel<NT>, dim3((unsigned)C), dim3(256), lds_c, st, ca);
     CFFM_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sweep_cand_kernel<NT>, dim3((unsigned)grid), dim3(SWEEP_NTH), lds_k, st, sa);
+    hipLaunchKernelGGL((sweep_cand_kernel<NT, TUP>), dim3((unsigned)grid), dim3(SWEEP_NTH), lds_k, st, sa);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -679,38 +861,67 @@ extern "C" int cffm_sweep_block_layout(const cffm_shape_t* s, cffm_sweep_block_t
     return 0;
 }
 
-// both entry points: cand_ctx_stride == 0 is the shared list of cffm_score_sweep
-static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C, int32_t field,
-                     const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores, int64_t row_stride, void* scratch,
-                     void* stream) {
+extern "C" int cffm_sweep_tuples_ok(const cffm_shape_t* s, int32_t nf) {
+    if (!cffm_sweep_ok(s) || nf < 1 || nf > CFFM_SWEEP_MAX_NF || nf > s->F) return 0;
+    const Geo g = make_geo(s);
+    if (nf * (s->K / 4 + SWEEP_D / 4 + 1) > SWEEP_NTH) return 0;                   // a candidate's rows: one piece per thread
+    return sweep_cand_lds(g.Pp, g.F, g.K, nf) <= (size_t)CFFM_LDS_WHOLE_CU;
+}
+
+extern "C" int64_t cffm_sweep_tuples_scratch_bytes(const cffm_shape_t* s, int32_t nf, int32_t C) {
+    if (C < 0 || !cffm_sweep_tuples_ok(s, nf)) return -1;
+    const Geo g = make_geo(s);
+    return SWEEP_HEADER + (int64_t)C * sweep_block(g.Pp, g.F, g.K, nf).floats * 4;
+}
+
+extern "C" int cffm_sweep_tuples_block_layout(const cffm_shape_t* s, int32_t nf, cffm_sweep_tuples_block_t* out) {
     int rc = check_shape(s);
     if (rc) return rc;
-    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
-    if (field < 0 || field >= s->F || N < 1 || C < 0 || row_stride < N) return CFFM_ERR_BAD_SHAPE;
-    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < N)) return CFFM_ERR_BAD_SHAPE;
-    if (C == 0) return 0;
-    if (!tab || !tab->inner_emb || !tab->outer_emb || !tab->feat_bias || !theta || !ctx || !cand || !scores || !scratch)
-        return CFFM_ERR_BAD_SHAPE;
+    if (!out) return CFFM_ERR_BAD_SHAPE;
+    if (!cffm_sweep_tuples_ok(s, nf)) return CFFM_ERR_UNSUPPORTED;
+    const Geo g = make_geo(s);
+    const SweepBlock b = sweep_block(g.Pp, g.F, g.K, nf);
+    out->header_floats = SWEEP_HEADER / 4;
+    out->block_floats = b.floats;
+    out->Z = b.Z; out->U = b.U; out->V = b.V; out->Ei = b.Ei;
+    out->s0fix = b.s0fix; out->A = b.A; out->fb = b.fb; out->scal = b.scal;
+    out->UV_stride = 2 * SWEEP_S * g.Pp;
+    out->A_stride = SWEEP_D;
+    return 0;
+}
+
+// The two launches for nf swept fields, sorted: fields[a] = f_a, col[a] = the caller's tuple column of f_a.  Every argument has been
+// checked by the caller.
+static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C, int nf,
+                     const int* fields, const int* col, const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores,
+                     int64_t row_stride, void* scratch, void* stream) {
     const Geo g = make_geo(s);
     cffm_theta_layout_t tl;
-    rc = cffm_theta_layout(s, &tl);
+    int rc = cffm_theta_layout(s, &tl);
     if (rc) return rc;
-    const SweepBlock bo = sweep_block(g.Pp, g.F, g.K);
+    const SweepBlock bo = sweep_block(g.Pp, g.F, g.K, nf);
     float* blocks = reinterpret_cast<float*>((char*)scratch + SWEEP_HEADER);
+    uint32_t packed = 0, swept = 0, perm = 0;
+    for (int a = 0; a < nf; ++a) {
+        packed |= (uint32_t)fields[a] << (4 * a);
+        perm |= (uint32_t)col[a] << (4 * a);
+        swept |= 1u << fields[a];
+    }
     SweepCtxArgs ca;
     ca.g = g;
     ca.inner = tab->inner_emb; ca.outer = tab->outer_emb; ca.fbias = tab->feat_bias;
-    ca.ctx = ctx; ca.field = field;
+    ca.ctx = ctx; ca.nf = nf; ca.fields = packed; ca.swept = swept;
     ca.W0 = theta + tl.conv_w[0]; ca.cw = theta + tl.inner_cw; ca.cb = theta + tl.inner_cb; ca.wd = theta + tl.inner_dw;
     ca.blocks = blocks; ca.block_floats = bo.floats;
     SweepArgs sa;
     sa.g = g; sa.loss = s->loss;
     sa.inner = tab->inner_emb; sa.outer = tab->outer_emb; sa.fbias = tab->feat_bias;
-    sa.cand = cand; sa.cand_ctx_stride = cand_ctx_stride; sa.N = N; sa.field = field;
+    sa.cand = cand; sa.cand_ctx_stride = cand_ctx_stride; sa.N = N; sa.field = fields[0];
+    sa.nf = nf; sa.fields = packed; sa.swept = swept; sa.perm = perm;
     sa.nchunks = (int)(((int64_t)N + CFFM_SWEEP_CHUNK - 1) / CFFM_SWEEP_CHUNK);
     sa.units = (int64_t)C * sa.nchunks;
     sa.blocks = blocks; sa.block_floats = bo.floats;
-    sa.b0 = theta + tl.conv_b[0];
+    sa.W0 = ca.W0; sa.b0 = theta + tl.conv_b[0];
     sa.W1 = theta + tl.conv_w[1]; sa.b1 = theta + tl.conv_b[1];
     sa.W2 = theta + tl.conv_w[2]; sa.b2 = theta + tl.conv_b[2];
     sa.W3 = theta + tl.conv_w[3]; sa.b3 = theta + tl.conv_b[3];
@@ -724,22 +935,68 @@ static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const floa
     const int64_t max_grid = 512;
     const int grid = (int)(sa.units < max_grid ? sa.units : max_grid);
     hipStream_t st = (hipStream_t)stream;
-    switch (g.Pp / 16) {
-        case 1: return sweep_launch<1>(ca, sa, C, grid, st);
-        case 2: return sweep_launch<2>(ca, sa, C, grid, st);
-        case 3: return sweep_launch<3>(ca, sa, C, grid, st);
+    switch (g.Pp / 16 * 2 + (nf > 1)) {
+        case 2: return sweep_launch<1, false>(ca, sa, C, grid, st);
+        case 3: return sweep_launch<1, true>(ca, sa, C, grid, st);
+        case 4: return sweep_launch<2, false>(ca, sa, C, grid, st);
+        case 5: return sweep_launch<2, true>(ca, sa, C, grid, st);
+        case 6: return sweep_launch<3, false>(ca, sa, C, grid, st);
+        case 7: return sweep_launch<3, true>(ca, sa, C, grid, st);
         default: return CFFM_ERR_UNSUPPORTED;
     }
+}
+
+// cffm_score_sweep (cand_ctx_stride == 0: the shared list) and cffm_score_sweep_lists
+static int sweep_one_field(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C, int32_t field,
+                           const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores, int64_t row_stride, void* scratch,
+                           void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
+    if (field < 0 || field >= s->F || N < 1 || C < 0 || row_stride < N) return CFFM_ERR_BAD_SHAPE;
+    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < N)) return CFFM_ERR_BAD_SHAPE;
+    if (C == 0) return 0;
+    if (!tab || !tab->inner_emb || !tab->outer_emb || !tab->feat_bias || !theta || !ctx || !cand || !scores || !scratch)
+        return CFFM_ERR_BAD_SHAPE;
+    const int f = field, col = 0;
+    return sweep_run(s, tab, theta, ctx, C, 1, &f, &col, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
 }
 
 extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
                                 int32_t field, const int32_t* cand, int32_t N, float* scores, int64_t row_stride, void* scratch,
                                 void* stream) {
-    return sweep_run(s, tab, theta, ctx, C, field, cand, 0, N, scores, row_stride, scratch, stream);
+    return sweep_one_field(s, tab, theta, ctx, C, field, cand, 0, N, scores, row_stride, scratch, stream);
 }
 
 extern "C" int cffm_score_sweep_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
                                       int32_t field, const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores,
                                       int64_t row_stride, void* scratch, void* stream) {
-    return sweep_run(s, tab, theta, ctx, C, field, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
+    return sweep_one_field(s, tab, theta, ctx, C, field, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
+}
+
+// nf == 1 runs the single-field instance: the bits of cffm_score_sweep_lists
+extern "C" int cffm_score_sweep_tuples(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
+                                       const int32_t* fields, int32_t nf, const int32_t* cand, int64_t cand_ctx_stride, int32_t N,
+                                       float* scores, int64_t row_stride, void* scratch, void* stream) {
+    int rc = check_shape(s);
+    if (rc) return rc;
+    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
+    if (nf < 1 || nf > s->F || !fields) return CFFM_ERR_BAD_SHAPE;
+    int sorted[CFFM_MAX_FIELDS], col[CFFM_MAX_FIELDS], slot[CFFM_MAX_FIELDS];
+    for (int f = 0; f < s->F; ++f) slot[f] = -1;
+    for (int a = 0; a < nf; ++a) {
+        const int f = fields[a];
+        if (f < 0 || f >= s->F || slot[f] >= 0) return CFFM_ERR_BAD_SHAPE;         // outside [0, F), or the same field twice
+        slot[f] = a;
+    }
+    if (!cffm_sweep_tuples_ok(s, nf)) return CFFM_ERR_UNSUPPORTED;
+    if (N < 1 || C < 0 || row_stride < N) return CFFM_ERR_BAD_SHAPE;
+    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < (int64_t)N * nf)) return CFFM_ERR_BAD_SHAPE;
+    if (C == 0) return 0;
+    if (!tab || !tab->inner_emb || !tab->outer_emb || !tab->feat_bias || !theta || !ctx || !cand || !scores || !scratch)
+        return CFFM_ERR_BAD_SHAPE;
+    int n = 0;
+    for (int f = 0; f < s->F; ++f)                                                 // by field: the caller's order ends here
+        if (slot[f] >= 0) { sorted[n] = f; col[n] = slot[f]; ++n; }
+    return sweep_run(s, tab, theta, ctx, C, nf, sorted, col, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
 }

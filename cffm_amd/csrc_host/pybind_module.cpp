@@ -93,6 +93,10 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_score_sweep);
     CFFM_BIND(cffm_score_sweep_lists);
     CFFM_BIND(cffm_sweep_block_layout);
+    CFFM_BIND(cffm_sweep_tuples_ok);
+    CFFM_BIND(cffm_sweep_tuples_scratch_bytes);
+    CFFM_BIND(cffm_score_sweep_tuples);
+    CFFM_BIND(cffm_sweep_tuples_block_layout);
     CFFM_BIND(cffm_probe_copy);
     CFFM_BIND(cffm_probe_read);
     CFFM_BIND(cffm_probe_mfma);

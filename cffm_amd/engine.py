@@ -488,6 +488,38 @@ class HipEngine(object):
                                                   _ptr(scores), N, _ptr(self._sweep_scratch(nctx)), self._stream()))
         return scores
 
+    def sweep_tuples_ok(self, nf):
+        """True where score_candidate_tuples_shared serves this engine's shape for tuples of nf ids (cffm_sweep_tuples_ok)."""
+        return bool(self.lib.cffm_sweep_tuples_ok(self._s, int(nf)))
+
+    def score_candidate_tuples_shared(self, ctx, fields, cand):
+        """The scores of score_candidate_tuples with everything that involves no swept field done once per context
+        (cffm_score_sweep_tuples, csrc/sweep.hip): `fields` nf distinct columns in any order, cand int32 [N, nf] (one list for every
+        context) or [C, N, nf] (a list per context) on the device -> fp32 [C, N] on the device, equal to score_candidate_tuples to
+        rounding.  The per-context scratch is kept in self._ws under a key of its own, grow-only; nothing synchronises.
+        ValueError where (shape, nf) is not served (sweep_tuples_ok(nf))."""
+        F = int(self.cfg.F)
+        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        nf = len(fields)
+        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
+            raise ValueError('score_candidate_tuples_shared: needs 1 to %d distinct fields of [0, %d)' % (F, F))
+        ctx, cand, nctx, N, stride = self._cand_lists(ctx, cand, nf, 'score_candidate_tuples_shared')
+        if not self.sweep_tuples_ok(nf):
+            raise ValueError('score_candidate_tuples_shared: the tuple sweep does not serve this shape for tuples of %d '
+                             '(both branches, D = 32, F <= 10, nf <= 4, the candidate kernel within a CU\'s LDS)' % nf)
+        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
+        if nctx == 0:
+            return scores
+        scratch = self._ws.get('sweep_tuples')
+        nbytes = int(self.lib.cffm_sweep_tuples_scratch_bytes(self._s, nf, nctx))
+        if scratch is None or int(scratch.numel()) < nbytes:
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._ws['sweep_tuples'] = scratch
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        hip.check(self.lib.cffm_score_sweep_tuples(self._s, self._t, _ptr(self.theta), _ptr(ctx), nctx, C.addressof(host_fields), nf,
+                                                   _ptr(cand), stride, N, _ptr(scores), N, _ptr(scratch), self._stream()))
+        return scores
+
     def _rank_args(self, scores, skip):
         if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
             raise ValueError('scores must be fp32 [C, N] with contiguous rows')

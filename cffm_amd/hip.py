@@ -25,6 +25,7 @@ MAX_LAYERS = 8
 NSLAB = 64
 HEAD_UNITS = 32
 SWEEP_CHUNK = 64            # CFFM_SWEEP_CHUNK: candidates of one (context, chunk) unit of cffm_score_sweep
+SWEEP_MAX_NF = 4            # CFFM_SWEEP_MAX_NF: the most fields a tuple of cffm_score_sweep_tuples may replace together
 LOSS_IDS = {'square_loss': 0, 'mse': 1, 'mae': 2, 'log_loss': 3, 'hybrid': 5}
 OPT_IDS = {'AdagradOptimizer': 0, 'GradientDescentOptimizer': 1, 'MomentumOptimizer': 2, 'AdamOptimizer': 3}
 
@@ -69,6 +70,11 @@ class ConvChoice(C.Structure):
 
 class SweepBlock(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ('header_floats', 'block_floats', 'Z', 'U', 'V', 'Ei', 's0fix', 'A', 'fb', 'scal')]
+
+
+class SweepTuplesBlock(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ('header_floats', 'block_floats', 'Z', 'U', 'V', 'Ei', 's0fix', 'A', 'fb', 'scal',
+                                         'UV_stride', 'A_stride')]
 
 
 class Tables(C.Structure):
@@ -133,6 +139,10 @@ PROTOTYPES = {
     'cffm_score_sweep': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, _P]),
     'cffm_score_sweep_lists': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
     'cffm_sweep_block_layout': (C.c_int, [_SH, _P]),
+    'cffm_sweep_tuples_ok': (C.c_int, [_SH, C.c_int32]),
+    'cffm_sweep_tuples_scratch_bytes': (C.c_int64, [_SH, C.c_int32, C.c_int32]),
+    'cffm_score_sweep_tuples': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
+    'cffm_sweep_tuples_block_layout': (C.c_int, [_SH, C.c_int32, _P]),
     'cffm_probe_copy': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_read': (C.c_int, [_P, _P, C.c_int64, _P]),
     'cffm_probe_mfma': (C.c_int, [_P, C.c_int32, _P, _P]),
@@ -242,6 +252,13 @@ def sweep_block_layout(shape):
     """Where the shared sweep leaves its per-context intermediates in its scratch (cffm_sweep_block_layout, include/cffm_hip.h)."""
     bl = SweepBlock()
     check(load().cffm_sweep_block_layout(C.byref(shape), C.byref(bl)))
+    return bl
+
+
+def sweep_tuples_block_layout(shape, nf):
+    """The per-context block of the tuple sweep for nf swept fields (cffm_sweep_tuples_block_layout, include/cffm_hip.h)."""
+    bl = SweepTuplesBlock()
+    check(load().cffm_sweep_tuples_block_layout(C.byref(shape), int(nf), C.byref(bl)))
     return bl
 
 

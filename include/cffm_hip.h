@@ -469,6 +469,45 @@ typedef struct cffm_sweep_block {
 } cffm_sweep_block_t;
 int cffm_sweep_block_layout(const cffm_shape_t *s, cffm_sweep_block_t *out);
 
+/* ---- the shared sweep for candidates that are TUPLES of nf ids (cffm_amd/csrc/sweep.hip) -------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  cffm_score_sweep_tuples: scores[c * row_stride + n] = the raw prediction of
+ * context row ctx[c] with its ids at the nf columns `fields` replaced TOGETHER by candidate n - the value cffm_predict defines for
+ * the row cffm_expand_candidates_ex writes, to rounding.  fields: HOST int32 [nf], distinct columns of [0, F) in any order, read
+ * before the launch; the library sorts them and carries the column permutation, so fields = {6, 1} with the candidate columns
+ * swapped gives the bits of fields = {1, 6}.  cand: device int32, id a of candidate n of context c at
+ * cand[c * cand_ctx_stride + n * nf + a] (indexed in 64 bits); cand_ctx_stride == 0: one list [N][nf] for every context, otherwise
+ * >= N * nf.  Ids are clamped as cffm_predict clamps them.  A (context, tuple) pair gives the same bits at every position, under a
+ * shared list and under its own, and on every call.  nf == 1 runs cffm_score_sweep_lists' kernels and gives its bits.
+ * Per context everything that involves no swept field is computed once; per candidate layer 0 costs 4 nf multiply-adds plus 4 per
+ * swept-swept pair and output element, the inner branch the pairs with a swept field; above layer 0 nothing changes.
+ * Served domain (cffm_sweep_tuples_ok(s, nf) == 1, host only): cffm_sweep_ok(s), 1 <= nf <= min(F, CFFM_SWEEP_MAX_NF), and the
+ * candidate kernel's LDS for nf fields within a CU: nf = 2 at every F <= 10 (Pp = 48: 149,184 bytes at K = 32, served up to K = 160
+ * at F = 10), nf <= 4 at Pp <= 32; nf = 3 at Pp = 48 is not (164,160 bytes at K = 32).  cffm_sweep_tuples_ok(s, 1) == cffm_sweep_ok(s).
+ * scratch: cffm_sweep_tuples_scratch_bytes(s, nf, C) bytes (< 0: bad arguments or not served); linear in C, larger for a larger nf.
+ * Refusals, all before the first launch or HIP call, in this order: the shape check; CFFM_ERR_UNSUPPORTED where cffm_sweep_ok(s) == 0;
+ * CFFM_ERR_BAD_SHAPE for nf < 1, nf > F, fields == NULL, a field outside [0, F), the same field twice; CFFM_ERR_UNSUPPORTED where
+ * cffm_sweep_tuples_ok(s, nf) == 0; CFFM_ERR_BAD_SHAPE for N < 1, C < 0, row_stride < N, a negative stride, a non-zero stride below
+ * N * nf; C == 0 returns 0; CFFM_ERR_BAD_SHAPE for a NULL pointer that would be read or written. */
+#define CFFM_SWEEP_MAX_NF 4
+int cffm_sweep_tuples_ok(const cffm_shape_t *s, int32_t nf);
+int64_t cffm_sweep_tuples_scratch_bytes(const cffm_shape_t *s, int32_t nf, int32_t C);
+int cffm_score_sweep_tuples(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
+                            const int32_t *fields, int32_t nf, const int32_t *cand, int64_t cand_ctx_stride, int32_t N,
+                            float *scores, int64_t row_stride, void *scratch, void *stream);
+/* The block of cffm_sweep_block_layout for nf swept fields f_0 < f_1 < ... (sorted, whatever order the caller gave), for the
+ * per-stage tests; host only.  Members as there, with
+ *   U [nf][2][16][Pp] (a, dw, y, q)  V [nf][2][16][Pp] (a, dh, x, q): field f_a's at U + a * UV_stride, V + a * UV_stride
+ *   A [nf][32]: A_a at A + a * A_stride      scal [16]: [0] the inner sum of the pairs without a swept field, [1 + a] R_a
+ *   Ei, fb: every swept row / slot zero      Z: the pairs with no swept field
+ * U_a, V_a, A_a and R_a run over the fields that are NOT swept below / above f_a.  nf == 1 is the layout of cffm_sweep_block_layout.
+ * Refusals as there, for (s, nf) where cffm_sweep_tuples_ok is 0. */
+typedef struct cffm_sweep_tuples_block {
+    int64_t header_floats, block_floats;
+    int64_t Z, U, V, Ei, s0fix, A, fb, scal;
+    int64_t UV_stride, A_stride;
+} cffm_sweep_tuples_block_t;
+int cffm_sweep_tuples_block_layout(const cffm_shape_t *s, int32_t nf, cffm_sweep_tuples_block_t *out);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
