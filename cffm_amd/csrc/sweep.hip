@@ -45,13 +45,20 @@
 //     s0[h] = s0fix[h] + sum_a (A_a[h] rowsum(e_a) + e_a[h] R_a) + sum_{a<b} e_a[h] rowsum(e_b),   A_a / R_a over the fields not swept
 // The fixed inner sum keeps the pairs with no swept field; the per-candidate part runs over the list of all pairs with at least one;
 // the first-order term takes the candidates' feature_bias at every swept slot.  The context role is one kernel for every nf (U_a
-// on 2 nf wave roles over its four wavefronts; the block grows by U_a, V_a and A_a per field).  The candidate role has a second
-// instance per Pp (TUP): it stages all U_a / V_a and the swept-swept filter slices in LDS, fetches nf inner rows, outer rows and
-// biases ahead (one 16-byte piece per thread, nf (K/4 + D/4 + 1) threads), forms C_0 with 4 nf multiply-adds plus 4 per
-// swept-swept pair and element - per field in sorted order, then the pairs (a < b) - and from C_0 on runs the code above.  Its sums
-// depend on the thread mapping and the sorted field order alone.  nf = 1 runs the single-field instance, which is compiled to what it
-// was.  The LDS of the tuple instance (sweep_tuples_lds) decides what is served: nf = 2 at every F <= 10 (at F = 10 up to K = 160),
-// nf <= 4 at Pp <= 32; nf = 3 at Pp = 48 does not fit a CU.
+// on 2 nf wave roles over its four wavefronts; the block grows by U_a, V_a and A_a per field).  The candidate role is one code for
+// every nf as well, with the field count a template parameter: NF = 1 for one field (cffm_score_sweep, _lists, and tuples of one: the
+// loops over the swept fields unroll, the loop over the swept-swept pairs is empty) and NF = 0 for a.nf = 2 .. 4 at run time - two
+// instances per Pp.  It stages all U_a / V_a and the swept-swept filter slices in LDS, builds the list of live pairs by a ballot (one
+// straight-line barrier between the ballot and the gather of their dense(1) weights, for every instance), fetches nf inner rows,
+// outer rows and biases ahead (one 16-byte piece per thread, nf (K/4 + D/4 + 1) threads; a candidate's bias goes to its field's slot
+// of the feature_bias row), forms C_0 with 4 nf multiply-adds plus 4 per swept-swept pair and element - per field in sorted order,
+// then the pairs (a < b) - adds s0 one term at a time per field (A_a rowsum(e_a), e_a R_a, then the fields below a), and from C_0 on
+// runs the code above.  Its sums depend on the thread mapping and the sorted field order alone.  The one LDS formula (sweep_lds)
+// decides what is served: one field up to K = 408 at F = 10, nf = 2 at every F <= 10 (at F = 10 up to K = 160), nf <= 4 at Pp <= 32;
+// nf = 3 at Pp = 48 does not fit a CU.
+#include <cstddef>
+#include <cstring>
+
 #include "inner_body.hpp"
 #include "internal.hpp"
 
@@ -282,7 +289,7 @@ struct SweepArgs {
     const float *inner, *outer, *fbias;
     const int32_t* cand;
     int64_t cand_ctx_stride;               // elements between the lists of two contexts; 0: one list for all
-    int N, field, nchunks;
+    int N, nchunks;
     int64_t units;
     const float* blocks;
     int64_t block_floats;
@@ -291,55 +298,29 @@ struct SweepArgs {
     const float *d1_w, *d1_b, *d2_w, *d2_b, *att_W, *att_b, *lin_w, *lin_b, *bias;
     float* scores;
     int64_t row_stride;
-    // the tuple instance: the swept fields, sorted as in SweepCtxArgs (field = f_0); sweep_field(perm, a) = the caller's tuple column
-    // that holds the id of field f_a; W0: the layer-0 filter (its swept-swept pairs)
+    // the swept fields, sorted as in SweepCtxArgs; sweep_field(perm, a) = the caller's tuple column that holds the id of field f_a;
+    // W0: the layer-0 filter (its swept-swept pairs)
     int nf;
     uint32_t fields, swept, perm;
     const float* W0;
 };
 
-// LDS of the candidate role, in floats: C_0 | W_1 (padded image of conv_fwd_taps_body) | red | C_1 | C_2 | C_3 | U | V | small | rows
+// pairs with at least one of nf swept fields / with both
+__host__ __device__ inline int sweep_live_pairs(int F, int nf) { return F * (F - 1) / 2 - (F - nf) * (F - nf - 1) / 2; }
+__host__ __device__ inline int sweep_cross_pairs(int nf) { return nf * (nf - 1) / 2; }
+// LDS of the candidate role for nf swept fields, in floats: C_0 | W_1 (padded image of conv_fwd_taps_body) | red | C_1 | C_2 | C_3 |
+// U | V | small | rows | the layer-0 filter slices of the swept-swept pairs.  This one formula sizes the launch and answers
+// cffm_sweep_ok (nf = 1) and cffm_sweep_tuples_ok.  Bytes at (Pp, K, nf), F the largest of that Pp: (48, 32, 1) 134,656; (48, 32, 2)
+// 149,184; (48, 64, 2) 152,640; (48, 32, 3) 164,160 (832 over CFFM_LDS_WHOLE_CU: not served, nor is F = 9 at 163,648); (32, 32, 4)
+// 113,216; (16, 32, 4) 54,848.
 struct SweepLds { int C0, W1, red, C1, C2, C3, U, V, t1s, hpart, s0fix, A, fbrow, sc, wpart, lutf, aW, eo, Eall, wdp, Wx, floats; };
-__host__ __device__ inline SweepLds sweep_lds(int Pp, int F, int K) {
+__host__ __device__ inline SweepLds sweep_lds(int Pp, int F, int K, int nf) {
     SweepLds l;
     int o = 0;
     l.C0 = o; o += 256 * Pp;                 // layers 2 and 3 reuse it for their 8 wave partials (2048 * NT floats)
     l.W1 = o; o += 4 * Pp * (Pp + 4);
-    l.red = o; o += 64 * Pp;                 // layer 1: the partials of taps 2, 3 ([4 row tiles][NT][64 lanes] x 4)
-    l.C1 = o; o += 64 * Pp;
-    l.C2 = o; o += 16 * Pp;
-    l.C3 = o; o += 4 * Pp;
-    l.U = o; o += 2 * SWEEP_S * Pp;
-    l.V = o; o += 2 * SWEEP_S * Pp;
-    l.t1s = o; o += 64;
-    l.hpart = o; o += 8 * CFFM_HEAD_UNITS;
-    l.s0fix = o; o += SWEEP_D;
-    l.A = o; o += SWEEP_D;
-    l.fbrow = o; o += 16;
-    l.sc = o; o += 16;                       // [1] first-order term, [2] the candidate's feature_bias, [3] fixed inner sum, [4] R
-    l.wpart = o; o += 16;
-    l.lutf = o; o += 16;
-    l.aW = o; o += 128;                      // att_W [F][F], F <= 10
-    l.eo = o; o += SWEEP_D;                  // the candidate's outer row
-    l.Eall = o; o += F * K;                  // the context's inner rows with the candidate's row at f
-    l.wdp = o; o += (F - 1) * K;             // dense(1) weights of the pairs that contain f, by partner slot
-    l.Wx = o;                                // (tuples only)
-    l.floats = o;
-    return l;
-}
-// pairs with at least one of nf swept fields / with both
-__host__ __device__ inline int sweep_live_pairs(int F, int nf) { return F * (F - 1) / 2 - (F - nf) * (F - nf - 1) / 2; }
-__host__ __device__ inline int sweep_cross_pairs(int nf) { return nf * (nf - 1) / 2; }
-// The tuple instance of the candidate role: the same regions, U / V / A / eo once per swept field, the pair list of the inner branch
-// by live pair, and the layer-0 filter slices of the swept-swept pairs.  This one formula sizes the launch and answers
-// cffm_sweep_tuples_ok.  Bytes at (Pp, K, nf), F the largest of that Pp: (48, 32, 2) 149,184; (48, 64, 2) 152,640; (48, 32, 3)
-// 164,160 (832 over CFFM_LDS_WHOLE_CU: not served, nor is F = 9 at 163,648); (32, 32, 4) 113,216; (16, 32, 4) 54,848.
-__host__ __device__ inline SweepLds sweep_tuples_lds(int Pp, int F, int K, int nf) {
-    SweepLds l;
-    int o = 0;
-    l.C0 = o; o += 256 * Pp;
-    l.W1 = o; o += 4 * Pp * (Pp + 4);
-    l.red = o; o += 64 * Pp;
+    l.red = o; o += 64 * Pp;                 // layer 1: the partials of taps 2, 3 ([4 row tiles][NT][64 lanes] x 4); before the
+                                             // candidate loop: the pair indices of the live pairs while wdp is staged
     l.C1 = o; o += 64 * Pp;
     l.C2 = o; o += 16 * Pp;
     l.C3 = o; o += 4 * Pp;
@@ -352,11 +333,12 @@ __host__ __device__ inline SweepLds sweep_tuples_lds(int Pp, int F, int K, int n
     l.fbrow = o; o += 16;                    // feature_bias by field: the context's, the candidate's at the swept slots
     l.sc = o; o += 16;                       // [1] first-order term, [3] fixed inner sum, [4 + a] R_a
     l.wpart = o; o += 16;
-    l.lutf = o; o += 2 * 32;                 // the live pairs (i | j << 16), then their pair indices: at most 30 (F = 10, nf = 4)
-    l.aW = o; o += 128;
+    l.lutf = o; o += nf > 1 ? 64 : 16;       // the live pairs (i | j << 16): at most 9 for one field, 30 for tuples (F = 10, nf = 4).
+                                             // The served domain sits on these sizes: one field reaches K = 408 at F = 10 with 96 B left
+    l.aW = o; o += 128;                      // att_W [F][F], F <= 10
     l.eo = o; o += nf * SWEEP_D;             // the candidate's outer rows, by sorted field
-    l.Eall = o; o += F * K;
-    l.wdp = o; o += sweep_live_pairs(F, nf) * K;
+    l.Eall = o; o += F * K;                  // the context's inner rows with the candidate's rows at the swept fields
+    l.wdp = o; o += sweep_live_pairs(F, nf) * K;     // dense(1) weights of the live pairs, in pair order
     l.Wx = o; o += sweep_cross_pairs(nf) * 4 * Pp;   // [pair (a < b)][dh][dw][q]
     l.floats = o;
     return l;
@@ -460,19 +442,19 @@ __device__ __forceinline__ void sweep_conv_reduce(const float* red2, const float
     }
 }
 
-// TUP: the tuple instance (cffm_score_sweep_tuples, nf >= 2 swept fields).  It differs from the single-field one in what a candidate
-// brings (nf inner rows, outer rows and biases) and in how layer 0, the live inner pairs, s0 and the first-order term are put
-// together from the block; from C_0 on the two run the same code.  The single-field instance compiles to what it was.
-template <int NT, bool TUP>
+// NF: the number of swept fields as a compile-time constant (1: cffm_score_sweep / _lists, and tuples of one); 0: a.nf, 2 ..
+// CFFM_SWEEP_MAX_NF.  The body is one code for every nf; at NF = 1 its loops over the swept fields unroll and the loop over the
+// swept-swept pairs is empty.
+template <int NT, int NF>
 __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     constexpr int PP = NT * 16, PQ = PP / 4, NTH = SWEEP_NTH, NWV = NTH / 64, D = SWEEP_D, S = SWEEP_S;
     constexpr int ZR = S * S * PQ / NTH;                         // float4 of Zctx per thread: 2 * NT
     static_assert(ZR * NTH == S * S * PQ, "Zctx divides evenly over the workgroup");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Geo& g = a.g;
-    const int F = g.F, K = g.K, f = a.field, act = g.act, K4 = K / 4, K2 = K / 2;
-    const int nf = TUP ? a.nf : 1;
-    const SweepLds L = TUP ? sweep_tuples_lds(PP, F, K, nf) : sweep_lds(PP, F, K);
+    const int F = g.F, K = g.K, act = g.act, K4 = K / 4, K2 = K / 2;
+    const int nf = NF ? NF : a.nf;
+    const SweepLds L = sweep_lds(PP, F, K, nf);
     const SweepBlock bo = sweep_block(PP, F, K, nf);
     float* sm = reinterpret_cast<float*>(smem);
     float *C0 = sm + L.C0, *W1s = sm + L.W1, *red = sm + L.red, *C1 = sm + L.C1, *C2 = sm + L.C2, *C3 = sm + L.C3;
@@ -489,9 +471,10 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
         *reinterpret_cast<float4*>(W1s + tap * PP * (PP + 4) + krow * PP + (krow >> 2) * 16 + 4 * c4) =
             reinterpret_cast<const float4*>(a.W1)[i];
     }
-    if constexpr (TUP) {
-        // the live pairs (at least one swept field) in pair order: pair p on lane p of wave 0 (P <= 45), compacted by ballot
-        uint32_t* pidx = lutf + 32;
+    {
+        // the live pairs (at least one swept field) in pair order: pair p on lane p of wave 0 (P <= 45), compacted by ballot.  Their
+        // pair indices are needed only until wdp is gathered: they borrow `red`, which layer 1 first writes inside the candidate loop.
+        uint32_t* pidx = reinterpret_cast<uint32_t*>(red);
         if (wave == 0) {
             int i = 0, base = 0;
             while (i < F - 2 && lane >= base + F - 1 - i) { base += F - 1 - i; ++i; }
@@ -520,12 +503,6 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
                     Wx[pr * 4 * PP + i] = a.W0[(tap * PP + prow) * PP + q];
                 }
             }
-    } else {
-        for (int i = tid; i < (F - 1) * K; i += NTH) {           // partner slot sl: field sl below f, sl + 1 from f on
-            const int sl = i / K, c = i - sl * K, pi = sl < f ? sl : sl + 1;
-            wdp[i] = a.wd[(int64_t)(pi < f ? sweep_pair(pi, f, F) : sweep_pair(f, pi, F)) * K + c];
-        }
-        if (tid < 16) lutf[tid] = tid < F - 1 ? ((uint32_t)(tid < f ? tid : tid + 1) | ((uint32_t)f << 16)) : 0u;
     }
     if (g.linear_att)
         for (int i = tid; i < F * F; i += NTH) aW[i] = a.att_W[i];
@@ -544,47 +521,32 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
     if (lane < CFFM_HEAD_UNITS) { d1b = a.d1_b[lane]; d2w = a.d2_w[lane]; }
     if (lane < F && g.linear_att) { linw = a.lin_w[lane]; attb = a.att_b[lane]; }
     const float d2b = a.d2_b[0], linb = g.linear_att ? a.lin_b[0] : 0.f, biasv = a.bias[0], bdv = a.bd[0];
-    const int nun = (TUP ? sweep_live_pairs(F, nf) : F - 1) * K2;
+    const int nun = sweep_live_pairs(F, nf) * K2;
     float w2r[NT][2][NT], w3r[NT][2][NT];                        // this lane's filter fragments of layers 2 and 3, for the whole launch
     sweep_load_w<NT>(w2r, a.W2);
     sweep_load_w<NT>(w3r, a.W3);
 
-    // this thread's piece of a candidate's rows: K/4 inner pieces, D/4 outer pieces, one feature_bias value
+    // this thread's piece of a candidate's rows: per swept field K/4 inner pieces, D/4 outer pieces and one feature_bias value, field
+    // f_a's on threads [a * per, (a + 1) * per) (one field: slot 0 without the division, a constant for the compiler)
     const int32_t* cand = a.cand;                                // the current unit's list
-    // (tuples: the same pieces once per swept field, field f_a's on threads [a * per, (a + 1) * per))
-    const int per = K4 + D / 4 + 1, fa_slot = TUP ? tid / per : 0, fa_piece = tid - fa_slot * per;
+    const int per = K4 + D / 4 + 1, fa_slot = nf > 1 ? tid / per : 0, fa_piece = tid - fa_slot * per;
     auto fetch = [&](int n) -> float4 {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (TUP) {
-            if (tid < nf * per) {
-                const int id = sweep_clamp(cand[(int64_t)n * nf + sweep_field(a.perm, fa_slot)], g.M);
-                if (fa_piece < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + fa_piece];
-                else if (fa_piece < K4 + D / 4) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)id * (D / 4) + fa_piece - K4];
-                else v.x = a.fbias[id];
-            }
-            return v;
-        }
-        if (tid <= K4 + D / 4) {
-            const int id = sweep_clamp(cand[n], g.M);
-            if (tid < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + tid];
-            else if (tid < K4 + D / 4) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)id * (D / 4) + tid - K4];
+        if (tid < nf * per) {
+            const int id = sweep_clamp(cand[(int64_t)n * nf + sweep_field(a.perm, fa_slot)], g.M);
+            if (fa_piece < K4) v = reinterpret_cast<const float4*>(a.inner)[(int64_t)id * K4 + fa_piece];
+            else if (fa_piece < K4 + D / 4) v = reinterpret_cast<const float4*>(a.outer)[(int64_t)id * (D / 4) + fa_piece - K4];
             else v.x = a.fbias[id];
         }
         return v;
     };
     auto put = [&](const float4& v) {
-        if constexpr (TUP) {
-            if (tid < nf * per) {
-                const int fa = sweep_field(a.fields, fa_slot);
-                if (fa_piece < K4) reinterpret_cast<float4*>(Eall + fa * K)[fa_piece] = v;
-                else if (fa_piece < K4 + D / 4) reinterpret_cast<float4*>(eo + fa_slot * D)[fa_piece - K4] = v;
-                else fbrow[fa] = v.x;
-            }
-            return;
+        if (tid < nf * per) {
+            const int fa = sweep_field(a.fields, fa_slot);
+            if (fa_piece < K4) reinterpret_cast<float4*>(Eall + fa * K)[fa_piece] = v;
+            else if (fa_piece < K4 + D / 4) reinterpret_cast<float4*>(eo + fa_slot * D)[fa_piece - K4] = v;
+            else fbrow[fa] = v.x;
         }
-        if (tid < K4) reinterpret_cast<float4*>(Eall + f * K)[tid] = v;
-        else if (tid < K4 + D / 4) reinterpret_cast<float4*>(eo)[tid - K4] = v;
-        else if (tid == K4 + D / 4) sc[2] = v.x;
     };
 
     for (int64_t u = blockIdx.x; u < a.units; u += gridDim.x) {
@@ -608,20 +570,13 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
             reinterpret_cast<float4*>(Us)[i] = reinterpret_cast<const float4*>(blk + bo.U)[i];
             reinterpret_cast<float4*>(Vs)[i] = reinterpret_cast<const float4*>(blk + bo.V)[i];
         }
-        if constexpr (TUP) {                                     // the swept rows and slots are the candidate's: put() writes them
-            for (int i = tid; i < F * K4; i += NTH)
-                if (!((a.swept >> (i / K4)) & 1u)) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
-            if (tid < D) s0fix[tid] = blk[bo.s0fix + tid];
-            if (tid < nf * D) As[tid] = blk[bo.A + tid];
-            if (tid < 16 && !((a.swept >> tid) & 1u)) fbrow[tid] = blk[bo.fb + tid];
-            if (tid < 1 + nf) sc[3 + tid] = blk[bo.scal + tid];
-        } else {
-            for (int i = tid; i < F * K4; i += NTH)
-                if (i / K4 != f) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
-            if (tid < D) { s0fix[tid] = blk[bo.s0fix + tid]; As[tid] = blk[bo.A + tid]; }
-            if (tid < 16) fbrow[tid] = blk[bo.fb + tid];
-            if (tid < 2) sc[3 + tid] = blk[bo.scal + tid];
-        }
+        // the swept rows and slots are the candidate's: put() writes them
+        for (int i = tid; i < F * K4; i += NTH)
+            if (!((a.swept >> (i / K4)) & 1u)) reinterpret_cast<float4*>(Eall)[i] = reinterpret_cast<const float4*>(blk + bo.Ei)[i];
+        if (tid < D) s0fix[tid] = blk[bo.s0fix + tid];
+        if (tid < nf * D) As[tid] = blk[bo.A + tid];
+        if (tid < 16 && !((a.swept >> tid) & 1u)) fbrow[tid] = blk[bo.fb + tid];
+        if (tid < 1 + nf) sc[3 + tid] = blk[bo.scal + tid];
         float4 pre = fetch(n0);
         put(pre);
         __syncthreads();
@@ -633,47 +588,34 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
 #pragma unroll
             for (int k = 0; k < ZR; ++k) {
                 const int i4 = tid + NTH * k, q4 = i4 % PQ, pix = i4 / PQ, y = pix >> 4, x = pix & 15;
-                if constexpr (TUP) {
-                    // per swept field, in sorted order, the four terms of the single-field sweep; then the swept-swept pairs
-                    // (a < b), each X_ab = sum_dh sum_dw (e_a[2y+dh] * e_b[2x+dw]) * W[dh][dw][(f_a, f_b)]
-                    float4 z = Zr[k];
-                    for (int sa = 0; sa < nf; ++sa) {
-                        const float* ea = eo + sa * D;
-                        const float ex0 = ea[2 * x], ex1 = ea[2 * x + 1], ey0 = ea[2 * y], ey1 = ea[2 * y + 1];
-                        const float4 u0 = reinterpret_cast<const float4*>(Us)[((2 * sa) * S + y) * PQ + q4];
-                        const float4 u1 = reinterpret_cast<const float4*>(Us)[((2 * sa + 1) * S + y) * PQ + q4];
-                        const float4 v0 = reinterpret_cast<const float4*>(Vs)[((2 * sa) * S + x) * PQ + q4];
-                        const float4 v1 = reinterpret_cast<const float4*>(Vs)[((2 * sa + 1) * S + x) * PQ + q4];
-                        z.x = fmaf(ey1, v1.x, fmaf(ey0, v0.x, fmaf(ex1, u1.x, fmaf(ex0, u0.x, z.x))));
-                        z.y = fmaf(ey1, v1.y, fmaf(ey0, v0.y, fmaf(ex1, u1.y, fmaf(ex0, u0.y, z.y))));
-                        z.z = fmaf(ey1, v1.z, fmaf(ey0, v0.z, fmaf(ex1, u1.z, fmaf(ex0, u0.z, z.z))));
-                        z.w = fmaf(ey1, v1.w, fmaf(ey0, v0.w, fmaf(ex1, u1.w, fmaf(ex0, u0.w, z.w))));
-                    }
-                    const float4* wx = reinterpret_cast<const float4*>(sm + L.Wx) + q4;
-                    for (int sa = 0; sa < nf; ++sa)
-                        for (int sb = sa + 1; sb < nf; ++sb, wx += 4 * PQ) {
-                            const float *ea = eo + sa * D, *eb = eo + sb * D;
-                            const float p00 = ea[2 * y] * eb[2 * x], p01 = ea[2 * y] * eb[2 * x + 1];
-                            const float p10 = ea[2 * y + 1] * eb[2 * x], p11 = ea[2 * y + 1] * eb[2 * x + 1];
-                            const float4 w00 = wx[0], w01 = wx[PQ], w10 = wx[2 * PQ], w11 = wx[3 * PQ];
-                            z.x = fmaf(p11, w11.x, fmaf(p10, w10.x, fmaf(p01, w01.x, fmaf(p00, w00.x, z.x))));
-                            z.y = fmaf(p11, w11.y, fmaf(p10, w10.y, fmaf(p01, w01.y, fmaf(p00, w00.y, z.y))));
-                            z.z = fmaf(p11, w11.z, fmaf(p10, w10.z, fmaf(p01, w01.z, fmaf(p00, w00.z, z.z))));
-                            z.w = fmaf(p11, w11.w, fmaf(p10, w10.w, fmaf(p01, w01.w, fmaf(p00, w00.w, z.w))));
-                        }
-                    reinterpret_cast<float4*>(C0)[i4] = make_float4(fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f));
-                    continue;
-                }
-                const float ex0 = eo[2 * x], ex1 = eo[2 * x + 1], ey0 = eo[2 * y], ey1 = eo[2 * y + 1];
-                const float4 u0 = reinterpret_cast<const float4*>(Us)[y * PQ + q4];
-                const float4 u1 = reinterpret_cast<const float4*>(Us)[(S + y) * PQ + q4];
-                const float4 v0 = reinterpret_cast<const float4*>(Vs)[x * PQ + q4];
-                const float4 v1 = reinterpret_cast<const float4*>(Vs)[(S + x) * PQ + q4];
+                // z += p0 * w0 + p1 * w1 + p2 * w2 + p3 * w3, four multiply-adds per channel in this order
+                auto fma4 = [](float4& z, float p0, const float4& w0, float p1, const float4& w1, float p2, const float4& w2, float p3,
+                               const float4& w3) {
+                    z.x = fmaf(p3, w3.x, fmaf(p2, w2.x, fmaf(p1, w1.x, fmaf(p0, w0.x, z.x))));
+                    z.y = fmaf(p3, w3.y, fmaf(p2, w2.y, fmaf(p1, w1.y, fmaf(p0, w0.y, z.y))));
+                    z.z = fmaf(p3, w3.z, fmaf(p2, w2.z, fmaf(p1, w1.z, fmaf(p0, w0.z, z.z))));
+                    z.w = fmaf(p3, w3.w, fmaf(p2, w2.w, fmaf(p1, w1.w, fmaf(p0, w0.w, z.w))));
+                };
+                // per swept field, in sorted order: e_a[2x+dw] * U_a[dw][y], then e_a[2y+dh] * V_a[dh][x]
                 float4 z = Zr[k];
-                z.x = fmaf(ey1, v1.x, fmaf(ey0, v0.x, fmaf(ex1, u1.x, fmaf(ex0, u0.x, z.x))));
-                z.y = fmaf(ey1, v1.y, fmaf(ey0, v0.y, fmaf(ex1, u1.y, fmaf(ex0, u0.y, z.y))));
-                z.z = fmaf(ey1, v1.z, fmaf(ey0, v0.z, fmaf(ex1, u1.z, fmaf(ex0, u0.z, z.z))));
-                z.w = fmaf(ey1, v1.w, fmaf(ey0, v0.w, fmaf(ex1, u1.w, fmaf(ex0, u0.w, z.w))));
+                for (int sa = 0; sa < nf; ++sa) {
+                    const float* ea = eo + sa * D;
+                    const float ex0 = ea[2 * x], ex1 = ea[2 * x + 1], ey0 = ea[2 * y], ey1 = ea[2 * y + 1];
+                    // (the spelling of these four addresses decides the register count of the single-field instances: this one
+                    // keeps all six at or below what they took with a path of their own, profiles/sweep_one_path.md)
+                    const int iv = (2 * sa * S + x) * PQ + q4;
+                    fma4(z, ex0, reinterpret_cast<const float4*>(Us)[((2 * sa) * S + y) * PQ + q4], ex1,
+                         reinterpret_cast<const float4*>(Us)[((2 * sa + 1) * S + y) * PQ + q4], ey0, reinterpret_cast<const float4*>(Vs)[iv],
+                         ey1, reinterpret_cast<const float4*>(Vs)[iv + S * PQ]);
+                }
+                // then the swept-swept pairs (a < b), each X_ab = sum_dh sum_dw (e_a[2y+dh] * e_b[2x+dw]) * W[dh][dw][(f_a, f_b)]
+                const float4* wx = reinterpret_cast<const float4*>(sm + L.Wx) + q4;
+                for (int sa = 0; sa < nf; ++sa)
+                    for (int sb = sa + 1; sb < nf; ++sb, wx += 4 * PQ) {
+                        const float *ea = eo + sa * D, *eb = eo + sb * D;
+                        fma4(z, ea[2 * y] * eb[2 * x], wx[0], ea[2 * y] * eb[2 * x + 1], wx[PQ], ea[2 * y + 1] * eb[2 * x], wx[2 * PQ],
+                             ea[2 * y + 1] * eb[2 * x + 1], wx[3 * PQ]);
+                    }
                 reinterpret_cast<float4*>(C0)[i4] = make_float4(fmaxf(z.x, 0.f), fmaxf(z.y, 0.f), fmaxf(z.z, 0.f), fmaxf(z.w, 0.f));
             }
             {
@@ -687,24 +629,22 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
                 part = wave_sum(part);
                 if (lane == 0) wpart[wave] = part;
             }
-            if (TUP && wave == 0) {      // s0[h] = s0fix[h] + sum_a (A_a[h] * rowsum(e_a) + e_a[h] * R_a) + sum_{a<b} e_a[h] * rowsum(e_b)
+            if (wave == 0) {             // s0[h] = s0fix[h] + sum_a (A_a[h] * rowsum(e_a) + e_a[h] * R_a) + sum_{a<b} e_a[h] * rowsum(e_b),
+                                         // one term at a time onto s, per field in sorted order: A_a, R_a, then the fields below a
                 float s = lane < D ? s0fix[lane] : 0.f, below = 0.f;                 // below: sum of e_a'[h] over a' < a
+#pragma nounroll                         // a run-time nf keeps one loop body (peeling a = 0 off cost the kernel two VGPRs)
                 for (int sa = 0; sa < nf; ++sa) {
                     const float ev = lane < D ? eo[sa * D + lane] : 0.f;
                     const float rse = wave_sum(ev);
-                    s += (lane < D ? As[sa * D + lane] : 0.f) * rse + ev * sc[4 + sa];
-                    s += below * rse;
+                    s = s + (lane < D ? As[sa * D + lane] : 0.f) * rse;
+                    s = s + ev * sc[4 + sa];
+                    if (sa > 0) s = s + below * rse;
                     below += ev;
                 }
                 if (lane < D) t1s[lane] = s;
             }
-            if (!TUP && wave == 0) {                             // s0[h] = s0fix[h] + A[h] * rowsum(e) + e[h] * R
-                const float ev = lane < D ? eo[lane] : 0.f;
-                const float rse = wave_sum(ev);
-                if (lane < D) t1s[lane] = s0fix[lane] + As[lane] * rse + ev * sc[4];
-            }
             if (wave == NWV - 1) {                               // first-order term (head_fwd_body), CFFM.py:422-446
-                const float fbv = lane < F ? ((!TUP && lane == f) ? sc[2] : fbrow[lane]) : 0.f;
+                const float fbv = lane < F ? fbrow[lane] : 0.f;
                 float lin;
                 if (g.linear_att) {
                     float z = attb;
@@ -809,21 +749,19 @@ __global__ __launch_bounds__(SWEEP_NTH) void sweep_cand_kernel(SweepArgs a) {
 }
 
 // LDS of the candidate role for nf swept fields, in bytes: what the launcher asks for and what the served-domain queries compare
-static inline size_t sweep_cand_lds(int Pp, int F, int K, int nf) {
-    return (size_t)(nf > 1 ? sweep_tuples_lds(Pp, F, K, nf) : sweep_lds(Pp, F, K)).floats * 4;
-}
+static inline size_t sweep_cand_lds(int Pp, int F, int K, int nf) { return (size_t)sweep_lds(Pp, F, K, nf).floats * 4; }
 
-template <int NT, bool TUP>
+template <int NT, int NF>
 int sweep_launch(const SweepCtxArgs& ca, const SweepArgs& sa, int C, int grid, hipStream_t st) {
     const Geo& g = sa.g;
     const size_t lds_c = sweep_ctx_lds(g.Pp, g.F, g.K), lds_k = sweep_cand_lds(g.Pp, g.F, g.K, sa.nf);
     int rc = set_lds(sweep_ctx_kernel<NT>, lds_c);
     if (rc) return rc;
-    rc = set_lds(sweep_cand_kernel<NT, TUP>, lds_k);
+    rc = set_lds(sweep_cand_kernel<NT, NF>, lds_k);
     if (rc) return rc;
     hipLaunchKernelGGL(sweep_ctx_kernel<NT>, dim3((unsigned)C), dim3(256), lds_c, st, ca);
     CFFM_CHECK_LAUNCH();
-    hipLaunchKernelGGL((sweep_cand_kernel<NT, TUP>), dim3((unsigned)grid), dim3(SWEEP_NTH), lds_k, st, sa);
+    hipLaunchKernelGGL((sweep_cand_kernel<NT, NF>), dim3((unsigned)grid), dim3(SWEEP_NTH), lds_k, st, sa);
     CFFM_CHECK_LAUNCH();
     return 0;
 }
@@ -837,28 +775,8 @@ extern "C" int cffm_sweep_ok(const cffm_shape_t* s) {
     if (check_lds(s)) return 0;
     if (s->K / 4 + SWEEP_D / 4 + 1 > SWEEP_NTH) return 0;                          // a candidate's rows: one piece per thread
     if (sweep_ctx_lds(g.Pp, g.F, g.K) > (size_t)CFFM_LDS_WHOLE_CU) return 0;
-    if ((size_t)sweep_lds(g.Pp, g.F, g.K).floats * 4 > (size_t)CFFM_LDS_WHOLE_CU) return 0;
+    if (sweep_cand_lds(g.Pp, g.F, g.K, 1) > (size_t)CFFM_LDS_WHOLE_CU) return 0;
     return 1;
-}
-
-extern "C" int64_t cffm_sweep_scratch_bytes(const cffm_shape_t* s, int32_t C) {
-    if (C < 0 || !cffm_sweep_ok(s)) return -1;
-    const Geo g = make_geo(s);
-    return SWEEP_HEADER + (int64_t)C * sweep_block(g.Pp, g.F, g.K).floats * 4;
-}
-
-extern "C" int cffm_sweep_block_layout(const cffm_shape_t* s, cffm_sweep_block_t* out) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (!out) return CFFM_ERR_BAD_SHAPE;
-    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
-    const Geo g = make_geo(s);
-    const SweepBlock b = sweep_block(g.Pp, g.F, g.K);
-    out->header_floats = SWEEP_HEADER / 4;
-    out->block_floats = b.floats;
-    out->Z = b.Z; out->U = b.U; out->V = b.V; out->Ei = b.Ei;
-    out->s0fix = b.s0fix; out->A = b.A; out->fb = b.fb; out->scal = b.scal;
-    return 0;
 }
 
 extern "C" int cffm_sweep_tuples_ok(const cffm_shape_t* s, int32_t nf) {
@@ -874,20 +792,36 @@ extern "C" int64_t cffm_sweep_tuples_scratch_bytes(const cffm_shape_t* s, int32_
     return SWEEP_HEADER + (int64_t)C * sweep_block(g.Pp, g.F, g.K, nf).floats * 4;
 }
 
-extern "C" int cffm_sweep_tuples_block_layout(const cffm_shape_t* s, int32_t nf, cffm_sweep_tuples_block_t* out) {
+extern "C" int64_t cffm_sweep_scratch_bytes(const cffm_shape_t* s, int32_t C) { return cffm_sweep_tuples_scratch_bytes(s, 1, C); }
+
+// The block layout for nf swept fields into *t.  `out` is the caller's pointer, looked at only for the refusal, in the documented order.
+static int sweep_layout(const cffm_shape_t* s, int32_t nf, const void* out, cffm_sweep_tuples_block_t* t) {
     int rc = check_shape(s);
     if (rc) return rc;
     if (!out) return CFFM_ERR_BAD_SHAPE;
     if (!cffm_sweep_tuples_ok(s, nf)) return CFFM_ERR_UNSUPPORTED;
     const Geo g = make_geo(s);
     const SweepBlock b = sweep_block(g.Pp, g.F, g.K, nf);
-    out->header_floats = SWEEP_HEADER / 4;
-    out->block_floats = b.floats;
-    out->Z = b.Z; out->U = b.U; out->V = b.V; out->Ei = b.Ei;
-    out->s0fix = b.s0fix; out->A = b.A; out->fb = b.fb; out->scal = b.scal;
-    out->UV_stride = 2 * SWEEP_S * g.Pp;
-    out->A_stride = SWEEP_D;
+    t->header_floats = SWEEP_HEADER / 4;
+    t->block_floats = b.floats;
+    t->Z = b.Z; t->U = b.U; t->V = b.V; t->Ei = b.Ei;
+    t->s0fix = b.s0fix; t->A = b.A; t->fb = b.fb; t->scal = b.scal;
+    t->UV_stride = 2 * SWEEP_S * g.Pp;
+    t->A_stride = SWEEP_D;
     return 0;
+}
+
+extern "C" int cffm_sweep_tuples_block_layout(const cffm_shape_t* s, int32_t nf, cffm_sweep_tuples_block_t* out) {
+    return sweep_layout(s, nf, out, out);
+}
+
+// the nf = 1 answer without the two stride members, which end the tuples' struct
+static_assert(offsetof(cffm_sweep_tuples_block_t, UV_stride) == sizeof(cffm_sweep_block_t), "cffm_sweep_block_t is a prefix");
+extern "C" int cffm_sweep_block_layout(const cffm_shape_t* s, cffm_sweep_block_t* out) {
+    cffm_sweep_tuples_block_t t;
+    const int rc = sweep_layout(s, 1, out, &t);
+    if (rc == 0) memcpy(out, &t, sizeof *out);
+    return rc;
 }
 
 // The two launches for nf swept fields, sorted: fields[a] = f_a, col[a] = the caller's tuple column of f_a.  Every argument has been
@@ -916,7 +850,7 @@ static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const floa
     SweepArgs sa;
     sa.g = g; sa.loss = s->loss;
     sa.inner = tab->inner_emb; sa.outer = tab->outer_emb; sa.fbias = tab->feat_bias;
-    sa.cand = cand; sa.cand_ctx_stride = cand_ctx_stride; sa.N = N; sa.field = fields[0];
+    sa.cand = cand; sa.cand_ctx_stride = cand_ctx_stride; sa.N = N;
     sa.nf = nf; sa.fields = packed; sa.swept = swept; sa.perm = perm;
     sa.nchunks = (int)(((int64_t)N + CFFM_SWEEP_CHUNK - 1) / CFFM_SWEEP_CHUNK);
     sa.units = (int64_t)C * sa.nchunks;
@@ -935,46 +869,19 @@ static int sweep_run(const cffm_shape_t* s, const cffm_tables_t* tab, const floa
     const int64_t max_grid = 512;
     const int grid = (int)(sa.units < max_grid ? sa.units : max_grid);
     hipStream_t st = (hipStream_t)stream;
-    switch (g.Pp / 16 * 2 + (nf > 1)) {
-        case 2: return sweep_launch<1, false>(ca, sa, C, grid, st);
-        case 3: return sweep_launch<1, true>(ca, sa, C, grid, st);
-        case 4: return sweep_launch<2, false>(ca, sa, C, grid, st);
-        case 5: return sweep_launch<2, true>(ca, sa, C, grid, st);
-        case 6: return sweep_launch<3, false>(ca, sa, C, grid, st);
-        case 7: return sweep_launch<3, true>(ca, sa, C, grid, st);
+    switch (g.Pp / 16 * 2 + (nf > 1)) {                          // one field: the count compiled in; tuples: a.nf
+        case 2: return sweep_launch<1, 1>(ca, sa, C, grid, st);
+        case 3: return sweep_launch<1, 0>(ca, sa, C, grid, st);
+        case 4: return sweep_launch<2, 1>(ca, sa, C, grid, st);
+        case 5: return sweep_launch<2, 0>(ca, sa, C, grid, st);
+        case 6: return sweep_launch<3, 1>(ca, sa, C, grid, st);
+        case 7: return sweep_launch<3, 0>(ca, sa, C, grid, st);
         default: return CFFM_ERR_UNSUPPORTED;
     }
 }
 
-// cffm_score_sweep (cand_ctx_stride == 0: the shared list) and cffm_score_sweep_lists
-static int sweep_one_field(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C, int32_t field,
-                           const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores, int64_t row_stride, void* scratch,
-                           void* stream) {
-    int rc = check_shape(s);
-    if (rc) return rc;
-    if (!cffm_sweep_ok(s)) return CFFM_ERR_UNSUPPORTED;
-    if (field < 0 || field >= s->F || N < 1 || C < 0 || row_stride < N) return CFFM_ERR_BAD_SHAPE;
-    if (cand_ctx_stride < 0 || (cand_ctx_stride != 0 && cand_ctx_stride < N)) return CFFM_ERR_BAD_SHAPE;
-    if (C == 0) return 0;
-    if (!tab || !tab->inner_emb || !tab->outer_emb || !tab->feat_bias || !theta || !ctx || !cand || !scores || !scratch)
-        return CFFM_ERR_BAD_SHAPE;
-    const int f = field, col = 0;
-    return sweep_run(s, tab, theta, ctx, C, 1, &f, &col, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
-}
-
-extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
-                                int32_t field, const int32_t* cand, int32_t N, float* scores, int64_t row_stride, void* scratch,
-                                void* stream) {
-    return sweep_one_field(s, tab, theta, ctx, C, field, cand, 0, N, scores, row_stride, scratch, stream);
-}
-
-extern "C" int cffm_score_sweep_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
-                                      int32_t field, const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores,
-                                      int64_t row_stride, void* scratch, void* stream) {
-    return sweep_one_field(s, tab, theta, ctx, C, field, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
-}
-
-// nf == 1 runs the single-field instance: the bits of cffm_score_sweep_lists
+// The one checked entry: cffm_score_sweep_tuples.  Its refusals, in the order include/cffm_hip.h documents; for one field they are those
+// of cffm_score_sweep / _lists in theirs (cffm_sweep_tuples_ok(s, 1) == cffm_sweep_ok(s), and what lies between is CFFM_ERR_BAD_SHAPE).
 extern "C" int cffm_score_sweep_tuples(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
                                        const int32_t* fields, int32_t nf, const int32_t* cand, int64_t cand_ctx_stride, int32_t N,
                                        float* scores, int64_t row_stride, void* scratch, void* stream) {
@@ -999,4 +906,16 @@ extern "C" int cffm_score_sweep_tuples(const cffm_shape_t* s, const cffm_tables_
     for (int f = 0; f < s->F; ++f)                                                 // by field: the caller's order ends here
         if (slot[f] >= 0) { sorted[n] = f; col[n] = slot[f]; ++n; }
     return sweep_run(s, tab, theta, ctx, C, nf, sorted, col, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
+}
+
+extern "C" int cffm_score_sweep(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
+                                int32_t field, const int32_t* cand, int32_t N, float* scores, int64_t row_stride, void* scratch,
+                                void* stream) {
+    return cffm_score_sweep_tuples(s, tab, theta, ctx, C, &field, 1, cand, 0, N, scores, row_stride, scratch, stream);
+}
+
+extern "C" int cffm_score_sweep_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const float* theta, const int32_t* ctx, int32_t C,
+                                      int32_t field, const int32_t* cand, int64_t cand_ctx_stride, int32_t N, float* scores,
+                                      int64_t row_stride, void* scratch, void* stream) {
+    return cffm_score_sweep_tuples(s, tab, theta, ctx, C, &field, 1, cand, cand_ctx_stride, N, scores, row_stride, scratch, stream);
 }

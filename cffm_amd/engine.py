@@ -453,21 +453,30 @@ class HipEngine(object):
         C = int(ctx.shape[0])
         if not self.sweep_ok():
             raise ValueError('score_candidates_shared: the shared sweep does not serve this shape (both branches, D = 32, F <= 10)')
-        scores = torch.empty((C, N), dtype=torch.float32, device=self.device)
-        if C == 0:
-            return scores
-        hip.check(self.lib.cffm_score_sweep(self._s, self._t, _ptr(self.theta), _ptr(ctx), C, int(field), _ptr(cand), N, _ptr(scores),
-                                            N, _ptr(self._sweep_scratch(C)), self._stream()))
-        return scores
+        return self._sweep_launch('sweep', ctx, C, [int(field)], cand, 0, N)
 
-    def _sweep_scratch(self, n_ctx):
-        """The grow-only per-context scratch of the two shared sweeps (cffm_sweep_scratch_bytes)."""
-        scratch = self._ws.get('sweep')
-        nbytes = int(self.lib.cffm_sweep_scratch_bytes(self._s, n_ctx))
+    def _sweep_scratch(self, n_ctx, nf=1, key='sweep'):
+        """The grow-only per-context scratch of the shared sweeps for nf swept fields (cffm_sweep_tuples_scratch_bytes; nf = 1 is
+        cffm_sweep_scratch_bytes), kept in self._ws[key]."""
+        scratch = self._ws.get(key)
+        nbytes = int(self.lib.cffm_sweep_tuples_scratch_bytes(self._s, nf, n_ctx))
         if scratch is None or int(scratch.numel()) < nbytes:
             scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws['sweep'] = scratch
+            self._ws[key] = scratch
         return scratch
+
+    def _sweep_launch(self, key, ctx, nctx, fields, cand, stride, N):
+        """The two launches of the three score_*_shared methods, every argument checked: cffm_score_sweep_tuples, the entry point
+        cffm_score_sweep and cffm_score_sweep_lists forward to with one field -> fp32 [nctx, N] on the device."""
+        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
+        if nctx == 0:
+            return scores
+        nf = len(fields)
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        hip.check(self.lib.cffm_score_sweep_tuples(self._s, self._t, _ptr(self.theta), _ptr(ctx), nctx, C.addressof(host_fields), nf,
+                                                   _ptr(cand), stride, N, _ptr(scores), N, _ptr(self._sweep_scratch(nctx, nf, key)),
+                                                   self._stream()))
+        return scores
 
     def score_candidate_lists_shared(self, ctx, field, cand):
         """score_candidates_shared with a candidate list per context: cand int32 [C, N] on the device, row c scored against its own
@@ -481,12 +490,7 @@ class HipEngine(object):
             raise ValueError('score_candidate_lists_shared: needs 0 <= field < %d' % F)
         if not self.sweep_ok():
             raise ValueError('score_candidate_lists_shared: the shared sweep does not serve this shape (both branches, D = 32, F <= 10)')
-        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
-        if nctx == 0:
-            return scores
-        hip.check(self.lib.cffm_score_sweep_lists(self._s, self._t, _ptr(self.theta), _ptr(ctx), nctx, int(field), _ptr(cand), N, N,
-                                                  _ptr(scores), N, _ptr(self._sweep_scratch(nctx)), self._stream()))
-        return scores
+        return self._sweep_launch('sweep', ctx, nctx, [int(field)], cand, N, N)
 
     def sweep_tuples_ok(self, nf):
         """True where score_candidate_tuples_shared serves this engine's shape for tuples of nf ids (cffm_sweep_tuples_ok)."""
@@ -507,18 +511,7 @@ class HipEngine(object):
         if not self.sweep_tuples_ok(nf):
             raise ValueError('score_candidate_tuples_shared: the tuple sweep does not serve this shape for tuples of %d '
                              '(both branches, D = 32, F <= 10, nf <= 4, the candidate kernel within a CU\'s LDS)' % nf)
-        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
-        if nctx == 0:
-            return scores
-        scratch = self._ws.get('sweep_tuples')
-        nbytes = int(self.lib.cffm_sweep_tuples_scratch_bytes(self._s, nf, nctx))
-        if scratch is None or int(scratch.numel()) < nbytes:
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws['sweep_tuples'] = scratch
-        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
-        hip.check(self.lib.cffm_score_sweep_tuples(self._s, self._t, _ptr(self.theta), _ptr(ctx), nctx, C.addressof(host_fields), nf,
-                                                   _ptr(cand), stride, N, _ptr(scores), N, _ptr(scratch), self._stream()))
-        return scores
+        return self._sweep_launch('sweep_tuples', ctx, nctx, fields, cand, stride, N)
 
     def _rank_args(self, scores, skip):
         if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):

@@ -450,7 +450,7 @@ int cffm_score_sweep(const cffm_shape_t *s, const cffm_tables_t *tab, const floa
  * cand[c * cand_ctx_stride + n] (indexed in 64 bits); cand_ctx_stride == 0 is the one shared list, otherwise it is >= N and what lies
  * beyond N of a context's block is never read.  The same two kernels, served domain (cffm_sweep_ok) and scratch
  * (cffm_sweep_scratch_bytes).  A (context, id) pair gives the same bits under a shared list, under its own list, at any position
- * and on every call.  One field only: tuples (cffm_expand_candidates_ex with nf > 1) are not served by the sweep.  Refusals: those
+ * and on every call.  One field only: this and cffm_score_sweep are cffm_score_sweep_tuples (below) with nf = 1.  Refusals: those
  * of cffm_score_sweep, in the same order, plus CFFM_ERR_BAD_SHAPE for a negative stride or a non-zero stride below N. */
 int cffm_score_sweep_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const float *theta, const int32_t *ctx, int32_t C,
                            int32_t field, const int32_t *cand, int64_t cand_ctx_stride, int32_t N, float *scores, int64_t row_stride,
@@ -477,7 +477,9 @@ int cffm_sweep_block_layout(const cffm_shape_t *s, cffm_sweep_block_t *out);
  * swapped gives the bits of fields = {1, 6}.  cand: device int32, id a of candidate n of context c at
  * cand[c * cand_ctx_stride + n * nf + a] (indexed in 64 bits); cand_ctx_stride == 0: one list [N][nf] for every context, otherwise
  * >= N * nf.  Ids are clamped as cffm_predict clamps them.  A (context, tuple) pair gives the same bits at every position, under a
- * shared list and under its own, and on every call.  nf == 1 runs cffm_score_sweep_lists' kernels and gives its bits.
+ * shared list and under its own, and on every call.  One candidate role serves every nf (the field count is compiled in for one field
+ * and read at run time for 2 .. CFFM_SWEEP_MAX_NF); cffm_score_sweep and cffm_score_sweep_lists are this function with nf = 1, so
+ * nf == 1 here gives their bits.
  * Per context everything that involves no swept field is computed once; per candidate layer 0 costs 4 nf multiply-adds plus 4 per
  * swept-swept pair and output element, the inner branch the pairs with a swept field; above layer 0 nothing changes.
  * Served domain (cffm_sweep_tuples_ok(s, nf) == 1, host only): cffm_sweep_ok(s), 1 <= nf <= min(F, CFFM_SWEEP_MAX_NF), and the

@@ -70,6 +70,17 @@ def test_served_table(libs):
     assert score(libs, frappe, (1, 6, 8), 3) == (BAD if three else UNSUPPORTED)
 
 
+def test_served_boundaries_in_K(libs):
+    """The last K served per (F, nf) that DESIGN.md 3.6.2 states, each with its first unserved neighbour: the candidate role's one
+    LDS formula decides them, to the byte (one field at F = 10, K = 408 has 96 bytes to spare)."""
+    ok = lambda F, K, nf: both(libs, 'cffm_sweep_tuples_ok', shape(F, K), nf)
+    for F, nf, last in ((10, 1, 408), (10, 2, 160), (10, 3, 24), (9, 3, 28), (8, 4, 448)):
+        assert ok(F, last, nf) == 1 and ok(F, last + 4, nf) == 0, (F, nf, last)
+        assert both(libs, 'cffm_sweep_tuples_scratch_bytes', shape(F, last), nf, 1) > 0
+        assert both(libs, 'cffm_sweep_tuples_scratch_bytes', shape(F, last + 4), nf, 1) < 0
+    assert both(libs, 'cffm_sweep_ok', shape(10, 408)) == 1 and both(libs, 'cffm_sweep_ok', shape(10, 412)) == 0
+
+
 def test_refusals_come_before_any_launch(libs):
     sh = shape(6, 8)
     bad_shape = hip.Shape(M=10, F=1, K=8, D=8, act=0, linear_att=1, inner_conv=1, outer_conv=1, loss=0, lamda_att=1.0, beta_outer=1.0, lr=0.05)
