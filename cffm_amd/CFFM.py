@@ -700,6 +700,21 @@ class CFFM(object):
         at = torch.searchsorted(cs, inv[N:]).clamp(max=N - 1)
         return torch.where(cs[at] == inv[N:], order[at], torch.full_like(at, N))
 
+    @staticmethod
+    def _draw_lists(rng, at, U, m):
+        """The sampled protocol's draw, shared by evaluate_ranking_tuples and train_ranking: for every row r a list of m + 1 indices
+        into a distinct set of U tuples - its target at[r] and m distinct others (one permutation of the set without the target per
+        row) - with the target at a position drawn afterwards, for all rows at once.  Returns (lists int64 [P, m + 1], place [P])."""
+        P = int(at.shape[0])
+        lists = np.empty((P, m + 1), dtype=np.int64)                   # indices into the distinct set
+        for r in range(P):
+            neg = rng.permutation(U - 1)[:m]
+            lists[r, 1:] = neg + (neg >= at[r])                        # the set without the target
+        place = rng.randint(0, m + 1, size=P)
+        lists[:, 0] = lists[np.arange(P), place]
+        lists[np.arange(P), place] = at
+        return lists, place
+
     def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand'):
         """(HR@k, NDCG@k) over the rows of `data` with a positive label, the target being the row's own tuple at `fields`.
         negatives=None: one shared list - by default the distinct tuples at `fields` over the train split and `data`, sorted
@@ -741,15 +756,7 @@ class CFFM(object):
             m = int(negatives)
             if m < 1 or m >= U:
                 raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
-            rng = np.random.RandomState(seed)
-            at = tpos.cpu().numpy()
-            lists = np.empty((P, m + 1), dtype=np.int64)               # indices into the distinct set
-            for r in range(P):
-                neg = rng.permutation(U - 1)[:m]
-                lists[r, 1:] = neg + (neg >= at[r])                    # the set without the target
-            place = rng.randint(0, m + 1, size=P)
-            lists[:, 0] = lists[np.arange(P), place]
-            lists[np.arange(P), place] = at
+            lists, place = self._draw_lists(np.random.RandomState(seed), tpos.cpu().numpy(), U, m)
             lists = torch.from_numpy(lists).to(eng.device)
             tpos, N = torch.from_numpy(place).to(eng.device), m + 1
         tpos = tpos.to(torch.int32)
@@ -773,6 +780,66 @@ class CFFM(object):
         if bad:
             raise ValueError('evaluate_ranking_tuples(): predictions contain NaN')
         return hits / rows, gains / rows
+
+    # ---- training on ranked lists ----------------------------------------------------------------------------
+    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0):
+        """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
+        its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
+        the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
+        'bpr' (mean softplus of negative minus positive score) or 'softmax' (cross entropy of the list) - HipEngine.train_step_lists,
+        lists_per_step lists at a time (default batch_size // (negatives + 1)), ragged last step.  Per epoch the positives are
+        permuted and the lists drawn with np.random.RandomState(seed + epoch).  Returns the per-epoch mean loss over the lists as a
+        list of floats (read from the device once per epoch) and logs it.  The --lamda regulariser of the pointwise step is not part
+        of the list step.  One GPU, replicated tables, Adagrad, and not loss_type='log_loss' (its forward leaves sigmoid(out), not
+        the score): each refused with a ValueError that names it."""
+        import torch
+        from . import hip
+        if self.optimizer_type != 'AdagradOptimizer':
+            raise ValueError('train_ranking(): the list step implements AdagradOptimizer, not --optimizer %s' % self.optimizer_type)
+        if self.loss_type == 'log_loss':
+            raise ValueError("train_ranking(): --loss_type log_loss leaves sigmoid(out) in the forward, not the score the list losses rank")
+        if loss not in hip.LIST_LOSS_IDS:
+            raise ValueError("train_ranking(): loss must be one of %s, not %r" % (sorted(hip.LIST_LOSS_IDS), loss))
+        if os.environ.get('CFFM_TABLES', 'replicated') == 'sharded' or self._sh is not None:
+            raise ValueError('train_ranking(): CFFM_TABLES=sharded is not implemented for the list step; it runs on replicated tables')
+        if self.engine is None:
+            self.build_graph()
+        if self.world > 1:
+            raise ValueError('train_ranking(): a process group of %d ranks is not implemented for the list step; it runs on one GPU'
+                             % self.world)
+        eng = self.engine
+        cols = self._tuple_fields(fields)
+        m, epochs = int(negatives), int(epochs)
+        ids, y, _ = self._device_split(data)
+        colt = torch.tensor(cols, dtype=torch.long, device=eng.device)
+        cand = torch.unique(ids[:, colt], dim=0).to(torch.int32)
+        ctx = ids[y.reshape(-1) > 0]
+        P, U = int(ctx.shape[0]), int(cand.shape[0])
+        if P == 0:
+            raise ValueError('train_ranking() needs at least one row with a positive label')
+        if m < 1 or m >= U:
+            raise ValueError('train_ranking(): negatives must be in [1, %d): the distinct tuples without the target' % U)
+        per = int(self.batch_size // (m + 1) if lists_per_step is None else lists_per_step)
+        if per < 1:
+            raise ValueError('train_ranking(): lists_per_step must be >= 1 (batch_size %d holds no list of %d)' % (self.batch_size, m + 1))
+        at = self._tuple_positions(cand, ctx[:, colt].to(torch.int32)).cpu().numpy()
+        means = []
+        for epoch in range(epochs):
+            t1 = time()
+            rng = np.random.RandomState(seed + epoch)
+            perm = rng.permutation(P)
+            lists, place = self._draw_lists(rng, at[perm], U, m)
+            rows = ctx[torch.from_numpy(perm).to(eng.device)]
+            tuples = cand[torch.from_numpy(lists).to(eng.device)]                  # [P, m + 1, nf]
+            target = torch.from_numpy(place.astype(np.int32)).to(eng.device)
+            total = torch.zeros(1, dtype=torch.float64, device=eng.device)         # sum over the lists, read once per epoch
+            for r0 in range(0, P, per):
+                r1 = min(P, r0 + per)
+                step_loss = eng.train_step_lists(rows[r0:r1], cols, tuples[r0:r1].contiguous(), target[r0:r1], loss)
+                total += step_loss.double() * (r1 - r0)
+            means.append(float(total.cpu()[0]) / P)
+            self._info('Ranking epoch %d [%.1f s] %s loss over %d lists of %d: %.6f' % (epoch + 1, time() - t1, loss, P, m + 1, means[-1]))
+        return means
 
     # ---- host-side helpers with the reference's list semantics (CFFM.py:556-635) -------------------------
     def shuffle_in_unison_scary(self, x, y):

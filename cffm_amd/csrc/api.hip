@@ -213,7 +213,8 @@ static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, flo
     }
     bool inner_done = false;
     const bool wide = wide_rows(s, o.rows);          // the forward did not materialise Ei / Eo: rows come from the tables (RowSrc)
-    if (bwd_top_ok(s, B) && s->loss != CFFM_LOSS_SQUARE_L2) {
+    // a caller's dL/dout (o.dout_in) always takes the stage route below: bwd_top / conv01_bwd form dL/dout from (out, y, L) themselves
+    if (!o.dout_in && bwd_top_ok(s, B) && s->loss != CFFM_LOSS_SQUARE_L2) {
         // head + top two conv layers + inner branch: one launch
         int next = 0;
         if ((rc = cffm_bwd_top_impl(c, y, B_global, o, stream, &next))) return rc;
@@ -251,6 +252,19 @@ extern "C" int cffm_backward(const cffm_shape_t* s, const float* theta, const fl
     if (rc || B <= 0) return rc;
     const StepCtx c(s, B, theta, ws);
     return backward_impl(c, y, B_global, grad, (hipStream_t)stream);
+}
+
+// Backward from the caller's dL/dout (include/cffm_hip.h): what a loss that couples the examples of a batch, or one written outside
+// the library, needs.  The forward was cffm_forward (rows materialised); s->loss is accepted and not used.
+extern "C" int cffm_backward_dout(const cffm_shape_t* s, const float* theta, const float* dout, int32_t B, void* ws, float* grad,
+                                  void* stream) {
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    if (!theta || !dout || !ws || !grad) return CFFM_ERR_BAD_SHAPE;
+    const StepCtx c(s, B, theta, ws);
+    BwdOpts bo;
+    bo.dout_in = dout;
+    return backward_impl(c, nullptr, (int64_t)B, grad, (hipStream_t)stream, bo);
 }
 
 // this rank's loss-term sum (ws.scalars[0]) -> grad[theta.n], so that ONE all-reduce carries gradients and loss

@@ -38,6 +38,18 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadBwdArgs a) {
     head_bwd_end(a, blockIdx.x, st);
 }
 
+// The same backward from a dL/dout the caller hands in (cffm_backward_dout): no loss is formed, so neither scalars[3], sqerr, out nor y
+// is read, and nothing is normalised - every gradient is linear in dout[b].
+__global__ __launch_bounds__(256) void head_bwd_dout_kernel(HeadBwdArgs a, const float* __restrict__ dout_in) {
+    __shared__ float dh1s[CFFM_HEAD_UNITS];
+    __shared__ float dt1s[1024];
+    HeadBwdState st;
+    head_bwd_begin(a, blockIdx.x, st);
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x)
+        head_bwd_example(a, blockIdx.x, st, b, dout_in[b], dh1s, dt1s);
+    head_bwd_end(a, blockIdx.x, st);
+}
+
 HeadArgs StepCtx::head_args(const float* y, bool s0_ready) const {
     HeadArgs a{};
     a.g = g; a.B = B;
@@ -116,7 +128,8 @@ int cffm_head_bwd_impl(const StepCtx& c, const float* y, int64_t B_global, const
     int rc = check_lds(c.s);
     if (rc) return rc;
     const HeadBwdArgs a = c.head_bwd_args(y, B_global, o);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(small_slabs(c.B)), dim3(256), 0, stream, a);
+    if (o.dout_in) hipLaunchKernelGGL(head_bwd_dout_kernel, dim3(small_slabs(c.B)), dim3(256), 0, stream, a, o.dout_in);
+    else hipLaunchKernelGGL(head_bwd_kernel, dim3(small_slabs(c.B)), dim3(256), 0, stream, a);
     CFFM_CHECK_LAUNCH();
     return 0;
 }

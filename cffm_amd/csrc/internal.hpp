@@ -75,6 +75,8 @@ struct BwdOpts {
     bool unscaled = false;               // data-parallel: dL/dout without the 1/L of the RMSE-style loss
     bool skip_reduce = false;            // the caller reduces the slabs together with the table update
     const int32_t* rank_ids = nullptr;   // non-NULL: the fused top also places the sort keys the forward left out
+    const float* dout_in = nullptr;      // non-NULL: device [B], the caller's dL/dout used as given (cffm_backward_dout): the stage route
+                                         // at every shape and B, head_bwd_dout_kernel in place of head_bwd_kernel; y is not read
     RowTables rows;
 };
 struct ConvBwdOpts {

@@ -62,6 +62,9 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_predict);
     CFFM_BIND(cffm_forward);
     CFFM_BIND(cffm_backward);
+    CFFM_BIND(cffm_backward_dout);
+    CFFM_BIND(cffm_list_loss_scratch_bytes);
+    CFFM_BIND(cffm_list_loss);
     CFFM_BIND(cffm_dp_runs_ok);
     CFFM_BIND(cffm_dp_local);
     CFFM_BIND(cffm_dp_dense_floats);

@@ -712,6 +712,99 @@ class HipEngine(object):
                                          int(B if B_global is None else B_global), _ptr(buf), _ptr(self.grad),
                                          self._stream()))
 
+    # ---- training on ranked lists: backward from a given dL/dout, the list losses, the list step -------------
+    def backward_dout(self, dout, B):
+        """Backward from the caller's dL/dout (cffm_backward_dout): dout fp32 [B] on the device, used as given (no 1/B, no loss).
+        The forward was forward(ids, y or None); the gradients are read as after backward(): export_grad(), row_grads(B)."""
+        B = int(B)
+        dout = dout.reshape(-1)
+        if dout.dtype != torch.float32 or not dout.is_contiguous():
+            dout = dout.to(torch.float32).contiguous()
+        if int(dout.numel()) != B:
+            raise ValueError('backward_dout: dout must hold one value per example (%d, not %d)' % (B, int(dout.numel())))
+        buf, _ = self.workspace(B)
+        hip.check(self.lib.cffm_backward_dout(self._s, _ptr(self.theta), _ptr(dout), B, _ptr(buf), _ptr(self.grad), self._stream()))
+
+    @staticmethod
+    def _list_kind(kind):
+        if kind not in hip.LIST_LOSS_IDS:
+            raise ValueError("list loss must be one of %s, not %r" % (sorted(hip.LIST_LOSS_IDS), kind))
+        return hip.LIST_LOSS_IDS[kind]
+
+    def list_loss(self, scores, target, G, Lg, kind):
+        """cffm_list_loss over scores fp32 [G * Lg] (list g = rows g * Lg ..) with target int32 [G] the positives' positions, kind
+        'bpr' or 'softmax': (loss [1], dout [G * Lg], terms [G]) on the device, dout = d loss / d scores.  Nothing synchronises."""
+        kind, G, Lg = self._list_kind(kind), int(G), int(Lg)
+        scores, target = scores.reshape(-1), self._ids(target.reshape(-1))
+        if scores.dtype != torch.float32 or not scores.is_contiguous():
+            scores = scores.to(torch.float32).contiguous()
+        if int(scores.numel()) != G * Lg or int(target.numel()) != G:
+            raise ValueError('list_loss: scores must hold G * Lg = %d values and target G = %d' % (G * Lg, G))
+        dev = self.device
+        dout = torch.empty(G * Lg, dtype=torch.float32, device=dev)
+        terms = torch.empty(G, dtype=torch.float32, device=dev)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        hip.check(self.lib.cffm_list_loss(kind, _ptr(scores), G, Lg, _ptr(target), _ptr(dout), _ptr(terms), _ptr(loss),
+                                          _ptr(self._list_scratch(G)), self._stream()))
+        return loss, dout, terms
+
+    def _list_scratch(self, G):
+        nbytes = int(self.lib.cffm_list_loss_scratch_bytes(int(G)))
+        scratch = self._ws.get('list_loss')
+        if scratch is None or int(scratch.numel()) < nbytes:
+            scratch = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
+            self._ws['list_loss'] = scratch
+        return scratch
+
+    def train_step_lists(self, ctx, fields, cand, target, kind):
+        """One Adagrad step on G ranked lists: ctx int32 [G, F] the contexts, cand int32 [G, Lg, nf] every list's candidate tuples
+        for the columns `fields`, target int32 [G] the position of each list's positive, kind 'bpr' or 'softmax'.  The id rows
+        (cffm_expand_candidates_ex), the forward without labels, the list loss on ws.out, the backward from its dL/dout
+        (cffm_backward_dout: the stage launches), then the dense and the sparse Adagrad update.  Returns the loss as a device
+        scalar (no host sync).  Adagrad only, and not loss_type='log_loss', whose forward leaves sigmoid(out) and not the score."""
+        if self.cfg.optimizer != 'AdagradOptimizer':
+            raise ValueError('train_step_lists: the list step implements AdagradOptimizer, not %s' % self.cfg.optimizer)
+        if self.cfg.loss_type == 'log_loss':
+            raise ValueError("train_step_lists: loss_type 'log_loss' leaves sigmoid(out) in the forward, not the score the list losses rank")
+        kind_id = self._list_kind(kind)
+        F = int(self.cfg.F)
+        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        nf = len(fields)
+        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
+            raise ValueError('train_step_lists: needs 1 to %d distinct fields of [0, %d)' % (F, F))
+        if cand.dim() != 3:
+            raise ValueError('train_step_lists: candidates must be [G, Lg, %d]' % nf)
+        ctx, cand, G, Lg, stride = self._cand_lists(ctx, cand, nf, 'train_step_lists')
+        target = self._ids(target.reshape(-1))
+        if Lg < 2 or int(target.numel()) != G:
+            raise ValueError('train_step_lists: needs lists of at least 2 candidates and one target per list')
+        B = G * Lg
+        if B == 0:
+            return self.loss_buf
+        key = ('list_ids', B)
+        ids = self._ws.get(key)
+        if ids is None:
+            ids = torch.empty((B, F), dtype=torch.int32, device=self.device)
+            self._ws[key] = ids
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        hip.check(self.lib.cffm_expand_candidates_ex(self._s, _ptr(ctx), G, C.addressof(host_fields), nf, _ptr(cand), stride, Lg,
+                                                     0, B, _ptr(ids), self._stream()))
+        self.forward(ids, None)
+        buf, wl = self.workspace(B)
+        key = ('list_out', G, Lg)
+        out = self._ws.get(key)
+        if out is None:
+            out = (torch.empty(B, dtype=torch.float32, device=self.device), torch.empty(G, dtype=torch.float32, device=self.device))
+            self._ws[key] = out
+        dout, terms = out
+        hip.check(self.lib.cffm_list_loss(kind_id, _ptr(buf) + int(wl.out), G, Lg, _ptr(target), _ptr(dout), _ptr(terms),
+                                          _ptr(self.loss_buf), _ptr(self._list_scratch(G)), self._stream()))
+        self.backward_dout(dout, B)
+        self.apply_dense()
+        dEi, dEo, dfb = self.row_grads(B)
+        self.apply_sparse(ids, dEi, dEo, dfb, B)
+        return self.loss_buf
+
     # ---- data-parallel halves with late loss normalisation (cffm_amd/dist.py) ----------------------------------
     def backward_unscaled(self, ids, y, B, B_global, pack=True):
         """Backward with dL/dout = (out - y) / B_global.  Returns (grad_full [n+4] with this rank's loss-term sum at

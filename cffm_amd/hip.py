@@ -27,6 +27,7 @@ HEAD_UNITS = 32
 SWEEP_CHUNK = 64            # CFFM_SWEEP_CHUNK: candidates of one (context, chunk) unit of cffm_score_sweep
 SWEEP_MAX_NF = 4            # CFFM_SWEEP_MAX_NF: the most fields a tuple of cffm_score_sweep_tuples may replace together
 LOSS_IDS = {'square_loss': 0, 'mse': 1, 'mae': 2, 'log_loss': 3, 'hybrid': 5}
+LIST_LOSS_IDS = {'bpr': 0, 'softmax': 1}            # CFFM_LIST_BPR, CFFM_LIST_SOFTMAX
 OPT_IDS = {'AdagradOptimizer': 0, 'GradientDescentOptimizer': 1, 'MomentumOptimizer': 2, 'AdamOptimizer': 3}
 
 
@@ -110,6 +111,9 @@ PROTOTYPES = {
     'cffm_predict': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, _P, _P, _P]),
     'cffm_forward': (C.c_int, [_SH, _TB, _P, _P, _P, C.c_int32, _P, _P]),
     'cffm_backward': (C.c_int, [_SH, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
+    'cffm_backward_dout': (C.c_int, [_SH, _P, _P, C.c_int32, _P, _P, _P]),
+    'cffm_list_loss_scratch_bytes': (C.c_int64, [C.c_int32]),
+    'cffm_list_loss': (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     'cffm_backward_unscaled': (C.c_int, [_SH, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     'cffm_dp_apply': (C.c_int, [_SH, _TB, _TB, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P]),
     'cffm_dp_apply_opt': (C.c_int, [_SH, _TB, _TB, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P]),

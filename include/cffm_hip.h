@@ -510,6 +510,39 @@ typedef struct cffm_sweep_tuples_block {
 } cffm_sweep_tuples_block_t;
 int cffm_sweep_tuples_block_layout(const cffm_shape_t *s, int32_t nf, cffm_sweep_tuples_block_t *out);
 
+/* ---- training on ranked lists: backward from a given dL/dout, and two list losses -------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes.
+ *
+ * cffm_backward_dout: the backward half from the CALLER's dL/dout.  The forward was cffm_forward (rows materialised in ws.Ei /
+ * ws.Eo / ws.fb; y may have been NULL).  dout: device float [B], used as given: no 1/B, no 1/L, no loss id, and y is not read - so
+ * a loss that couples the examples of a batch (the list losses below), or one written in torch on `out`, can be trained.  Leaves
+ * what cffm_backward leaves: grad [theta.n], ws.dout (= dout, bit for bit), ws.dt1, ws.dC[l], ws.dEi, ws.dEo, ws.dfb.  Every shape
+ * and B takes the stage launches (head, conv layers from the top down, inner branch, slab reduction); the fused backward launches
+ * form dL/dout from (out, y, loss) themselves and are never taken.  Any valid s->loss is accepted and not used.
+ * Refusals, before any launch: the shape check first (CFFM_ERR_BAD_SHAPE); B <= 0 returns 0 as cffm_backward does;
+ * CFFM_ERR_BAD_SHAPE for a NULL theta, dout, ws or grad; CFFM_ERR_UNSUPPORTED for a shape a CU's LDS cannot hold, as cffm_backward. */
+int cffm_backward_dout(const cffm_shape_t *s, const float *theta, const float *dout, int32_t B, void *ws, float *grad,
+                       void *stream);
+
+/* cffm_list_loss: scores and dout are [G][Lg] contiguous device floats, list g being rows g * Lg .. g * Lg + Lg - 1 in the order
+ * cffm_expand_candidates_ex writes them; target[g] (device int32) is the position t of list g's positive.  With m = Lg - 1:
+ *   CFFM_LIST_BPR      terms[g] = (1/m) sum_{n != t} softplus(s_n - s_t)
+ *                      dout[n] = sigmoid(s_n - s_t) / (G m) for n != t,  dout[t] = -sum_{n != t} dout[n]
+ *   CFFM_LIST_SOFTMAX  terms[g] = log sum_n exp(s_n - max) + max - s_t
+ *                      dout[n] = (p_n - [n = t]) / G,  p = softmax(s)
+ *   loss[0] = (1/G) sum_g terms[g]
+ * dout is the gradient of loss[0] with respect to the scores: what cffm_backward_dout takes.  Every exponential has a non-positive
+ * argument, so scores of any finite size stay finite.  A NaN score makes its list's term and its whole dout row NaN, and the loss
+ * NaN.  A target[g] outside [0, Lg) gives terms[g] = 0 and a zero dout row; nothing is read out of range.  The sums run in a fixed
+ * order (one wavefront per list, then two stages in list order): the same bits on every run, whatever scratch held.
+ * Writes exactly G * Lg floats of dout, G of terms, one of loss.  scratch: cffm_list_loss_scratch_bytes(G) bytes (-1 for G < 0).
+ * CFFM_ERR_BAD_SHAPE, before any launch, for: an unknown kind; G < 0; Lg < 2; G * Lg >= 2^31; a NULL pointer that would be read or
+ * written (scores, target, dout, terms, loss, scratch).  G == 0 returns 0 without a launch. */
+enum { CFFM_LIST_BPR = 0, CFFM_LIST_SOFTMAX = 1 };
+int64_t cffm_list_loss_scratch_bytes(int32_t G);
+int cffm_list_loss(int32_t kind, const float *scores, int32_t G, int32_t Lg, const int32_t *target, float *dout, float *terms,
+                   float *loss, void *scratch, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
