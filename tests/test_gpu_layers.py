@@ -27,7 +27,7 @@ from oracle import layer_check as lc  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-FWD_ROWS, FWD_TAPS, FWD_TILE, FWD_DIRECT, WGRAD_TAPS, WGRAD_DIRECT0, DGRAD_TAPS = 2, 3, 4, 6, 2, 5, 1      # include/cffm_hip.h
+FWD_ROWS, FWD_TAPS, FWD_TILE, FWD_DIRECT, WGRAD_TAPS, WGRAD_DIRECT0, DGRAD_TAPS, DGRAD_DIRECT = 2, 3, 4, 6, 2, 5, 1, 3   # include/cffm_hip.h
 
 CASES = {
     # narrow filters (Pp <= 64): tap-split kernels with 1 and 2 row groups, the rows kernel (>= 32768 rows at layer 1)
@@ -88,6 +88,49 @@ CASES = {
     'f34-d32-b3-selu': dict(F=34, K=8, D=32, act='selu', B=3, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
     'f40-d16-b2-elu': dict(F=40, K=8, D=16, act='elu', B=2, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
     'f64-d4-b3-relu': dict(F=64, K=8, D=4, act='relu', B=3, want=[('fwd', FWD_DIRECT, 8, 1, 0), ('wgrad', WGRAD_DIRECT0, 8, 0, 0)]),
+    # The instances of the recorded dispatch grid that only a row count of 16384 and more on the layer reaches (the coverage ledger,
+    # tests/test_shape_domain.py), at D <= 32.  'want' here is (layer, role, family, NT, RM, HALVES, b3, paired), the ledger's record.
+    # tests/test_layer_cases.py holds the rows per layer stated below, without a GPU.
+    # direct layer 0 on 128-row tiles (>= 32768 rows): 513 x 64 = 32832 rows, the last 128-row tile is half full.  NT = 6, and NT = 8
+    # (whose layers >= 1 run wgrad3: the fp32-loop twin)
+    'f12-d16-b513-gelu': dict(F=12, K=8, D=16, act='gelu', B=513,
+                              want=[(0, 'fwd', FWD_DIRECT, 6, 2, 0, 0, 0), (0, 'dgrad', DGRAD_DIRECT, 8, 2, 0, 0, 0)]),
+    'f16-d16-b513-relu': dict(F=16, K=8, D=16, act='relu', B=513,
+                              want=[(0, 'fwd', FWD_DIRECT, 8, 2, 0, 0, 0), (0, 'dgrad', DGRAD_DIRECT, 8, 2, 0, 0, 0)]),
+    # conv_fwd_rows on layer 0 at NT = 1 (32832 rows), and the tap-split layer 0 with two row groups at NT = 4 (65 x 256 = 16640 rows)
+    'f2-d16-b513-elu': dict(F=2, K=8, D=16, act='elu', B=513, want=[(0, 'fwd', FWD_ROWS, 1, 1, 0, 0, 0)]),
+    'f11-d32-b65-selu': dict(F=11, K=8, D=32, act='selu', B=65, want=[(0, 'fwd', FWD_TAPS, 4, 2, 0, 0, 0)]),
+    # layer 1 of D = 32 (64 rows per example) at 16384 .. 32767 rows: two row groups of the tap-split forward and input gradient,
+    # paired (B = 256: 16384 rows) and unpaired (B = 509: 32576 rows); at B = 513 (32832 rows) the forward is conv_fwd_rows
+    'f7-d32-b256-relu': dict(F=7, K=8, D=32, act='relu', B=256,
+                             want=[(1, 'fwd', FWD_TAPS, 2, 2, 0, 0, 1), (1, 'dgrad', DGRAD_TAPS, 2, 2, 1, 0, 1)]),
+    'f7-d32-b509-gelu': dict(F=7, K=8, D=32, act='gelu', B=509,
+                             want=[(1, 'fwd', FWD_TAPS, 2, 2, 0, 0, 0), (1, 'dgrad', DGRAD_TAPS, 2, 2, 1, 0, 0)]),
+    'f7-d32-b513-elu': dict(F=7, K=8, D=32, act='elu', B=513, want=[(1, 'fwd', FWD_ROWS, 2, 1, 0, 0, 0)]),
+    # NT = 4 on a layer >= 1, unpaired: one row group with the HALVES = 2 weight gradient (D = 16: 8144 rows on layer 1), two row
+    # groups (D = 32: 32576 rows), conv_fwd_rows (32832 rows)
+    'f11-d16-b509-relu': dict(F=11, K=8, D=16, act='relu', B=509,
+                              want=[(1, 'fwd', FWD_TAPS, 4, 1, 0, 0, 0), (1, 'dgrad', DGRAD_TAPS, 4, 1, 1, 0, 0),
+                                    (1, 'wgrad', WGRAD_TAPS, 4, 0, 2, 0, 0)]),
+    'f11-d32-b509-selu': dict(F=11, K=8, D=32, act='selu', B=509,
+                              want=[(1, 'fwd', FWD_TAPS, 4, 2, 0, 0, 0), (1, 'dgrad', DGRAD_TAPS, 4, 2, 1, 0, 0)]),
+    'f11-d32-b513-gelu': dict(F=11, K=8, D=32, act='gelu', B=513, want=[(1, 'fwd', FWD_ROWS, 4, 1, 0, 0, 0)]),
+    # two row groups, unpaired, at NT = 1 and at NT = 3: the frappe shape (F = 10, D = 32, selu) in the batch range 410 .. 511, where
+    # the step has left the fused forward (B F > 4096) and runs one launch per stage
+    'f2-d32-b509-elu': dict(F=2, K=8, D=32, act='elu', B=509, want=[(1, 'fwd', FWD_TAPS, 1, 2, 0, 0, 0)]),
+    'f10-d32-b509-selu': dict(F=10, K=8, D=32, act='selu', B=509, want=[(1, 'fwd', FWD_TAPS, 3, 2, 0, 0, 0)]),
+    # Ragged ends of the two-row-group and the 64-row-block kernels (S^2 >= 32 makes the 16-row tile count of a layer even, so none
+    # of the cases above has them, and no other case of this file has a layer >= 2 with 16384 rows):
+    # B = 1025: layer 2 has 16400 rows = 1025 tiles of 16, so the last workgroup of the RM = 2 forward / input gradient (paired) holds
+    # one tile; layer 3 has 4100 rows, a 16-row tile with 4 rows
+    'f7-d32-b1025-selu': dict(F=7, K=8, D=32, act='selu', B=1025,
+                              want=[(2, 'fwd', FWD_TAPS, 2, 2, 0, 0, 1), (2, 'dgrad', DGRAD_TAPS, 2, 2, 1, 0, 1),
+                                    (3, 'fwd', FWD_TAPS, 2, 1, 0, 0, 1)]),
+    # B = 2049: layer 2 has 32784 rows on conv_fwd_rows, 16 of them in the last 64-row block, and an odd tile count (2049) on the
+    # unpaired RM = 2 input gradient; layer 3 has 8196 rows
+    'f7-d32-b2049-relu': dict(F=7, K=8, D=32, act='relu', B=2049,
+                              want=[(2, 'fwd', FWD_ROWS, 2, 1, 0, 0, 0), (2, 'dgrad', DGRAD_TAPS, 2, 2, 1, 0, 0),
+                                    (3, 'fwd', FWD_TAPS, 2, 1, 0, 0, 0)]),
 }
 HEAVY = [k for k, v in CASES.items() if v.get('heavy')]
 WS_CAP = 4 << 30          # bytes of workspace a case of this file may ask for (the heavy case apart)
@@ -126,25 +169,45 @@ def b3_set(cfg, B):
     return out
 
 
+def want_entries(name):
+    """The 'want' of a case as (layer, role, (family, NT, RM, HALVES), (b3, paired) or None): a 5-tuple names layer 0, a 6-tuple starts
+    with the layer, an 8-tuple also ends with the b3 and paired of the coverage ledger's record."""
+    out = []
+    for w in CASES[name].get('want', ()):
+        assert len(w) in (5, 6, 8), '%s: want entry %s' % (name, (w,))
+        w = ((0,) + tuple(w)) if len(w) == 5 else tuple(w)
+        out.append((w[0], w[1], w[2:6], w[6:8] if len(w) == 8 else None))
+    return out
+
+
 def check_instances(name, cfg, B):
-    """The layer-0 instances the case names ('want') are what the library picks at this (shape, B), and the workspace stays below
-    WS_CAP: asked on the host, before anything is allocated."""
+    """The instances the case names ('want') are what the library picks at this (shape, B) on the layer they name, and the workspace
+    stays below WS_CAP: asked on the host, before anything is allocated."""
     from cffm_amd import hip
     shape = hip.make_shape(cfg)
     if not CASES[name].get('heavy'):
         nbytes = hip.ws_layout(shape, B).bytes
         assert nbytes < WS_CAP, '%s: workspace of %d bytes' % (name, nbytes)
-    ch = hip.conv_choice(shape, B, 0)
-    for role, family, NT, RM, HALVES in CASES[name].get('want', ()):
+    for layer, role, inst, extra in want_entries(name):
+        assert 0 <= layer < cfg.live_layers, '%s: no layer %d' % (name, layer)
+        ch = hip.conv_choice(shape, B, layer)
         k = getattr(ch, role)
-        assert (k.family, k.NT, k.RM, k.HALVES) == (family, NT, RM, HALVES), \
-            '%s: layer 0 %s now runs (family %d, NT %d, RM %d, HALVES %d), the case is there for %s' % (
-                name, role, k.family, k.NT, k.RM, k.HALVES, (family, NT, RM, HALVES))
+        assert (k.family, k.NT, k.RM, k.HALVES) == inst, \
+            '%s: layer %d %s now runs (family %d, NT %d, RM %d, HALVES %d), the case is there for %s' % (
+                name, layer, role, k.family, k.NT, k.RM, k.HALVES, inst)
+        if extra is not None:
+            assert (k.b3, ch.paired) == extra, '%s: layer %d %s now has (b3 %d, paired %d), the case is there for %s' % (
+                name, layer, role, k.b3, ch.paired, extra)
+
+
+def case_config(name):
+    c = CASES[name]
+    return CFFMConfig(M=c.get('M', 4000), F=c['F'], K=c['K'], D=c['D'], activation=c['act'], lamda_att=1.3)
 
 
 def make_layer_case(name, seed=0):
     c = CASES[name]
-    cfg = CFFMConfig(M=c.get('M', 4000), F=c['F'], K=c['K'], D=c['D'], activation=c['act'], lamda_att=1.3)
+    cfg = case_config(name)
     p32 = init_params(cfg, seed=seed, dtype=np.float32)
     rng = np.random.default_rng(seed + 7)
     p32['feature_bias'] = (rng.standard_normal(p32['feature_bias'].shape) * 0.3).astype(np.float32)
