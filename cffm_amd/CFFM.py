@@ -782,7 +782,7 @@ class CFFM(object):
         return hits / rows, gains / rows
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
-    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0):
+    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages'):
         """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
         its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
         the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
@@ -791,9 +791,15 @@ class CFFM(object):
         permuted and the lists drawn with np.random.RandomState(seed + epoch).  Returns the per-epoch mean loss over the lists as a
         list of floats (read from the device once per epoch) and logs it.  The --lamda regulariser of the pointwise step is not part
         of the list step.  One GPU, replicated tables, Adagrad, and not loss_type='log_loss' (its forward leaves sigmoid(out), not
-        the score): each refused with a ValueError that names it."""
+        the score): each refused with a ValueError that names it.
+        step: 'stages' (default) takes every step through HipEngine.train_step_lists, the stage launches; 'fused' through
+        train_step_lists_fused, the launches of the pointwise step, and raises a ValueError where a step's size is not served
+        (HipEngine.list_step_ok, the ragged last step included); 'auto' takes the fused step where it is served, step by step, and the
+        stage step elsewhere."""
         import torch
         from . import hip
+        if step not in ('stages', 'fused', 'auto'):
+            raise ValueError("train_ranking(): step must be 'stages', 'fused' or 'auto', not %r" % (step,))
         if self.optimizer_type != 'AdagradOptimizer':
             raise ValueError('train_ranking(): the list step implements AdagradOptimizer, not --optimizer %s' % self.optimizer_type)
         if self.loss_type == 'log_loss':
@@ -835,7 +841,9 @@ class CFFM(object):
             total = torch.zeros(1, dtype=torch.float64, device=eng.device)         # sum over the lists, read once per epoch
             for r0 in range(0, P, per):
                 r1 = min(P, r0 + per)
-                step_loss = eng.train_step_lists(rows[r0:r1], cols, tuples[r0:r1].contiguous(), target[r0:r1], loss)
+                fused = step == 'fused' or (step == 'auto' and eng.list_step_ok((r1 - r0) * (m + 1)))
+                run = eng.train_step_lists_fused if fused else eng.train_step_lists
+                step_loss = run(rows[r0:r1], cols, tuples[r0:r1].contiguous(), target[r0:r1], loss)
                 total += step_loss.double() * (r1 - r0)
             means.append(float(total.cpu()[0]) / P)
             self._info('Ranking epoch %d [%.1f s] %s loss over %d lists of %d: %.6f' % (epoch + 1, time() - t1, loss, P, m + 1, means[-1]))

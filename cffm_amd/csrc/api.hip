@@ -207,13 +207,15 @@ static int backward_impl(const StepCtx& c, const float* y, int64_t B_global, flo
     const int32_t B = c.B;
     int rc = cffm_route_check(c);        // as in forward_impl (also covers the inner-branch roles of bwd_top / conv_bwd_pair)
     if (rc) return rc;
+    if (o.dout_fused && (o.dout_in || !bwd_top_ok(s, B) || s->loss == CFFM_LOSS_SQUARE_L2)) return CFFM_ERR_UNSUPPORTED;   // no fused top there
     if (!s->inner_conv || !s->outer_conv || !s->linear_att) {   // slabs of a disabled branch must read as zeros
         hipError_t e = hipMemsetAsync(c.at(c.wl.gpart), 0, (size_t)c.wl.gpart_floats * 4, stream);
         if (e != hipSuccess) return (int)e;
     }
     bool inner_done = false;
     const bool wide = wide_rows(s, o.rows);          // the forward did not materialise Ei / Eo: rows come from the tables (RowSrc)
-    // a caller's dL/dout (o.dout_in) always takes the stage route below: bwd_top / conv01_bwd form dL/dout from (out, y, L) themselves
+    // a caller's dL/dout (o.dout_in) always takes the stage route below: bwd_top / conv01_bwd form dL/dout from (out, y, L) themselves.
+    // o.dout_fused is the caller's dL/dout on the fused route (the DOUT instances of bwd_top; nothing below it looks at the loss)
     if (!o.dout_in && bwd_top_ok(s, B) && s->loss != CFFM_LOSS_SQUARE_L2) {
         // head + top two conv layers + inner branch: one launch
         int next = 0;
@@ -264,6 +266,19 @@ extern "C" int cffm_backward_dout(const cffm_shape_t* s, const float* theta, con
     const StepCtx c(s, B, theta, ws);
     BwdOpts bo;
     bo.dout_in = dout;
+    return backward_impl(c, nullptr, (int64_t)B, grad, (hipStream_t)stream, bo);
+}
+
+// The same from the caller's dL/dout on the launches cffm_backward takes where the fused top runs (include/cffm_hip.h): bwd_top as its
+// DOUT instance, then conv01_bwd or the pair / stage launches below it, then the slab reduction.
+extern "C" int cffm_backward_dout_fused(const cffm_shape_t* s, const float* theta, const float* dout, int32_t B, void* ws, float* grad,
+                                        void* stream) {
+    int rc = check_shape(s);
+    if (rc || B <= 0) return rc;
+    if (!theta || !dout || !ws || !grad) return CFFM_ERR_BAD_SHAPE;
+    const StepCtx c(s, B, theta, ws);
+    BwdOpts bo;
+    bo.dout_fused = dout;
     return backward_impl(c, nullptr, (int64_t)B, grad, (hipStream_t)stream, bo);
 }
 
@@ -415,6 +430,60 @@ extern "C" int cffm_train_step(const cffm_shape_t* s, const cffm_tables_t* tab, 
     so.prepacked = true;                         // the gather left the packed keys in ws.sort_keys
     if ((rc = cffm_sort_keys_impl(c, ids, (int64_t)B * s->F, so, st))) return rc;
     return cffm_sparse_apply(c, tab, tab_acc, (int64_t)B * s->F, RowGrads::of_ws(c), LateScale::none(), st);
+}
+
+// Where the list step runs in the fused launches: the fused top of the backward, whose key role then places the update's sort keys
+// (bwd_top_ok means F <= 11 and B <= 256: within what that role takes, F <= RANK_MAXF and B * F <= 4096), and update_all (Adagrad, both
+// branches on: part of bwd_top_ok).  The forward is the single launch where cffm_fwd_all_ok and the stage launches elsewhere (D = 8 or
+// 16, and F = 11 at D = 32, whose layer-0 tiles pass the LDS of a CU).  That second combination - stage forward, fused top with the key role, update_all - is this entry point's own: cffm_train_step
+// at those shapes takes the folded Adagrad reduction, the sort and cffm_sparse_apply.  It is served because each of the three takes the
+// shape on its own terms (the key role asks for F <= RANK_MAXF and B * F <= 4096, update_all for the placed keys and the slabs), and
+// tests/test_gpu_list_step.py runs whole steps on it (f4-d8, and f11-d32 with the Pp = 64 top) next to the single-launch forward at f10-d32.  Not the
+// regularised loss (dense table updates, stage backward) and not the log loss (its forward leaves sigmoid(out), not the score a list
+// loss ranks).
+extern "C" int cffm_list_step_ok(const cffm_shape_t* s, int32_t B) {
+    if (check_shape(s) || B < 1) return 0;
+    return (bwd_top_ok(s, B) && s->optimizer == CFFM_OPT_ADAGRAD && s->loss != CFFM_LOSS_SQUARE_L2 && s->loss != CFFM_LOSS_LOG) ? 1 : 0;
+}
+
+// One Adagrad step on G ranked lists of Lg candidates in the launches of cffm_train_step at B = G * Lg (include/cffm_hip.h): id rows,
+// forward without labels, list loss on ws.out, backward from its dL/dout through the fused top, update.
+extern "C" int cffm_train_step_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
+                                     float* theta_acc, float* grad, const int32_t* ctx, int32_t G, const int32_t* fields, int32_t nf,
+                                     const int32_t* cand, int64_t cand_stride, int32_t Lg, const int32_t* target, int32_t kind,
+                                     int32_t* ids_out, float* dout, float* terms, void* ws, float* loss, void* scratch, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    int rc = check_shape(s);
+    if (rc || G <= 0) return rc;
+    if (Lg < 2 || (kind != CFFM_LIST_BPR && kind != CFFM_LIST_SOFTMAX)) return CFFM_ERR_BAD_SHAPE;
+    const int64_t B64 = (int64_t)G * Lg;
+    if (B64 > 0x7fffffff || !cffm_list_step_ok(s, (int32_t)B64)) return CFFM_ERR_UNSUPPORTED;
+    const int32_t B = (int32_t)B64;
+    if (!tab || !tab_acc || !theta || !theta_acc || !grad || !ctx || !fields || !cand || !target || !ids_out || !dout || !terms || !ws ||
+        !loss || !scratch)
+        return CFFM_ERR_BAD_SHAPE;
+    const StepCtx c(s, B, theta, ws);
+    if ((rc = cffm_route_check(c))) return rc;       // what the forward and the backward ask first: here ahead of the expansion
+    // the expansion checks fields / strides itself, before its launch, which is the first of the step
+    if ((rc = cffm_expand_candidates_ex(s, ctx, G, fields, nf, cand, cand_stride, Lg, 0, B, ids_out, stream))) return rc;
+    // The keys: in the single-launch forward or deferred to the fused top, as cffm_train_step decides (defer_rank - always deferred
+    // here, since bwd_top_ok holds); the stage forward places none, so the fused top does there too.
+    const bool fwd_all = cffm_fwd_all_ok(s, B), keys_in_fwd = fwd_all && !defer_rank(s, B);
+    if (fwd_all) {
+        rc = cffm_fwd_all_impl(c, tab, ids_out, nullptr, st, keys_in_fwd);
+    } else {
+        FwdOpts fo;
+        fo.fused_step = true;                        // the inner-branch kernel gathers the rows itself, as in cffm_train_step
+        rc = forward_impl(c, step_rows(tab, ids_out), nullptr, st, fo);
+    }
+    if (rc) return rc;
+    if ((rc = cffm_list_loss(kind, c.at<const float>(c.wl.out), G, Lg, target, dout, terms, loss, scratch, stream))) return rc;
+    BwdOpts bo;
+    bo.dout_fused = dout;
+    bo.skip_reduce = true;                           // cffm_update_all reduces
+    if (!keys_in_fwd) bo.rank_ids = ids_out;
+    if ((rc = backward_impl(c, nullptr, (int64_t)B, grad, st, bo))) return rc;
+    return cffm_update_all(c, tab, tab_acc, theta, theta_acc, grad, st);
 }
 
 extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_state1,

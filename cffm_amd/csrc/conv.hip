@@ -2927,7 +2927,13 @@ struct BwdTopArgs {
 };
 
 // (NT <= 3: three workgroups per CU - with 256 + 2 x 256 workgroups at the frappe shape that is what lets every role start at once)
-template <int NT, int ACT = -1>
+// DOUT (the fused list step, cffm_backward_dout_fused): dL/dout of example b is a.ib.dout[b], the caller's, used as given by both the
+// head role and the inner-branch role.  No loss is formed: neither y, out, sqerr nor scalars is read, neither scalars nor loss_out is
+// written, and `red` is not used.  Taking the loss sum out removes barriers only from straight-line code every thread of the workgroup
+// runs: the head role goes from the barrier that ends head_bwd_begin to the one head_bwd_example starts with (what the unscaled path,
+// whose head_bwd_loss has no barrier either, always did), the inner-branch role from its requests to the barrier at the top of its
+// example loop.
+template <int NT, int ACT = -1, bool DOUT = false>
 __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ float dh1s[CFFM_HEAD_UNITS];
@@ -2942,6 +2948,9 @@ __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopA
         // single pass: the launcher refuses B > n_inner (cffm_bwd_top_impl), so slab bid has example bid or none.  The loss sum runs
         // inside the body, behind the requests for the example's rows, out and y.  (The key placement is never in this role: the
         // launcher gives it workgroups of its own whenever there are keys to place.)
+        if constexpr (DOUT) {
+            inner_bwd_body<ACT, true>(a.ib, bid, a.n_inner, smem);      // a.ib.dout is set: nothing to sum (InnerNoLoss)
+        } else {
         inner_bwd_body<ACT, true>(a.ib, bid, a.n_inner, smem, [&]() __attribute__((always_inline)) {
             const float L = head_bwd_loss(a.hb, false, red);
             __syncthreads();
@@ -2949,6 +2958,7 @@ __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopA
             PHASE_MARKB(38, bid);
             return L;
         });
+        }
         PHASE_MARKB(39, bid);
 #ifdef CFFM_PHASE_TIMERS
         if (threadIdx.x == 0) cffm_wg_times[2 * blockIdx.x + 1] = wall_clock64();
@@ -2967,10 +2977,14 @@ __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopA
     HeadBwdState st;
     head_bwd_begin(a.hb, b, st);
     PHASE_MARKB(1, b);
+    if constexpr (DOUT) {
+        if (b < a.hb.B) head_bwd_example<ACT>(a.hb, b, st, b, a.ib.dout[b], dh1s, dt1s);
+    } else {
     const float L = head_bwd_loss(a.hb, b == 0, red);
     PHASE_MARKB(2, b);
     if (b < a.hb.B)
         head_bwd_example<ACT>(a.hb, b, st, b, head_dout(a.hb.loss, a.hb.out[b], a.hb.y[b], 1.f / (float)a.hb.Bg, L), dh1s, dt1s);
+    }
     PHASE_MARKB(3, b);
     head_bwd_end(a.hb, b, st);
     PHASE_MARKB(4, b);
@@ -4417,17 +4431,21 @@ int cffm_conv_fwd_impl(const StepCtx& c, int l, hipStream_t st, const RowSrc* rs
     }
 }
 
-template <int NT>
+template <int NT, bool DOUT = false>
 static int launch_bwd_top(const BwdTopArgs& a, size_t lds, hipStream_t st) {
     return with_readme_act<NT>(a.hb.g.act, [&](auto act) {
         constexpr int ACT = decltype(act)::value;
-        int rc = set_lds(bwd_top_kernel<NT, ACT>, lds);
+        int rc = set_lds(bwd_top_kernel<NT, ACT, DOUT>, lds);
         if (rc) return rc;
-        hipLaunchKernelGGL((bwd_top_kernel<NT, ACT>), dim3(a.n_inner + a.n_keys + 256), dim3(256), lds, st, a);
+        hipLaunchKernelGGL((bwd_top_kernel<NT, ACT, DOUT>), dim3(a.n_inner + a.n_keys + 256), dim3(256), lds, st, a);
         CFFM_CHECK_LAUNCH();
         return 0;
     });
 }
+
+// the DOUT instances are first named at the end of this file (launch_bwd_top_dout), so that they are generated after every other kernel
+// of the translation unit and the kernels of the pointwise step stay where they were in the code object
+static int launch_bwd_top_dout(const BwdTopArgs& a, int nt, size_t lds, hipStream_t st);
 
 int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const BwdOpts& o, hipStream_t st, int* next_layer) {
     const cffm_shape_t* s = c.s;
@@ -4449,6 +4467,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
     if (B > a.n_inner || B > 256) return CFFM_ERR_UNSUPPORTED;   // one example per workgroup of either role (inner_bwd_body<ACT, true>)
     a.ib.dout = nullptr;                                     // recomputed from (out, y, L): no dependency on the head role
     a.ib.y = y; a.ib.invB = 1.f / (float)B_global;
+    if (o.dout_fused) a.ib.dout = o.dout_fused;              // the DOUT instances: both roles read the caller's dL/dout here, y is not read
     if (o.rank_ids != nullptr && s->F <= RANK_MAXF && (int64_t)B * s->F <= 4096) {
         a.rank_ids = o.rank_ids; a.n_rows = B * s->F;
         a.keys_sorted = c.at<unsigned long long>(c.wl.sort_vals);
@@ -4457,6 +4476,7 @@ int cffm_bwd_top_impl(const StepCtx& c, const float* y, int64_t B_global, const 
     size_t lds = (size_t)(WGT_SUB * g.Pp) * 4 + 16;
     if (inner_bwd_lds(g) > lds) lds = inner_bwd_lds(g);
     *next_layer = first - 1;
+    if (o.dout_fused) return launch_bwd_top_dout(a, g.Pp / 16, lds, st);
     return with_int<NT4>(g.Pp / 16, [&](auto nt) { return launch_bwd_top<CV(nt)>(a, lds, st); });
 }
 
@@ -4683,4 +4703,9 @@ int cffm_fwd_all_impl(const StepCtx& c, const cffm_tables_t* tab, const int32_t*
     fa.early_off = (pl.early_fits && ids != nullptr) ? pl.t_off : 0;
     fa.es_off = pl.es_off;
     return with_int<NT4>(PP / 16, [&](auto nt) { return launch_fwd_all<CV(nt)>(fa, lds, st); });
+}
+
+// ---- the fused top taking a given dL/dout: last in the file on purpose (see cffm_bwd_top_impl) ------------------------------------------
+static int launch_bwd_top_dout(const BwdTopArgs& a, int nt, size_t lds, hipStream_t st) {
+    return with_int<NT4>(nt, [&](auto n) { return launch_bwd_top<CV(n), true>(a, lds, st); });
 }

@@ -77,6 +77,9 @@ struct BwdOpts {
     const int32_t* rank_ids = nullptr;   // non-NULL: the fused top also places the sort keys the forward left out
     const float* dout_in = nullptr;      // non-NULL: device [B], the caller's dL/dout used as given (cffm_backward_dout): the stage route
                                          // at every shape and B, head_bwd_dout_kernel in place of head_bwd_kernel; y is not read
+    const float* dout_fused = nullptr;   // non-NULL: device [B], the caller's dL/dout used as given on the FUSED route (bwd_top_ok(s, B)
+                                         // and not the regularised loss, else refused): the launches cffm_backward takes there, the fused
+                                         // top as its DOUT instance (cffm_backward_dout_fused, cffm_train_step_lists); y is not read
     RowTables rows;
 };
 struct ConvBwdOpts {

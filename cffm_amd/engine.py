@@ -805,6 +805,72 @@ class HipEngine(object):
         self.apply_sparse(ids, dEi, dEo, dfb, B)
         return self.loss_buf
 
+    def list_step_ok(self, B):
+        """True where train_step_lists_fused serves B = G * Lg rows of this engine's shape (cffm_list_step_ok; host only)."""
+        return bool(self.lib.cffm_list_step_ok(self._s, int(B)))
+
+    def backward_dout_fused(self, dout, B):
+        """backward_dout on the launches backward() takes where its fused top runs (cffm_backward_dout_fused); raises where it does not."""
+        B = int(B)
+        dout = dout.reshape(-1)
+        if dout.dtype != torch.float32 or not dout.is_contiguous():
+            dout = dout.to(torch.float32).contiguous()
+        if int(dout.numel()) != B:
+            raise ValueError('backward_dout_fused: dout must hold one value per example (%d, not %d)' % (B, int(dout.numel())))
+        buf, _ = self.workspace(B)
+        hip.check(self.lib.cffm_backward_dout_fused(self._s, _ptr(self.theta), _ptr(dout), B, _ptr(buf), _ptr(self.grad), self._stream()))
+
+    def train_step_lists_fused(self, ctx, fields, cand, target, kind):
+        """train_step_lists through the fused top of the backward (cffm_train_step_lists, one library call): the id rows, the forward
+        without labels, the list loss on ws.out, the backward from its dL/dout with the fused top placing the update's sort keys, and
+        update_all.  Where the single-launch forward runs (cffm_fwd_all_ok: the frappe shape among them) these are the launches of
+        train_step plus three, seven at the frappe shape; at D = 8 or 16, and at F = 11 with D = 32, the forward is the stage launches,
+        a combination train_step itself does not run (it sorts and applies the rows separately there).  Same arguments,
+        checks, return value and buffers (('list_ids', B), ('list_out', G, Lg), loss_buf) as train_step_lists.  Served where
+        list_step_ok(G * Lg); elsewhere a ValueError names the shape and B, and nothing has been touched."""
+        who = 'train_step_lists_fused'
+        if self.cfg.optimizer != 'AdagradOptimizer':
+            raise ValueError('%s: the list step implements AdagradOptimizer, not %s' % (who, self.cfg.optimizer))
+        if self.cfg.loss_type == 'log_loss':
+            raise ValueError("%s: loss_type 'log_loss' leaves sigmoid(out) in the forward, not the score the list losses rank" % who)
+        kind_id = self._list_kind(kind)
+        F = int(self.cfg.F)
+        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        nf = len(fields)
+        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
+            raise ValueError('%s: needs 1 to %d distinct fields of [0, %d)' % (who, F, F))
+        if cand.dim() != 3:
+            raise ValueError('%s: candidates must be [G, Lg, %d]' % (who, nf))
+        ctx, cand, G, Lg, stride = self._cand_lists(ctx, cand, nf, who)
+        target = self._ids(target.reshape(-1))
+        if Lg < 2 or int(target.numel()) != G:
+            raise ValueError('%s: needs lists of at least 2 candidates and one target per list' % who)
+        B = G * Lg
+        if B == 0:
+            return self.loss_buf
+        if not self.list_step_ok(B):
+            raise ValueError('%s: the fused list step does not serve F=%d K=%d D=%d %s, lamda_bilinear=%g at B = %d x %d = %d rows '
+                             '(list_step_ok); train_step_lists does' % (who, F, self.cfg.K, self.cfg.D, self.cfg.activation,
+                                                                       self.cfg.lamda_bilinear, G, Lg, B))
+        key = ('list_ids', B)
+        ids = self._ws.get(key)
+        if ids is None:
+            ids = torch.empty((B, F), dtype=torch.int32, device=self.device)
+            self._ws[key] = ids
+        buf, _ = self.workspace(B)
+        key = ('list_out', G, Lg)
+        out = self._ws.get(key)
+        if out is None:
+            out = (torch.empty(B, dtype=torch.float32, device=self.device), torch.empty(G, dtype=torch.float32, device=self.device))
+            self._ws[key] = out
+        dout, terms = out
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        hip.check(self.lib.cffm_train_step_lists(self._s, self._t, self._ta, _ptr(self.theta), _ptr(self.theta_acc), _ptr(self.grad),
+                                                 _ptr(ctx), G, C.addressof(host_fields), nf, _ptr(cand), stride, Lg, _ptr(target),
+                                                 kind_id, _ptr(ids), _ptr(dout), _ptr(terms), _ptr(buf), _ptr(self.loss_buf),
+                                                 _ptr(self._list_scratch(G)), self._stream()))
+        return self.loss_buf
+
     # ---- data-parallel halves with late loss normalisation (cffm_amd/dist.py) ----------------------------------
     def backward_unscaled(self, ids, y, B, B_global, pack=True):
         """Backward with dL/dout = (out - y) / B_global.  Returns (grad_full [n+4] with this rank's loss-term sum at

@@ -543,6 +543,43 @@ int64_t cffm_list_loss_scratch_bytes(int32_t G);
 int cffm_list_loss(int32_t kind, const float *scores, int32_t G, int32_t Lg, const int32_t *target, float *dout, float *terms,
                    float *loss, void *scratch, void *stream);
 
+/* ---- the fused list step: train on ranked lists in the launches of the pointwise step ----------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel instance, default or refusal changes;
+ * cffm_backward_dout keeps the stage launches bit for bit.
+ *
+ * cffm_list_step_ok: 1 where cffm_train_step_lists is served at B = G * Lg rows, else 0 (also for a shape the shape check refuses or
+ * B < 1).  Host only, nothing is launched.  Served: the shapes whose backward runs the fused top, which also places the update's sort
+ * keys (both branches on, Pp <= 64 i.e. F <= 11, at least two live conv layers i.e. D >= 8, B <= 256), CFFM_OPT_ADAGRAD, and a loss
+ * that is neither CFFM_LOSS_SQUARE_L2 (lamda > 0) nor CFFM_LOSS_LOG (its forward leaves sigmoid(out)). */
+int cffm_list_step_ok(const cffm_shape_t *s, int32_t B);
+/* cffm_backward_dout_fused: the contract of cffm_backward_dout - after cffm_forward, dout [B] used as given, y not read, leaves what
+ * cffm_backward leaves (grad [theta.n], ws.dout = dout bit for bit, ws.dt1, ws.dC[l], ws.dEi, ws.dEo, ws.dfb) - on the launches
+ * cffm_backward takes at that (shape, B) where its fused top runs: the fused top with dL/dout read instead of formed (the same kernel
+ * body, a compile-time switch), then the one launch for the layers below it or the pair / stage launches, then the slab reduction.
+ * Neither ws.scalars nor a loss is written.  Refusals, before any launch: the shape check (CFFM_ERR_BAD_SHAPE); B <= 0 returns 0;
+ * CFFM_ERR_BAD_SHAPE for a NULL theta, dout, ws or grad; CFFM_ERR_UNSUPPORTED for a shape a CU's LDS cannot hold and wherever
+ * cffm_backward does not take the fused top: B > 256, Pp > 64, a disabled branch, fewer than two live conv layers, CFFM_LOSS_SQUARE_L2. */
+int cffm_backward_dout_fused(const cffm_shape_t *s, const float *theta, const float *dout, int32_t B, void *ws, float *grad,
+                             void *stream);
+/* cffm_train_step_lists: one Adagrad step on G ranked lists of Lg candidates each, B = G * Lg rows, in seven launches at the frappe shape:
+ *   1. cffm_expand_candidates_ex(s, ctx, G, fields, nf, cand, cand_stride, Lg, 0, B, ids_out): the id rows, ids_out int32 [B][F]
+ *   2. the forward of cffm_train_step on ids_out, without labels: ws.out holds the raw scores.  One launch where the pointwise step
+ *      has its single-launch forward (cffm_dp_runs_ok(s, B): D = 32 or 64 with the layer-0 tiles within a CU's LDS, the frappe shape
+ *      among them); the stage launches at the other served shapes (F = 11 at D = 32, D = 8, D = 16)
+ *   3. cffm_list_loss(kind, ws.out, G, Lg, target, dout, terms, loss, scratch)                         (2 launches)
+ *   4. the backward of cffm_train_step from dout (as cffm_backward_dout_fused, which also places the update's sort keys)
+ *   5. the fused update of cffm_train_step (slab reduction + dense Adagrad, sorted sparse table update)
+ * ctx, fields (HOST), cand, cand_stride as cffm_expand_candidates_ex takes them (N = Lg); target, kind, dout [B], terms [G], loss [1],
+ * scratch (cffm_list_loss_scratch_bytes(G) bytes) as cffm_list_loss; the rest as cffm_train_step.  ids_out, dout and terms are the
+ * caller's and hold the step's id rows, dL/dout and list terms afterwards; grad holds the dense gradients.
+ * Refusals, all with nothing launched, in this order: the shape check; G <= 0 returns 0; CFFM_ERR_BAD_SHAPE for Lg < 2 or an unknown
+ * kind; CFFM_ERR_UNSUPPORTED where cffm_list_step_ok(s, G * Lg) == 0; CFFM_ERR_BAD_SHAPE for a NULL pointer; then what
+ * cffm_expand_candidates_ex refuses (nf, fields, strides). */
+int cffm_train_step_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *tab_acc, float *theta,
+                          float *theta_acc, float *grad, const int32_t *ctx, int32_t G, const int32_t *fields, int32_t nf,
+                          const int32_t *cand, int64_t cand_stride, int32_t Lg, const int32_t *target, int32_t kind,
+                          int32_t *ids_out, float *dout, float *terms, void *ws, float *loss, void *scratch, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
