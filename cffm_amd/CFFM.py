@@ -715,7 +715,28 @@ class CFFM(object):
         lists[np.arange(P), place] = at
         return lists, place
 
-    def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand'):
+    @staticmethod
+    def _check_sampler(who, sampler, negatives):
+        if sampler not in ('host', 'device'):
+            raise ValueError("%s: sampler must be 'host' or 'device', not %r" % (who, sampler))
+        if sampler == 'device' and negatives is not None and int(negatives) > 1023:
+            raise ValueError("%s: sampler='device' draws lists of at most 1024: negatives must be <= 1023, not %d" % (who, int(negatives)))
+
+    @staticmethod
+    def _draw_lists_device(eng, seed, list0, at, U, m, cand):
+        """HipEngine.draw_lists for the lists list0 .. list0 + len(at) - 1, in as many calls as the 2^31 element bound of one call
+        asks for (a list is a function of its id, so the split does not show): (tuples int32 [G, m + 1, nf], target int32 [G])."""
+        import torch
+        G = int(at.shape[0])
+        per = max(1, ((1 << 31) - 1) // ((m + 1) * int(cand.shape[1])))
+        if G <= per:
+            tuples, _, target = eng.draw_lists(seed, list0, at, U, m, cand)
+            return tuples, target
+        parts = [eng.draw_lists(seed, list0 + g0, at[g0:g0 + per], U, m, cand) for g0 in range(0, G, per)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[2] for p in parts])
+
+    def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand',
+                                sampler='host'):
         """(HR@k, NDCG@k) over the rows of `data` with a positive label, the target being the row's own tuple at `fields`.
         negatives=None: one shared list - by default the distinct tuples at `fields` over the train split and `data`, sorted
         (torch.unique(dim=0) on the device); explicit candidates [N] / [N, nf] that lack a target raise ValueError.  negatives=m:
@@ -725,8 +746,12 @@ class CFFM(object):
         so a target fixed at position 0 would win every tie.  m >= the number of distinct tuples raises ValueError.  Under a process
         group every rank draws all lists from the same seed and then takes its contiguous share of the rows.  The sums stay on the
         device in float64 and are read once, as in evaluate_ranking.  sweep: as in recommend_tuples ('tuples': the tuple sweep for the
-        shared list and for the sampled lists alike)."""
+        shared list and for the sampled lists alike).
+        sampler: 'host' (default) is the draw above.  'device' draws the lists on the GPU (HipEngine.draw_lists(seed, 0, ...):
+        cffm_amd.spec.draw_lists is the specification, list r a function of (seed, r) alone) - other lists than 'host' draws, of the
+        same distribution, at most 1023 negatives; under a process group every rank draws its own share of the rows only."""
         import torch
+        self._check_sampler('evaluate_ranking_tuples()', sampler, negatives)
         eng = self._ranking_engine()
         cols = self._tuple_fields(fields)
         ids, y, _ = self._device_split(data)
@@ -751,25 +776,34 @@ class CFFM(object):
         if bool(missing.any()):
             raise ValueError('evaluate_ranking_tuples(): target %s at fields %s is not among the candidates'
                              % (tuple(int(v) for v in tgt[missing][0]), tuple(cols)))
-        N, lists = U, None
-        if negatives is not None:
-            m = int(negatives)
-            if m < 1 or m >= U:
-                raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
-            lists, place = self._draw_lists(np.random.RandomState(seed), tpos.cpu().numpy(), U, m)
-            lists = torch.from_numpy(lists).to(eng.device)
-            tpos, N = torch.from_numpy(place).to(eng.device), m + 1
-        tpos = tpos.to(torch.int32)
         r0, r1 = 0, P
         if self.world > 1:
             share = -(-P // self.world)
             r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
+        N, lists, drawn = U, None, None
+        if negatives is not None:
+            m = int(negatives)
+            if m < 1 or m >= U:
+                raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
+            N = m + 1
+            if sampler == 'device':                                            # this rank's rows only: list r is row r's
+                drawn, place = self._draw_lists_device(eng, seed, r0, tpos[r0:r1], U, m, cand)
+                tpos = torch.cat([tpos.new_zeros(r0), place.to(tpos.dtype), tpos.new_zeros(P - r1)])
+            else:
+                lists, place = self._draw_lists(np.random.RandomState(seed), tpos.cpu().numpy(), U, m)
+                lists = torch.from_numpy(lists).to(eng.device)
+                tpos = torch.from_numpy(place).to(eng.device)
+        tpos = tpos.to(torch.int32)
         sums = torch.zeros(4, dtype=torch.float64, device=eng.device)      # [hits, gains, rows, NaN flag], read once
         group = max(1, int(score_rows) // N)
-        score = self._tuple_scorer(eng, sweep, cols, N, lists is not None)
+        score = self._tuple_scorer(eng, sweep, cols, N, negatives is not None)
         for c0 in range(r0, r1, group):
             c1 = min(r1, c0 + group)
-            scores = score(ctx[c0:c1], cand if lists is None else cand[lists[c0:c1]])
+            if drawn is not None:
+                tuples = drawn[c0 - r0:c1 - r0]
+            else:
+                tuples = cand if lists is None else cand[lists[c0:c1]]
+            scores = score(ctx[c0:c1], tuples)
             rank = eng.rank_of(scores, tpos[c0:c1]).double()
             hit = rank < k
             sums[0] += hit.sum()
@@ -782,7 +816,7 @@ class CFFM(object):
         return hits / rows, gains / rows
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
-    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages'):
+    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host'):
         """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
         its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
         the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
@@ -795,9 +829,15 @@ class CFFM(object):
         step: 'stages' (default) takes every step through HipEngine.train_step_lists, the stage launches; 'fused' through
         train_step_lists_fused, the launches of the pointwise step, and raises a ValueError where a step's size is not served
         (HipEngine.list_step_ok, the ragged last step included); 'auto' takes the fused step where it is served, step by step, and the
-        stage step elsewhere."""
+        stage step elsewhere.
+        sampler: 'host' (default) is the draw above.  'device' keeps the epoch permutation (RandomState(seed + epoch).permutation,
+        the only thing that crosses the bus) and draws the epoch's lists on the GPU: list j of epoch e, the one of the j-th permuted
+        positive, is list e * P + j of HipEngine.draw_lists(seed, ...) (cffm_amd.spec.draw_lists is the specification), a function of
+        (seed, e * P + j) alone and so the same under every lists_per_step.  Other lists than 'host' draws, of the same
+        distribution; at most 1023 negatives."""
         import torch
         from . import hip
+        self._check_sampler('train_ranking()', sampler, negatives)
         if step not in ('stages', 'fused', 'auto'):
             raise ValueError("train_ranking(): step must be 'stages', 'fused' or 'auto', not %r" % (step,))
         if self.optimizer_type != 'AdagradOptimizer':
@@ -828,16 +868,22 @@ class CFFM(object):
         per = int(self.batch_size // (m + 1) if lists_per_step is None else lists_per_step)
         if per < 1:
             raise ValueError('train_ranking(): lists_per_step must be >= 1 (batch_size %d holds no list of %d)' % (self.batch_size, m + 1))
-        at = self._tuple_positions(cand, ctx[:, colt].to(torch.int32)).cpu().numpy()
+        at_dev = self._tuple_positions(cand, ctx[:, colt].to(torch.int32))
+        at = at_dev.cpu().numpy() if sampler == 'host' else None
         means = []
         for epoch in range(epochs):
             t1 = time()
             rng = np.random.RandomState(seed + epoch)
             perm = rng.permutation(P)
-            lists, place = self._draw_lists(rng, at[perm], U, m)
-            rows = ctx[torch.from_numpy(perm).to(eng.device)]
-            tuples = cand[torch.from_numpy(lists).to(eng.device)]                  # [P, m + 1, nf]
-            target = torch.from_numpy(place.astype(np.int32)).to(eng.device)
+            if sampler == 'device':
+                permt = torch.from_numpy(perm).to(eng.device)
+                rows = ctx[permt]
+                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, m, cand)
+            else:
+                lists, place = self._draw_lists(rng, at[perm], U, m)
+                rows = ctx[torch.from_numpy(perm).to(eng.device)]
+                tuples = cand[torch.from_numpy(lists).to(eng.device)]              # [P, m + 1, nf]
+                target = torch.from_numpy(place.astype(np.int32)).to(eng.device)
             total = torch.zeros(1, dtype=torch.float64, device=eng.device)         # sum over the lists, read once per epoch
             for r0 in range(0, P, per):
                 r1 = min(P, r0 + per)

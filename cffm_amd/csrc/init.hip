@@ -12,6 +12,7 @@
 // (width % 4 == 0), two 8-byte stores otherwise (the widths are even).  Grid-stride over the groups with the (row, group) pair
 // advanced incrementally, so the loop holds no 64-bit division; no LDS, 36 VGPRs (8 waves per SIMD), nothing but occupancy to hide the stores.
 #include "internal.hpp"
+#include "philox.hpp"
 
 #define INIT_THREADS 256
 #define INIT_MAX_BLOCKS 2048            // 256 CUs x 8 blocks: a memory-bound grid is capped there and strides the rest
@@ -26,18 +27,6 @@ struct InitArgs {
     uint64_t step_rows;                 // the grid stride (gridDim.x * INIT_THREADS groups) as rows + leftover groups
     uint32_t step_groups;
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t x[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
-}
 
 // two unit normals from two words: u1 in (0, 1], u2 in [0, 1), both multiples of 2^-24
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {

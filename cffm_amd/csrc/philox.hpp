@@ -1,0 +1,18 @@
+// Philox4x32-10, the counter-based generator of the table draw (init.hip) and of the list draw (draw.hip): ten rounds on a
+// 128-bit counter under a 64-bit key.  cffm_amd/spec.py philox4x32_10() is the numpy twin, with known-answer tests.
+#pragma once
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t x[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    x[0] = c0; x[1] = c1; x[2] = c2; x[3] = c3;
+}

@@ -805,6 +805,29 @@ class HipEngine(object):
         self.apply_sparse(ids, dEi, dEo, dfb, B)
         return self.loss_buf
 
+    def draw_lists(self, seed, list0, at, U, m, cand=None):
+        """cffm_draw_lists: G = len(at) ranked lists over U distinct tuples, list g (id list0 + g) a function of (seed, id) alone -
+        the positive at[g] (int32 [G] on the device), m distinct others, the positive at a drawn place; cffm_amd.spec.draw_lists
+        is the specification.  cand: int32 [U, nf] on the device, or None for the indices alone.  Returns (tuples int32
+        [G, m + 1, nf] = cand[lists] or None, lists int32 [G, m + 1], target int32 [G]) on the device.  Nothing synchronises."""
+        seed, list0, U, m = int(seed) & 0xffffffffffffffff, int(list0), int(U), int(m)
+        at = self._ids(at.reshape(-1))
+        G, nf = int(at.numel()), 0
+        if cand is not None:
+            if cand.dim() != 2 or int(cand.shape[0]) != U or int(cand.shape[1]) < 1:
+                raise ValueError('draw_lists: cand must be [U = %d, nf >= 1]' % U)
+            cand, nf = self._ids(cand), int(cand.shape[1])
+        if U < 2 or not 1 <= m <= min(U - 1, 1023):
+            raise ValueError('draw_lists: needs 1 <= m <= min(U - 1, 1023) (U = %d, m = %d)' % (U, m))
+        dev = self.device
+        lists = torch.empty((G, m + 1), dtype=torch.int32, device=dev)
+        target = torch.empty(G, dtype=torch.int32, device=dev)
+        tuples = None if cand is None else torch.empty((G, m + 1, nf), dtype=torch.int32, device=dev)
+        if G:
+            hip.check(self.lib.cffm_draw_lists(seed, list0, G, _ptr(at), U, m, _ptr(cand), nf, _ptr(lists), _ptr(tuples), _ptr(target),
+                                               self._stream()))
+        return tuples, lists, target
+
     def list_step_ok(self, B):
         """True where train_step_lists_fused serves B = G * Lg rows of this engine's shape (cffm_list_step_ok; host only)."""
         return bool(self.lib.cffm_list_step_ok(self._s, int(B)))

@@ -205,3 +205,61 @@ def table_rows(cfg, seed, rows, dtype=np.float64):
             out[name] = np.zeros((rows.shape[0], width), dtype=dtype)
     out['feature_bias'] = np.zeros((rows.shape[0], 1), dtype=dtype)
     return out
+
+
+# ---- ranked lists drawn BY LIST ID: the numpy twin (and the specification) of cffm_draw_lists, include/cffm_hip.h ----------------
+DRAW_TAG = 2                 # fourth counter word of the list draw; the table draw uses 0 (inner) and 1 (outer) there
+DRAW_MAX_M = 1023            # lists of at most 1024, the bound cffm_topk has
+
+
+def draw_words(seed, ids, n_words):
+    """Words 0 .. n_words - 1 of the lists ``ids`` (64-bit list ids), uint64 [G, n_words]: word i is output word i & 3 of
+    philox4x32_10(counter = (id lo, id hi, i >> 2, DRAW_TAG), key = (seed lo, seed hi))."""
+    seed = int(seed) & 0xffffffffffffffff
+    g = np.asarray(ids).astype(np.uint64).reshape(-1, 1)
+    q = np.arange((int(n_words) + 3) // 4, dtype=np.uint64).reshape(1, -1)
+    x = philox4x32_10((g & np.uint64(0xffffffff), g >> np.uint64(32), q, np.uint64(DRAW_TAG)), (seed & 0xffffffff, seed >> 32))
+    return np.stack(x, axis=2).reshape(g.shape[0], -1)[:, :int(n_words)].astype(np.uint64)
+
+
+def draw_lists(seed, list0, at, U, m):
+    """G = len(at) ranked lists over a set of U distinct tuples: list g (id list0 + g) holds its positive at[g] and m distinct
+    other indices of [0, U), the positive at a drawn place.  Returns (lists int64 [G, m + 1], place int64 [G]).  A list is a
+    function of (seed, id) alone.  Integer arithmetic only: the negatives are the length-m prefix of a Fisher-Yates shuffle of
+    0 .. U - 2 carried as a sparse map (position -> value, absent = identity), step i swapping position i with
+    t = i + ((w_i * (U - 1 - i)) >> 32); a value >= at[g] is moved up by one (the set without the target); the place is
+    (w_m * (m + 1)) >> 32.  The map is two arrays filled in step order, as the kernel holds it."""
+    at = np.asarray(at).astype(np.int64).reshape(-1)
+    U, m, G = int(U), int(m), int(at.shape[0])
+    if U < 2 or not 1 <= m <= U - 1:
+        raise ValueError('draw_lists: needs U >= 2 and 1 <= m <= U - 1')
+    n = U - 1
+    w = draw_words(seed, np.uint64(int(list0)) + np.arange(G, dtype=np.uint64), m + 1)
+    sh = np.uint64(32)
+    keys = np.full((G, m), -1, dtype=np.int64)
+    vals = np.zeros((G, m), dtype=np.int64)
+    cnt = np.zeros(G, dtype=np.int64)
+    chosen = np.empty((G, m), dtype=np.int64)
+    rows = np.arange(G)
+
+    def find(k, i):
+        hit = keys[:, :max(i, 1)] == k[:, None]             # unfilled entries hold -1
+        return hit.any(axis=1), hit.argmax(axis=1)
+
+    for i in range(m):
+        t = i + ((w[:, i] * np.uint64(n - i)) >> sh).astype(np.int64)
+        has_t, pos_t = find(t, i)
+        has_i, pos_i = find(np.full(G, i, dtype=np.int64), i)
+        vt = np.where(has_t, vals[rows, pos_t], t)
+        vi = np.where(has_i, vals[rows, pos_i], i)
+        chosen[:, i] = vt
+        slot = np.where(has_t, pos_t, cnt)                  # map[t] = vi: the entry of t, or a new one
+        keys[rows, slot] = t
+        vals[rows, slot] = vi
+        cnt += ~has_t
+    neg = chosen + (chosen >= at[:, None])
+    place = ((w[:, m] * np.uint64(m + 1)) >> sh).astype(np.int64)
+    p = np.arange(m + 1)[None, :]
+    src = np.clip(p - (p > place[:, None]), 0, m - 1)
+    lists = np.where(p == place[:, None], at[:, None], np.take_along_axis(neg, src, axis=1))
+    return lists, place

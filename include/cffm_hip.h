@@ -580,6 +580,29 @@ int cffm_train_step_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const
                           const int32_t *cand, int64_t cand_stride, int32_t Lg, const int32_t *target, int32_t kind,
                           int32_t *ids_out, float *dout, float *terms, void *ws, float *loss, void *scratch, void *stream);
 
+/* ---- ranked lists drawn on the device, by list id ----------------------------------------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes; the
+ * table draw (cffm_init_table_rows) keeps its bits.
+ *
+ * cffm_draw_lists: G lists of m + 1 indices into a set of U distinct tuples.  List g has the id list0 + g and is a function of
+ * (seed, id) alone - the same list under every split of an epoch into calls.  at: device int32 [G], the index of each list's
+ * positive.  The list holds at[g] and m distinct other indices of [0, U): the length-m prefix of a uniform permutation of the set
+ * without at[g] (sparse Fisher-Yates on Philox4x32-10 words, counter (id lo, id hi, word >> 2, 2), key seed), with the positive at a
+ * place drawn from word m.  cffm_amd/spec.py draw_lists() is the specification; the match is exact.
+ *   lists_out   int32 [G][m + 1] indices, or NULL
+ *   tuples_out  int32 [G][m + 1][nf], tuples_out[g][p][a] = cand[lists[g][p]][a] with cand device int32 [U][nf]: the cand operand,
+ *               at cand_ctx_stride = (m + 1) * nf, of cffm_expand_candidates_ex and cffm_train_step_lists.  NULL together with cand
+ *               for the indices alone (nf is then not used beyond the size check)
+ *   target_out  int32 [G], the place of the positive in its list: the target of cffm_list_loss and cffm_rank_of
+ * Writes exactly those elements: no scratch, no atomics, the same bits on every call.  A list whose at[g] lies outside [0, U) gets
+ * target_out = -1, an index row of -1 and a tuple row of zeros; nothing is read out of range (cffm_list_loss gives such a list a
+ * zero term).  One launch.
+ * CFFM_ERR_BAD_SHAPE, before any launch, for: U < 2; m < 1; m > U - 1; m > 1023; G < 0; list0 < 0; list0 + G beyond int64;
+ * G * (m + 1) * max(nf, 1) >= 2^31; nf < 0; nf == 0 with a non-NULL cand or tuples_out; exactly one of cand / tuples_out NULL; both
+ * lists_out and tuples_out NULL; a NULL at or target_out.  G == 0 (with arguments that pass) returns 0 without a launch. */
+int cffm_draw_lists(uint64_t seed, int64_t list0, int32_t G, const int32_t *at, int32_t U, int32_t m, const int32_t *cand,
+                    int32_t nf, int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
