@@ -723,20 +723,69 @@ class CFFM(object):
             raise ValueError("%s: sampler='device' draws lists of at most 1024: negatives must be <= 1023, not %d" % (who, int(negatives)))
 
     @staticmethod
-    def _draw_lists_device(eng, seed, list0, at, U, m, cand):
+    def _negative_cdf(who, eng, negative_weights, negative_power, sampler, m, U, counts):
+        """The cdf words of HipEngine.draw_lists_weighted on the device (int32 storage of cffm_amd.spec.weight_cdf, built on the
+        host once per call; U words cross the bus), or None for negative_weights=None.  counts: a callable that returns the
+        occurrence count of every distinct tuple as a device tensor [U] (for 'popularity'), or None where there is no data to count."""
+        import torch
+        from .spec import weight_cdf
+        if negative_weights is None:
+            return None
+        if sampler != 'device':
+            raise ValueError("%s: negative_weights needs sampler='device', the only sampler that draws weighted lists (not %r)"
+                             % (who, sampler))
+        if isinstance(negative_weights, str):
+            if negative_weights != 'popularity':
+                raise ValueError("%s: negative_weights must be None, 'popularity' or an array of %d weights, not %r"
+                                 % (who, U, negative_weights))
+            if counts is None:
+                raise ValueError("%s: negative_weights='popularity' counts the tuples of the data the candidates are built from; with "
+                                 "explicit candidates pass negative_weights as an array of %d weights" % (who, U))
+            power = float(negative_power)
+            if not np.isfinite(power):
+                raise ValueError('%s: negative_power must be finite, not %r' % (who, negative_power))
+            w = counts().double().cpu().numpy() ** power
+        else:
+            w = np.asarray(negative_weights, dtype=np.float64)
+            if w.shape != (U,):
+                raise ValueError('%s: negative_weights must hold one weight per distinct tuple, shape (%d,), in the lexicographic order '
+                                 'of the tuples, not shape %s' % (who, U, w.shape))
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError('%s: negative_weights must be non-negative and finite' % who)
+        if int((w > 0).sum()) < m + 1:
+            raise ValueError('%s: negative_weights has %d positive weights; lists of %d need at least %d'
+                             % (who, int((w > 0).sum()), m + 1, m + 1))
+        return torch.from_numpy(weight_cdf(w).view(np.int32)).to(eng.device)
+
+    @staticmethod
+    def _draw_lists_device(eng, seed, list0, at, U, m, cand, cdf=None, who=None):
         """HipEngine.draw_lists for the lists list0 .. list0 + len(at) - 1, in as many calls as the 2^31 element bound of one call
-        asks for (a list is a function of its id, so the split does not show): (tuples int32 [G, m + 1, nf], target int32 [G])."""
+        asks for (a list is a function of its id, so the split does not show): (tuples int32 [G, m + 1, nf], target int32 [G]).
+        With cdf (from _negative_cdf) the lists are those of HipEngine.draw_lists_weighted, and a list that came back incomplete
+        raises ValueError (one device reduction and one read per call of this function)."""
         import torch
         G = int(at.shape[0])
         per = max(1, ((1 << 31) - 1) // ((m + 1) * int(cand.shape[1])))
+
+        def draw(g0, a):
+            if cdf is None:
+                return eng.draw_lists(seed, g0, a, U, m, cand)
+            return eng.draw_lists_weighted(seed, g0, a, cdf, m, cand)
+
         if G <= per:
-            tuples, _, target = eng.draw_lists(seed, list0, at, U, m, cand)
-            return tuples, target
-        parts = [eng.draw_lists(seed, list0 + g0, at[g0:g0 + per], U, m, cand) for g0 in range(0, G, per)]
-        return torch.cat([p[0] for p in parts]), torch.cat([p[2] for p in parts])
+            tuples, _, target = draw(list0, at)
+        else:
+            parts = [draw(list0 + g0, at[g0:g0 + per]) for g0 in range(0, G, per)]
+            tuples, target = torch.cat([p[0] for p in parts]), torch.cat([p[2] for p in parts])
+        if cdf is not None:
+            short = int(((target < 0) & (at >= 0) & (at < U)).sum())
+            if short:
+                raise ValueError('%s: negative_weights is too skewed for lists of %d under the word cap of the weighted draw: %d of %d '
+                                 'lists did not collect their %d negatives (cffm_amd.spec.draw_weighted_cap)' % (who, m + 1, short, G, m))
+        return tuples, target
 
     def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand',
-                                sampler='host'):
+                                sampler='host', negative_weights=None, negative_power=0.75):
         """(HR@k, NDCG@k) over the rows of `data` with a positive label, the target being the row's own tuple at `fields`.
         negatives=None: one shared list - by default the distinct tuples at `fields` over the train split and `data`, sorted
         (torch.unique(dim=0) on the device); explicit candidates [N] / [N, nf] that lack a target raise ValueError.  negatives=m:
@@ -749,7 +798,16 @@ class CFFM(object):
         shared list and for the sampled lists alike).
         sampler: 'host' (default) is the draw above.  'device' draws the lists on the GPU (HipEngine.draw_lists(seed, 0, ...):
         cffm_amd.spec.draw_lists is the specification, list r a function of (seed, r) alone) - other lists than 'host' draws, of the
-        same distribution, at most 1023 negatives; under a process group every rank draws its own share of the rows only."""
+        same distribution, at most 1023 negatives; under a process group every rank draws its own share of the rows only.
+        negative_weights (with negatives=m and sampler='device' only; a ValueError names it otherwise): None (default) draws the
+        negatives uniformly, everything as without the keyword.  'popularity' draws them in proportion to count ** negative_power,
+        count the number of rows (any label) of the train split plus `data` that carry the tuple; with explicit `candidates` there
+        is nothing to count and a ValueError asks for an array.  An array [U] gives non-negative finite weights in the lexicographic
+        order of the distinct tuples (a zero weight is never drawn).  The lists are those of HipEngine.draw_lists_weighted(seed, r0,
+        ...) (cffm_amd.spec.draw_lists_weighted is the specification: successive sampling without replacement by rejection, list r
+        a function of (seed, r) alone); they differ from the uniform device lists even for equal weights.  Fewer than m + 1
+        positive weights, and weights so skewed that a list does not collect its m negatives under the word cap, raise ValueError.
+        Out of scope: hard-negative (model-scored) draws."""
         import torch
         self._check_sampler('evaluate_ranking_tuples()', sampler, negatives)
         eng = self._ranking_engine()
@@ -781,13 +839,21 @@ class CFFM(object):
             share = -(-P // self.world)
             r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
         N, lists, drawn = U, None, None
+        if negatives is None and negative_weights is not None:
+            raise ValueError('evaluate_ranking_tuples(): negative_weights weighs the drawn negatives; it needs negatives=m')
         if negatives is not None:
             m = int(negatives)
             if m < 1 or m >= U:
                 raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
             N = m + 1
+
+            def counts():                                                      # rows of any label, in the order of cand
+                return torch.unique(torch.cat([self._device_split(d)[0][:, colt] for d in splits]), dim=0, return_counts=True)[1]
+
+            cdf = self._negative_cdf('evaluate_ranking_tuples()', eng, negative_weights, negative_power, sampler, m, U,
+                                     counts if candidates is None else None)
             if sampler == 'device':                                            # this rank's rows only: list r is row r's
-                drawn, place = self._draw_lists_device(eng, seed, r0, tpos[r0:r1], U, m, cand)
+                drawn, place = self._draw_lists_device(eng, seed, r0, tpos[r0:r1], U, m, cand, cdf, 'evaluate_ranking_tuples()')
                 tpos = torch.cat([tpos.new_zeros(r0), place.to(tpos.dtype), tpos.new_zeros(P - r1)])
             else:
                 lists, place = self._draw_lists(np.random.RandomState(seed), tpos.cpu().numpy(), U, m)
@@ -816,7 +882,8 @@ class CFFM(object):
         return hits / rows, gains / rows
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
-    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host'):
+    def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host',
+                      negative_weights=None, negative_power=0.75):
         """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
         its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
         the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
@@ -834,7 +901,18 @@ class CFFM(object):
         the only thing that crosses the bus) and draws the epoch's lists on the GPU: list j of epoch e, the one of the j-th permuted
         positive, is list e * P + j of HipEngine.draw_lists(seed, ...) (cffm_amd.spec.draw_lists is the specification), a function of
         (seed, e * P + j) alone and so the same under every lists_per_step.  Other lists than 'host' draws, of the same
-        distribution; at most 1023 negatives."""
+        distribution; at most 1023 negatives.
+        negative_weights (with sampler='device' only; a ValueError names it otherwise): None (default) draws the negatives
+        uniformly, everything as without the keyword.  'popularity' draws them in proportion to count ** negative_power, count the
+        number of rows of `data` (any label) that carry the tuple - the usual remedy for uniform negatives that are almost all
+        trivially easy on a long-tailed catalogue.  An array [U] gives non-negative finite weights in the lexicographic order of the
+        distinct tuples (a zero weight is never drawn).  The cdf is built once per call on the host (cffm_amd.spec.weight_cdf; U
+        words cross the bus) and list e * P + j is that of HipEngine.draw_lists_weighted(seed, ...): successive sampling without
+        replacement by rejection, cffm_amd.spec.draw_lists_weighted the specification.  These lists differ from the uniform device
+        lists even for equal weights.  The BPR and softmax losses are used as they are: no logQ correction of the sampled softmax
+        is applied.  Fewer than negatives + 1 positive weights, and weights so skewed that a list does not collect its negatives
+        under the word cap (checked after each epoch's draw, before its first step), raise ValueError.  Out of scope: hard-negative
+        (model-scored) draws, the multi-GPU list step, other optimizers."""
         import torch
         from . import hip
         self._check_sampler('train_ranking()', sampler, negatives)
@@ -870,6 +948,8 @@ class CFFM(object):
             raise ValueError('train_ranking(): lists_per_step must be >= 1 (batch_size %d holds no list of %d)' % (self.batch_size, m + 1))
         at_dev = self._tuple_positions(cand, ctx[:, colt].to(torch.int32))
         at = at_dev.cpu().numpy() if sampler == 'host' else None
+        cdf = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, m, U,
+                                 lambda: torch.unique(ids[:, colt], dim=0, return_counts=True)[1])
         means = []
         for epoch in range(epochs):
             t1 = time()
@@ -878,7 +958,7 @@ class CFFM(object):
             if sampler == 'device':
                 permt = torch.from_numpy(perm).to(eng.device)
                 rows = ctx[permt]
-                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, m, cand)
+                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, m, cand, cdf, 'train_ranking()')
             else:
                 lists, place = self._draw_lists(rng, at[perm], U, m)
                 rows = ctx[torch.from_numpy(perm).to(eng.device)]

@@ -828,6 +828,34 @@ class HipEngine(object):
                                                self._stream()))
         return tuples, lists, target
 
+    def draw_lists_weighted(self, seed, list0, at, cdf, m, cand=None):
+        """cffm_draw_lists_weighted: draw_lists with the m negatives drawn in proportion to weights, by rejection - successive
+        sampling without replacement over the set without at[g]; cffm_amd.spec.draw_lists_weighted is the specification.  cdf: int32
+        or uint32 [U] on the device, the words of cffm_amd.spec.weight_cdf (reinterpreted, not converted); U = len(cdf).  cand:
+        int32 [U, nf] on the device, or None for the indices alone.  Returns (tuples int32 [G, m + 1, nf] = cand[lists] or None,
+        lists int32 [G, m + 1], target int32 [G]) on the device; a list that did not collect m negatives within the word cap (too
+        skewed weights) and one whose at[g] is outside [0, U) come back as -1 / zeros / target -1.  Nothing synchronises."""
+        seed, list0, m = int(seed) & 0xffffffffffffffff, int(list0), int(m)
+        at = self._ids(at.reshape(-1))
+        if cdf.dim() != 1 or cdf.dtype not in (torch.int32, torch.uint32) or cdf.device != at.device:
+            raise ValueError('draw_lists_weighted: cdf must be an int32 / uint32 vector on the device (spec.weight_cdf)')
+        cdf = cdf.contiguous()
+        G, U, nf = int(at.numel()), int(cdf.numel()), 0
+        if cand is not None:
+            if cand.dim() != 2 or int(cand.shape[0]) != U or int(cand.shape[1]) < 1:
+                raise ValueError('draw_lists_weighted: cand must be [U = %d, nf >= 1]' % U)
+            cand, nf = self._ids(cand), int(cand.shape[1])
+        if U < 1 or not 1 <= m <= min(U - 1, 1023):
+            raise ValueError('draw_lists_weighted: needs 1 <= m <= min(U - 1, 1023) (U = %d, m = %d)' % (U, m))
+        dev = self.device
+        lists = torch.empty((G, m + 1), dtype=torch.int32, device=dev)
+        target = torch.empty(G, dtype=torch.int32, device=dev)
+        tuples = None if cand is None else torch.empty((G, m + 1, nf), dtype=torch.int32, device=dev)
+        if G:
+            hip.check(self.lib.cffm_draw_lists_weighted(seed, list0, G, _ptr(at), U, m, _ptr(cdf), _ptr(cand), nf, _ptr(lists),
+                                                        _ptr(tuples), _ptr(target), self._stream()))
+        return tuples, lists, target
+
     def list_step_ok(self, B):
         """True where train_step_lists_fused serves B = G * Lg rows of this engine's shape (cffm_list_step_ok; host only)."""
         return bool(self.lib.cffm_list_step_ok(self._s, int(B)))

@@ -263,3 +263,112 @@ def draw_lists(seed, list0, at, U, m):
     src = np.clip(p - (p > place[:, None]), 0, m - 1)
     lists = np.where(p == place[:, None], at[:, None], np.take_along_axis(neg, src, axis=1))
     return lists, place
+
+
+# ---- weighted ranked lists drawn BY LIST ID: the numpy twin (and the specification) of cffm_draw_lists_weighted -------------------
+DRAW_W_TAG = 3               # fourth counter word of the weighted list draw (the table draw: 0 and 1, the uniform list draw: 2)
+DRAW_W_PLACE = 0xffffffff    # third counter word of the block whose word 0 draws the place
+
+
+def draw_weighted_cap(m):
+    """The most words a list of m negatives consumes before it counts as incomplete: 8 rounds of 64 per 64 slots, and 8 more."""
+    return 64 * (8 * ((int(m) + 1 + 63) // 64) + 8)
+
+
+def weight_cdf(weights):
+    """uint32 [U] for cffm_draw_lists_weighted: the running sum of q_j = floor(w_j * scale) + (w_j > 0) with
+    scale = (2^32 - 1 - U) / sum(w), so that the total is at most 2^32 - 1, every positive weight holds at least one of the T values
+    and a zero weight holds none (cdf[j] == cdf[j - 1]: never drawn).  weights: non-negative, finite, one positive at least."""
+    w = np.asarray(weights, dtype=np.float64)
+    if w.ndim != 1 or w.shape[0] < 1 or not np.isfinite(w).all() or (w < 0).any() or not (w > 0).any():
+        raise ValueError('weight_cdf: weights must be a vector of non-negative finite numbers with at least one positive')
+    U = int(w.shape[0])
+    if U > 2 ** 31 - 1:
+        raise ValueError('weight_cdf: at most 2^31 - 1 weights')
+    total = float(w.sum())
+    if not np.isfinite(total):
+        raise ValueError('weight_cdf: the sum of the weights is not finite')
+    scale = float(2 ** 32 - 1 - U) / total
+    q = np.floor(w * scale).astype(np.uint64) + (w > 0).astype(np.uint64)
+    cdf = np.cumsum(q, dtype=np.uint64)
+    if int(cdf[-1]) > 2 ** 32 - 1:                          # only rounding in sum(w) could do this; never seen
+        raise ValueError('weight_cdf: the quantised weights sum to more than 2^32 - 1')
+    return cdf.astype(np.uint32)
+
+
+def draw_words_weighted(seed, ids, n_words):
+    """Words 0 .. n_words - 1 of the weighted lists ``ids``, uint64 [G, n_words] (n_words a multiple of 4): word i is output word
+    i & 3 of philox4x32_10(counter = (id lo, id hi, i >> 2, DRAW_W_TAG), key = (seed lo, seed hi))."""
+    seed = int(seed) & 0xffffffffffffffff
+    g = np.asarray(ids).astype(np.uint64).reshape(-1, 1)
+    q = np.arange((int(n_words) + 3) // 4, dtype=np.uint64).reshape(1, -1)
+    x = philox4x32_10((g & np.uint64(0xffffffff), g >> np.uint64(32), q, np.uint64(DRAW_W_TAG)), (seed & 0xffffffff, seed >> 32))
+    return np.stack(x, axis=2).reshape(g.shape[0], -1)[:, :int(n_words)].astype(np.uint64)
+
+
+def _accept_first(cand, at, m):
+    """Sequential acceptance over the candidate words of every row at once: candidate i is accepted iff it is not the row's target
+    and did not occur earlier in the row.  Returns (neg int64 [G, m], the first m accepted in order, -1 where there are fewer;
+    full bool [G])."""
+    G, n = cand.shape
+    order = np.argsort(cand, axis=1, kind='stable')
+    srt = np.take_along_axis(cand, order, axis=1)
+    first_sorted = np.ones((G, n), dtype=bool)
+    first_sorted[:, 1:] = srt[:, 1:] != srt[:, :-1]          # stable: the earliest occurrence leads its run
+    first = np.zeros((G, n), dtype=bool)
+    np.put_along_axis(first, order, first_sorted, axis=1)
+    ok = first & (cand != at[:, None])
+    rank = np.cumsum(ok, axis=1)
+    neg = np.full((G, m + 1), -1, dtype=np.int64)            # column m takes everything past the m-th
+    rows, cols = np.nonzero(ok)
+    neg[rows, np.minimum(rank[rows, cols] - 1, m)] = cand[rows, cols]
+    return neg[:, :m], rank[:, -1] >= m
+
+
+def draw_lists_weighted(seed, list0, at, cdf, m):
+    """G = len(at) ranked lists over U = len(cdf) distinct tuples with the negatives drawn in proportion to the weights behind
+    ``cdf`` (weight_cdf): list g (id list0 + g) holds its positive at[g] and m distinct other indices, the positive at a drawn
+    place.  Returns (lists int64 [G, m + 1], place int64 [G]).  A list is a function of (seed, id) alone; integer arithmetic only.
+    With T = cdf[U - 1]: word w gives r = (w * T) >> 32 and the candidate j = #{cdf <= r}, clamped to U - 1; candidates are taken
+    in word order, one is accepted iff it is not at[g] and was not accepted before, and the negatives are the first m accepted in
+    that order - successive sampling without replacement, proportional to the weights, over the set without the target.  A list
+    that has not accepted m after draw_weighted_cap(m) words is incomplete: its row and its place are -1, as they are for an at[g]
+    outside [0, U) and for T == 0.  The place is (w_place * (m + 1)) >> 32, w_place word 0 of the counter
+    (id lo, id hi, DRAW_W_PLACE, DRAW_W_TAG)."""
+    at = np.asarray(at).astype(np.int64).reshape(-1)
+    cdf = np.asarray(cdf)
+    if cdf.ndim != 1 or cdf.shape[0] < 1:
+        raise ValueError('draw_lists_weighted: cdf must be a vector of U >= 1 words')
+    cdf = (cdf.astype(np.int64) & 0xffffffff).astype(np.uint64)                  # int32 storage is reinterpreted
+    U, m, G = int(cdf.shape[0]), int(m), int(at.shape[0])
+    if not 1 <= m <= U - 1:
+        raise ValueError('draw_lists_weighted: needs 1 <= m <= U - 1')
+    T = cdf[U - 1]
+    sh = np.uint64(32)
+    ids = np.uint64(int(list0)) + np.arange(G, dtype=np.uint64)
+    lists = np.full((G, m + 1), -1, dtype=np.int64)
+    place = np.full(G, -1, dtype=np.int64)
+    live = np.nonzero((at >= 0) & (at < U))[0] if int(T) > 0 else np.zeros(0, dtype=np.int64)
+    cap = draw_weighted_cap(m)
+    chunk = max(1, (1 << 21) // cap)
+    for c0 in range(0, live.shape[0], chunk):
+        todo = live[c0:c0 + chunk]
+        n = min(cap, 64 * (2 * ((m + 1 + 63) // 64)))
+        while todo.shape[0]:                                 # a prefix of the words decides a list that completes inside it
+            w = draw_words_weighted(seed, ids[todo], n)
+            cand = np.minimum(np.searchsorted(cdf, (w * T) >> sh, side='right'), U - 1).astype(np.int64)
+            neg, full = _accept_first(cand, at[todo], m)
+            done = todo[full]
+            if done.shape[0]:
+                idd = ids[done].reshape(-1, 1)
+                wp = philox4x32_10((idd & np.uint64(0xffffffff), idd >> sh, np.uint64(DRAW_W_PLACE), np.uint64(DRAW_W_TAG)),
+                                   (int(seed) & 0xffffffff, (int(seed) & 0xffffffffffffffff) >> 32))[0].astype(np.uint64).reshape(-1)
+                pl = ((wp * np.uint64(m + 1)) >> sh).astype(np.int64)
+                p = np.arange(m + 1)[None, :]
+                src = np.clip(p - (p > pl[:, None]), 0, m - 1)
+                lists[done] = np.where(p == pl[:, None], at[done][:, None], np.take_along_axis(neg[full], src, axis=1))
+                place[done] = pl
+            if n == cap:
+                break
+            todo, n = todo[~full], min(cap, 2 * n)
+    return lists, place

@@ -603,6 +603,33 @@ int cffm_train_step_lists(const cffm_shape_t *s, const cffm_tables_t *tab, const
 int cffm_draw_lists(uint64_t seed, int64_t list0, int32_t G, const int32_t *at, int32_t U, int32_t m, const int32_t *cand,
                     int32_t nf, int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
 
+/* ---- weighted ranked lists drawn on the device, by list id --------------------------------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes;
+ * cffm_draw_lists keeps its bits.
+ *
+ * cffm_draw_lists_weighted: cffm_draw_lists with the m negatives drawn in proportion to weights - successive sampling without
+ * replacement over the set without at[g].  cdf: device uint32 [U], the running sum of the quantised weights as
+ * cffm_amd/spec.py weight_cdf() makes it (non-decreasing, total T = cdf[U - 1] <= 2^32 - 1; an index whose entry equals the one
+ * before it is never drawn).  T is read on the device; nothing synchronises.  Word i of list id is output word i & 3 of
+ * Philox4x32-10 at counter (id lo, id hi, i >> 2, 3), key seed; it gives r = (word * T) >> 32 and the candidate j = #{cdf <= r},
+ * clamped to U - 1.  Candidates are taken in word order; one is accepted iff it is not at[g] and was not accepted before, and
+ * the negatives are the first m accepted, in that order.  The place of the positive is (word * (m + 1)) >> 32 of output word 0 at
+ * counter (id lo, id hi, 0xffffffff, 3).  A list consumes at most 64 * (8 * ceil((m + 1) / 64) + 8) words: one that is still short
+ * of m then is INCOMPLETE (heavy skew; rejection sampling, part of the contract).  cffm_amd/spec.py draw_lists_weighted() is the
+ * specification; the match is exact.  A cdf that is not non-decreasing gives an unspecified distribution; the search stays inside
+ * [0, U) and nothing is read out of range.
+ *   lists_out, tuples_out, target_out, cand, nf   as in cffm_draw_lists, NULL rules included
+ * An incomplete list, a list whose at[g] lies outside [0, U) and every list when T == 0 get target_out = -1, an index row of -1
+ * and a tuple row of zeros.  Writes exactly G * (m + 1) indices, G * (m + 1) * nf tuple words and G targets: one launch, no
+ * scratch, no atomics, the same bits on every call.
+ * CFFM_ERR_BAD_SHAPE, before any launch, for: U < 1; m < 1; m > U - 1 (so U = 1 is refused); m > 1023; G < 0; list0 < 0; list0 + G
+ * beyond int64; G * (m + 1) * max(nf, 1) >= 2^31; nf < 0; nf == 0 with a non-NULL cand or tuples_out; exactly one of cand /
+ * tuples_out NULL; both lists_out and tuples_out NULL; a NULL at, target_out or cdf.  G == 0 (with arguments that pass) returns 0
+ * without a launch. */
+int cffm_draw_lists_weighted(uint64_t seed, int64_t list0, int32_t G, const int32_t *at, int32_t U, int32_t m,
+                             const uint32_t *cdf, const int32_t *cand, int32_t nf,
+                             int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
