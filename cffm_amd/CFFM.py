@@ -419,10 +419,14 @@ class CFFM(object):
     def _share(self, num_example):
         """This rank's contiguous share [r0, r1) of a split's rows, the block size of the sweep and the number of blocks the
         LARGEST share takes (shares only get shorter with the rank, so that is rank 0's)."""
-        share = -(-num_example // self.world)
-        r0, r1 = min(self.rank * share, num_example), min((self.rank + 1) * share, num_example)
+        r0, r1, share = self._row_share(num_example)
         block = max(int(self.batch_size), 8192)
         return r0, r1, block, -(-share // block)
+
+    def _row_share(self, n):
+        """This rank's contiguous share [r0, r1) of n rows and the size of the largest share; all of them without a process group."""
+        share = -(-n // self.world)
+        return min(self.rank * share, n), min((self.rank + 1) * share, n), share
 
     def predict_split(self, data):
         """Raw (unclipped) predictions of a split as a host float64 array, in the split's current order."""
@@ -464,34 +468,56 @@ class CFFM(object):
         return self.engine
 
     @staticmethod
-    def _candidate_scorer(eng, sweep, N):
-        """The engine call that scores one group of contexts.  'expand': score_candidates, called exactly as before the shared
-        sweep existed; 'shared': score_candidates_shared (ValueError where the shape is not served); 'auto': the shared sweep
-        where the shape is served and N >= SWEEP_MIN_N, else expand."""
-        if sweep not in ('expand', 'shared', 'auto'):
-            raise ValueError("sweep must be 'expand', 'shared' or 'auto', not %r" % (sweep,))
-        if sweep == 'expand':
-            return eng.score_candidates
+    def _scorer(eng, sweep, fields, N, per_context=False):
+        """score(ctx, cand), the engine call that scores one group of contexts.  fields: an int for recommend / evaluate_ranking
+        (cand [N]; 'expand' is score_candidates, called exactly as before the shared sweep existed, and there is no 'tuples'), or
+        the list of columns of the *_tuples methods (cand [N, nf], or [C, N, nf] per context; 'expand' is score_candidate_tuples,
+        bit for bit predict on the expanded rows).  'shared': the shared sweep, one field only (ValueError for tuples or a shape
+        that is not served).  'auto': the shared sweep for one field at a served shape with N >= SWEEP_MIN_N, else expand.
+        'tuples': the tuple sweep (score_candidate_tuples_shared) for any nf >= 1, ValueError where (shape, nf) is not served;
+        'auto' never picks it."""
+        one = isinstance(fields, int)
+        allowed = ('expand', 'shared', 'auto') if one else ('expand', 'shared', 'auto', 'tuples')
+        if sweep not in allowed:
+            raise ValueError('sweep must be %s or %r, not %r' % (', '.join(repr(a) for a in allowed[:-1]), allowed[-1], sweep))
+        cols = [fields] if one else fields
+        nf = len(cols)
+        if sweep == 'tuples':
+            if not eng.sweep_tuples_ok(nf):
+                raise ValueError("sweep='tuples': the tuple sweep does not serve this shape for tuples of %d (both branches, D = 32, "
+                                 "F <= 10, nf <= 4, the candidate kernel within a CU's LDS)" % nf)
+            return lambda ctx, cand: eng.score_candidate_tuples_shared(ctx, fields, cand)
         if sweep == 'shared':
+            if nf > 1:
+                raise ValueError("sweep='shared': the shared sweep scores one field, not tuples of %d" % nf)
             if not eng.sweep_ok():
                 raise ValueError("sweep='shared': the shared sweep does not serve this shape (both branches, D = 32, F <= 10)")
-            return eng.score_candidates_shared
-        if SWEEP_MIN_N is not None and N >= SWEEP_MIN_N and eng.sweep_ok():
-            return eng.score_candidates_shared
-        return eng.score_candidates
+        elif sweep == 'expand' or nf > 1 or SWEEP_MIN_N is None or N < SWEEP_MIN_N or not eng.sweep_ok():
+            expand = eng.score_candidates if one else eng.score_candidate_tuples
+            return lambda ctx, cand: expand(ctx, fields, cand)
+        if per_context:
+            return lambda ctx, cand: eng.score_candidate_lists_shared(ctx, cols[0], cand.reshape(cand.shape[0], cand.shape[1]))
+        return lambda ctx, cand: eng.score_candidates_shared(ctx, cols[0], cand.reshape(-1))
 
-    def _field_ids(self, splits, field):
-        """Sorted distinct ids in column `field` over the given splits, int32 on the device."""
+    def _distinct(self, splits, cols, counts=False):
+        """The distinct tuples at the columns `cols` (ids, for one column) over the given splits, sorted, int32 on the device; with
+        counts, the number of rows (any label) that carry each of them instead."""
         import torch
-        cols = [self._device_split(d)[0][:, field] for d in splits]
-        return torch.unique(torch.cat(cols)).to(torch.int32)
+        rows = torch.cat([self._device_split(d)[0][:, cols] for d in splits])
+        if counts:
+            return torch.unique(rows, dim=0, return_counts=True)[1]
+        return torch.unique(rows, dim=0).to(torch.int32)
+
+    def _eval_splits(self, data):
+        """The splits an evaluation's default candidates come from: the train split last passed to train(), and `data`."""
+        return [data] if self._train_split is None or self._train_split is data else [self._train_split, data]
 
     def _candidates(self, candidates, field, splits):
         import torch
         if not 0 <= int(field) < self.num_field:
             raise ValueError('field %r is outside [0, %d)' % (field, self.num_field))
         if candidates is None:
-            return self._field_ids(splits, int(field))
+            return self._distinct(splits, int(field))
         cand = np.asarray(candidates)
         if cand.ndim != 1 or cand.size == 0:
             raise ValueError('candidates must be a non-empty 1-D array of feature ids')
@@ -513,29 +539,53 @@ class CFFM(object):
         if not 1 <= int(k) <= 1024:
             raise ValueError('recommend(): k must be in [1, 1024]')
         cand = self._candidates(candidates, field, [self._train_split])
+        pos, val = self._topk_sweep(eng, self._contexts(eng, contexts), int(field), cand, False, None, int(k), skip, score_rows, sweep)
+        cand64 = cand.long()
+        ids = torch.where(pos >= 0, cand64[pos.clamp(min=0).long()], cand64.new_full((), -1)).to(torch.int32)
+        return ids.cpu().numpy(), val.cpu().numpy()
+
+    def _contexts(self, eng, contexts):
+        """The caller's context rows [C, F], checked, as int32 on the device."""
+        import torch
         ctx = np.asarray(contexts)
         if ctx.ndim != 2 or ctx.shape[1] != self.num_field:
             raise ValueError('contexts must be [C, %d] feature ids' % self.num_field)
-        ctx = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(eng.device)
-        C, N, k = int(ctx.shape[0]), int(cand.numel()), int(k)
+        return torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(eng.device)
+
+    def _topk_sweep(self, eng, ctx, fields, cand, per_context, counts, k, skip, score_rows, sweep):
+        """The top-k sweep of recommend and recommend_tuples over ctx and cand on the device (fields and cand as _scorer takes
+        them), the contexts in groups of max(1, score_rows // N): (pos int32 [C, k] candidate positions, -1 padded; val float32
+        [C, k], NaN padded) on the device.  skip and counts are the caller's host arrays; counts is merged into the skip mask."""
+        import torch
+        C, N = int(ctx.shape[0]), int(cand.shape[1 if per_context else 0])
+        if per_context and cand.shape[0] != C:
+            raise ValueError('per_context candidates must hold one list per context: [%d, N, ...], not %r' % (C, tuple(cand.shape)))
         mask = None
         if skip is not None:
-            mask = torch.from_numpy(np.ascontiguousarray(np.asarray(skip) != 0)).to(eng.device)
-            if tuple(mask.shape) != (C, N):
+            mask = np.asarray(skip) != 0
+            if mask.shape != (C, N):
                 raise ValueError('skip must be [%d, %d]: contexts x candidates' % (C, N))
-            mask = mask.to(torch.uint8)
-        ids_out = torch.empty((C, k), dtype=torch.int32, device=eng.device)
+        if counts is not None:
+            if not per_context:
+                raise ValueError('counts belongs to per_context candidate lists')
+            cnt = np.asarray(counts)
+            if cnt.shape != (C,) or cnt.dtype.kind not in 'iu' or (cnt < 0).any() or (cnt > N).any():
+                raise ValueError('counts must be [%d] integers in [0, %d]' % (C, N))
+            pad = np.arange(N)[None, :] >= cnt[:, None]
+            mask = pad if mask is None else (mask | pad)
+        if mask is not None:
+            mask = torch.from_numpy(np.ascontiguousarray(mask)).to(eng.device).to(torch.uint8)
+        pos_out = torch.empty((C, k), dtype=torch.int32, device=eng.device)
         val_out = torch.empty((C, k), dtype=torch.float32, device=eng.device)
         group = max(1, int(score_rows) // N)
-        cand64 = cand.long()
-        score = self._candidate_scorer(eng, sweep, N)
+        score = self._scorer(eng, sweep, fields, N, per_context)
         for c0 in range(0, C, group):
             c1 = min(C, c0 + group)
-            scores = score(ctx[c0:c1], int(field), cand)
+            scores = score(ctx[c0:c1], cand[c0:c1] if per_context else cand)
             idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
-            ids_out[c0:c1] = torch.where(idx >= 0, cand64[idx.clamp(min=0).long()], cand64.new_full((), -1)).to(torch.int32)
+            pos_out[c0:c1] = idx
             val_out[c0:c1] = val
-        return ids_out.cpu().numpy(), val_out.cpu().numpy()
+        return pos_out, val_out
 
     def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22, sweep='expand'):
         """(HR@k, NDCG@k) of a split: for every row with label > 0 the context is the row and the target is the row's own id at
@@ -544,11 +594,9 @@ class CFFM(object):
         stays on the device: scores, rank of the target, and the two sums and the count in float64; under a process group with
         replicated tables every rank takes a contiguous share of the positive rows and the sums are all-reduced.  sweep: as in
         recommend()."""
-        import torch
         eng = self._ranking_engine()
         ids, y, _ = self._device_split(data)
-        splits = [data] if self._train_split is None or self._train_split is data else [self._train_split, data]
-        cand = self._candidates(candidates, field, splits)
+        cand = self._candidates(candidates, field, self._eval_splits(data))
         field, k = int(field), int(k)
         if k < 1:
             raise ValueError('evaluate_ranking(): k must be >= 1')
@@ -556,26 +604,27 @@ class CFFM(object):
         P, N = int(ctx.shape[0]), int(cand.numel())
         if P == 0:
             raise ValueError('evaluate_ranking() needs at least one row with a positive label')
-        # position of every target in the candidate list (the first one, should the caller's list repeat an id)
-        tgt = ctx[:, field].long()
-        cs, order = torch.sort(cand.long(), stable=True)
-        at = torch.searchsorted(cs, tgt).clamp(max=N - 1)
-        missing = cs[at] != tgt
+        tgt = ctx[:, field]
+        tpos = self._positions(cand, tgt)
+        missing = tpos == N
         if bool(missing.any()):
             raise ValueError('evaluate_ranking(): target id %d at field %d is not among the candidates'
                              % (int(tgt[missing][0]), field))
-        tpos = order[at].to(torch.int32)
-        r0, r1 = 0, P
-        if self.world > 1:
-            share = -(-P // self.world)
-            r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
-        # [sum of hits, sum of gains, rows, NaN flag]: accumulated on the device, read once
+        r0, r1, _ = self._row_share(P)
+        return self._rank_targets('evaluate_ranking()', eng, self._scorer(eng, sweep, field, N), ctx, lambda c0, c1: cand, tpos, r0, r1,
+                                  N, k, score_rows)
+
+    def _rank_targets(self, who, eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows):
+        """(HR@k, NDCG@k) of the rows [r0, r1) of ctx, in groups of max(1, score_rows // N): score(ctx[c0:c1], cand_of(c0, c1)) and
+        the rank of candidate tpos[c] in row c, the sums [hits, gains, rows, NaN flag] accumulated on the device in float64,
+        all-reduced and read once.  who names the calling method in the NaN error."""
+        import torch
+        tpos = tpos.to(torch.int32)
         sums = torch.zeros(4, dtype=torch.float64, device=eng.device)
         group = max(1, int(score_rows) // N)
-        score = self._candidate_scorer(eng, sweep, N)
         for c0 in range(r0, r1, group):
             c1 = min(r1, c0 + group)
-            scores = score(ctx[c0:c1], field, cand)
+            scores = score(ctx[c0:c1], cand_of(c0, c1))
             rank = eng.rank_of(scores, tpos[c0:c1]).double()
             hit = rank < k
             sums[0] += hit.sum()
@@ -584,13 +633,15 @@ class CFFM(object):
             sums[3] += torch.isnan(scores).any()
         hits, gains, rows, bad = (float(v) for v in self._all_reduce_sum(sums).cpu().numpy())
         if bad:
-            raise ValueError('evaluate_ranking(): predictions contain NaN')
+            raise ValueError('%s: predictions contain NaN' % who)
         return hits / rows, gains / rows
 
     # ---- candidates that are tuples of ids, and a candidate list per context ----------------------------
     # recommend / evaluate_ranking put ONE id at ONE column and leave the context's other ids alone.  Where an item's attributes are
     # fields of their own (frappe: the app's cost next to the app id) that scores rows that cannot occur; the methods below replace
-    # several columns together, from one shared list or from a list per context.  The two methods above stay as they are.
+    # several columns together, from one shared list or from a list per context.  Both pairs are wrappers with their own defaults
+    # and messages around the same code: _scorer picks the engine call (an int field is the one-id form, which still goes to
+    # score_candidates), _topk_sweep is the top-k loop of both recommend methods, _rank_targets the metric loop of both evaluations.
     def _tuple_fields(self, fields):
         cols = [fields] if isinstance(fields, (int, np.integer)) else list(fields)
         cols = [int(f) for f in cols]
@@ -607,31 +658,6 @@ class CFFM(object):
         if cand.ndim != lead + 1 or cand.shape[-1] != nf or cand.size == 0 or cand.dtype.kind not in 'iu':
             raise ValueError('%s must be integer ids of shape %s' % (what, ('[C, N' if lead == 2 else '[N') + (', %d]' % nf if nf > 1 else ']')))
         return np.ascontiguousarray(cand.astype(np.int32))
-
-    @staticmethod
-    def _tuple_scorer(eng, sweep, fields, N, per_context):
-        """score(ctx, cand) for cand [N, nf] (shared) or [C, N, nf] (per context).  'expand': score_candidate_tuples, bit for bit
-        predict on the expanded rows.  'shared': the shared sweep, one field only (ValueError for tuples or a shape that is not
-        served).  'auto': the shared sweep for one field at a served shape with N >= SWEEP_MIN_N, else expand.  'tuples': the tuple
-        sweep (score_candidate_tuples_shared) for any nf >= 1, ValueError where (shape, nf) is not served; 'auto' never picks it."""
-        if sweep not in ('expand', 'shared', 'auto', 'tuples'):
-            raise ValueError("sweep must be 'expand', 'shared', 'auto' or 'tuples', not %r" % (sweep,))
-        nf = len(fields)
-        if sweep == 'tuples':
-            if not eng.sweep_tuples_ok(nf):
-                raise ValueError("sweep='tuples': the tuple sweep does not serve this shape for tuples of %d (both branches, D = 32, "
-                                 "F <= 10, nf <= 4, the candidate kernel within a CU's LDS)" % nf)
-            return lambda ctx, cand: eng.score_candidate_tuples_shared(ctx, fields, cand)
-        if sweep == 'shared':
-            if nf > 1:
-                raise ValueError("sweep='shared': the shared sweep scores one field, not tuples of %d" % nf)
-            if not eng.sweep_ok():
-                raise ValueError("sweep='shared': the shared sweep does not serve this shape (both branches, D = 32, F <= 10)")
-        elif sweep == 'expand' or nf > 1 or SWEEP_MIN_N is None or N < SWEEP_MIN_N or not eng.sweep_ok():
-            return lambda ctx, cand: eng.score_candidate_tuples(ctx, fields, cand)
-        if per_context:
-            return lambda ctx, cand: eng.score_candidate_lists_shared(ctx, fields[0], cand.reshape(cand.shape[0], cand.shape[1]))
-        return lambda ctx, cand: eng.score_candidates_shared(ctx, fields[0], cand.reshape(-1))
 
     def recommend_tuples(self, contexts, fields, candidates, per_context=False, counts=None, k=10, skip=None, score_rows=1 << 22,
                          sweep='expand'):
@@ -652,47 +678,15 @@ class CFFM(object):
         cols = self._tuple_fields(fields)
         if not 1 <= int(k) <= 1024:
             raise ValueError('recommend_tuples(): k must be in [1, 1024]')
-        ctx = np.asarray(contexts)
-        if ctx.ndim != 2 or ctx.shape[1] != self.num_field:
-            raise ValueError('contexts must be [C, %d] feature ids' % self.num_field)
-        cand = self._tuple_array(candidates, len(cols), 2 if per_context else 1, 'candidates')
-        C, N, k = int(ctx.shape[0]), int(cand.shape[-2]), int(k)
-        if per_context and cand.shape[0] != C:
-            raise ValueError('per_context candidates must hold one list per context: [%d, N, ...], not %r' % (C, cand.shape))
-        mask = None
-        if skip is not None:
-            mask = np.asarray(skip) != 0
-            if mask.shape != (C, N):
-                raise ValueError('skip must be [%d, %d]: contexts x candidates' % (C, N))
-        if counts is not None:
-            if not per_context:
-                raise ValueError('counts belongs to per_context candidate lists')
-            cnt = np.asarray(counts)
-            if cnt.shape != (C,) or cnt.dtype.kind not in 'iu' or (cnt < 0).any() or (cnt > N).any():
-                raise ValueError('counts must be [%d] integers in [0, %d]' % (C, N))
-            pad = np.arange(N)[None, :] >= cnt[:, None]
-            mask = pad if mask is None else (mask | pad)
-        dev = eng.device
-        ctx = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(dev)
-        cand = torch.from_numpy(cand).to(dev)
-        if mask is not None:
-            mask = torch.from_numpy(np.ascontiguousarray(mask)).to(dev).to(torch.uint8)
-        pos_out = torch.empty((C, k), dtype=torch.int32, device=dev)
-        val_out = torch.empty((C, k), dtype=torch.float32, device=dev)
-        group = max(1, int(score_rows) // N)
-        score = self._tuple_scorer(eng, sweep, cols, N, per_context)
-        for c0 in range(0, C, group):
-            c1 = min(C, c0 + group)
-            scores = score(ctx[c0:c1], cand[c0:c1] if per_context else cand)
-            idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
-            pos_out[c0:c1] = idx
-            val_out[c0:c1] = val
-        return pos_out.cpu().numpy(), val_out.cpu().numpy()
+        ctx = self._contexts(eng, contexts)
+        cand = torch.from_numpy(self._tuple_array(candidates, len(cols), 2 if per_context else 1, 'candidates')).to(eng.device)
+        pos, val = self._topk_sweep(eng, ctx, cols, cand, per_context, counts, int(k), skip, score_rows, sweep)
+        return pos.cpu().numpy(), val.cpu().numpy()
 
     @staticmethod
-    def _tuple_positions(cand, tgt):
-        """Position in cand [N, nf] of every row of tgt [P, nf] (the first one, should the list repeat a tuple); N where it is
-        missing.  On the device: one torch.unique(dim=0) over both."""
+    def _positions(cand, tgt):
+        """Position in cand [N, nf] of every row of tgt [P, nf] - or in ids [N] of every id of [P] - the first one, should the list
+        repeat an entry; N where it is missing.  On the device: one torch.unique(dim=0) over both."""
         import torch
         N = int(cand.shape[0])
         inv = torch.unique(torch.cat([cand, tgt]), dim=0, return_inverse=True)[1]      # one number per distinct tuple
@@ -818,8 +812,7 @@ class CFFM(object):
             raise ValueError('evaluate_ranking_tuples(): k must be >= 1')
         colt = torch.tensor(cols, dtype=torch.long, device=eng.device)
         if candidates is None:
-            splits = [data] if self._train_split is None or self._train_split is data else [self._train_split, data]
-            cand = torch.unique(torch.cat([self._device_split(d)[0][:, colt] for d in splits]), dim=0).to(torch.int32)
+            cand = self._distinct(self._eval_splits(data), colt)
         else:
             cand = torch.from_numpy(self._tuple_array(candidates, len(cols), 1, 'candidates')).to(eng.device)
             if negatives is not None:
@@ -829,16 +822,13 @@ class CFFM(object):
         if P == 0:
             raise ValueError('evaluate_ranking_tuples() needs at least one row with a positive label')
         tgt = ctx[:, colt].to(torch.int32)
-        tpos = self._tuple_positions(cand, tgt)
+        tpos = self._positions(cand, tgt)
         missing = tpos == U
         if bool(missing.any()):
             raise ValueError('evaluate_ranking_tuples(): target %s at fields %s is not among the candidates'
                              % (tuple(int(v) for v in tgt[missing][0]), tuple(cols)))
-        r0, r1 = 0, P
-        if self.world > 1:
-            share = -(-P // self.world)
-            r0, r1 = min(self.rank * share, P), min((self.rank + 1) * share, P)
-        N, lists, drawn = U, None, None
+        r0, r1, _ = self._row_share(P)
+        N, cand_of = U, lambda c0, c1: cand
         if negatives is None and negative_weights is not None:
             raise ValueError('evaluate_ranking_tuples(): negative_weights weighs the drawn negatives; it needs negatives=m')
         if negatives is not None:
@@ -847,39 +837,20 @@ class CFFM(object):
                 raise ValueError('evaluate_ranking_tuples(): negatives must be in [1, %d): the distinct tuples without the target' % U)
             N = m + 1
 
-            def counts():                                                      # rows of any label, in the order of cand
-                return torch.unique(torch.cat([self._device_split(d)[0][:, colt] for d in splits]), dim=0, return_counts=True)[1]
-
-            cdf = self._negative_cdf('evaluate_ranking_tuples()', eng, negative_weights, negative_power, sampler, m, U,
-                                     counts if candidates is None else None)
+            # rows of any label, in the order of cand; explicit candidates leave nothing to count
+            counts = None if candidates is not None else lambda: self._distinct(self._eval_splits(data), colt, counts=True)
+            cdf = self._negative_cdf('evaluate_ranking_tuples()', eng, negative_weights, negative_power, sampler, m, U, counts)
             if sampler == 'device':                                            # this rank's rows only: list r is row r's
                 drawn, place = self._draw_lists_device(eng, seed, r0, tpos[r0:r1], U, m, cand, cdf, 'evaluate_ranking_tuples()')
                 tpos = torch.cat([tpos.new_zeros(r0), place.to(tpos.dtype), tpos.new_zeros(P - r1)])
+                cand_of = lambda c0, c1: drawn[c0 - r0:c1 - r0]
             else:
                 lists, place = self._draw_lists(np.random.RandomState(seed), tpos.cpu().numpy(), U, m)
                 lists = torch.from_numpy(lists).to(eng.device)
                 tpos = torch.from_numpy(place).to(eng.device)
-        tpos = tpos.to(torch.int32)
-        sums = torch.zeros(4, dtype=torch.float64, device=eng.device)      # [hits, gains, rows, NaN flag], read once
-        group = max(1, int(score_rows) // N)
-        score = self._tuple_scorer(eng, sweep, cols, N, negatives is not None)
-        for c0 in range(r0, r1, group):
-            c1 = min(r1, c0 + group)
-            if drawn is not None:
-                tuples = drawn[c0 - r0:c1 - r0]
-            else:
-                tuples = cand if lists is None else cand[lists[c0:c1]]
-            scores = score(ctx[c0:c1], tuples)
-            rank = eng.rank_of(scores, tpos[c0:c1]).double()
-            hit = rank < k
-            sums[0] += hit.sum()
-            sums[1] += torch.where(hit, 1.0 / torch.log2(rank + 2.0), torch.zeros_like(rank)).sum()
-            sums[2] += c1 - c0
-            sums[3] += torch.isnan(scores).any()
-        hits, gains, rows, bad = (float(v) for v in self._all_reduce_sum(sums).cpu().numpy())
-        if bad:
-            raise ValueError('evaluate_ranking_tuples(): predictions contain NaN')
-        return hits / rows, gains / rows
+                cand_of = lambda c0, c1: cand[lists[c0:c1]]
+        score = self._scorer(eng, sweep, cols, N, negatives is not None)
+        return self._rank_targets('evaluate_ranking_tuples()', eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows)
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
     def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host',
@@ -936,7 +907,7 @@ class CFFM(object):
         m, epochs = int(negatives), int(epochs)
         ids, y, _ = self._device_split(data)
         colt = torch.tensor(cols, dtype=torch.long, device=eng.device)
-        cand = torch.unique(ids[:, colt], dim=0).to(torch.int32)
+        cand = self._distinct([data], colt)
         ctx = ids[y.reshape(-1) > 0]
         P, U = int(ctx.shape[0]), int(cand.shape[0])
         if P == 0:
@@ -946,10 +917,10 @@ class CFFM(object):
         per = int(self.batch_size // (m + 1) if lists_per_step is None else lists_per_step)
         if per < 1:
             raise ValueError('train_ranking(): lists_per_step must be >= 1 (batch_size %d holds no list of %d)' % (self.batch_size, m + 1))
-        at_dev = self._tuple_positions(cand, ctx[:, colt].to(torch.int32))
+        at_dev = self._positions(cand, ctx[:, colt].to(torch.int32))
         at = at_dev.cpu().numpy() if sampler == 'host' else None
         cdf = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, m, U,
-                                 lambda: torch.unique(ids[:, colt], dim=0, return_counts=True)[1])
+                                 lambda: self._distinct([data], colt, counts=True))
         means = []
         for epoch in range(epochs):
             t1 = time()

@@ -103,16 +103,21 @@ __global__ __launch_bounds__(64 * DL_WAVES) void draw_lists_kernel(uint32_t k0, 
     }
 }
 
+// What both entry points refuse, given a U their own check let through (U >= 1, so U - 1 does not wrap).
+static bool draw_args_ok(int64_t list0, int32_t G, const int32_t* at, int32_t U, int32_t m, const int32_t* cand, int32_t nf,
+                         const int32_t* lists_out, const int32_t* tuples_out, const int32_t* target_out) {
+    if (m < 1 || m > U - 1 || m > 1023 || G < 0 || list0 < 0 || list0 > INT64_MAX - (int64_t)G || nf < 0) return false;
+    const int64_t slots = (int64_t)G * (m + 1);                                    // < 2^41
+    if (slots >= (1ll << 31) || slots * (nf > 1 ? nf : 1) >= (1ll << 31)) return false;
+    if ((cand == nullptr) != (tuples_out == nullptr)) return false;
+    if (nf == 0 && cand) return false;
+    if (!lists_out && !tuples_out) return false;
+    return at && target_out;
+}
+
 extern "C" int cffm_draw_lists(uint64_t seed, int64_t list0, int32_t G, const int32_t* at, int32_t U, int32_t m, const int32_t* cand,
                                int32_t nf, int32_t* lists_out, int32_t* tuples_out, int32_t* target_out, void* stream) {
-    if (U < 2 || m < 1 || m > U - 1 || m > 1023 || G < 0 || list0 < 0 || list0 > INT64_MAX - (int64_t)G || nf < 0)
-        return CFFM_ERR_BAD_SHAPE;
-    const int64_t slots = (int64_t)G * (m + 1);                                    // < 2^41
-    if (slots >= (1ll << 31) || slots * (nf > 1 ? nf : 1) >= (1ll << 31)) return CFFM_ERR_BAD_SHAPE;
-    if ((cand == nullptr) != (tuples_out == nullptr)) return CFFM_ERR_BAD_SHAPE;
-    if (nf == 0 && cand) return CFFM_ERR_BAD_SHAPE;
-    if (!lists_out && !tuples_out) return CFFM_ERR_BAD_SHAPE;
-    if (!at || !target_out) return CFFM_ERR_BAD_SHAPE;
+    if (U < 2 || !draw_args_ok(list0, G, at, U, m, cand, nf, lists_out, tuples_out, target_out)) return CFFM_ERR_BAD_SHAPE;
     if (G == 0) return 0;
     const int W = (m + 1 + 3) & ~3;
     const size_t lds = (size_t)DL_WAVES * 3 * W * sizeof(uint32_t);                // at most 48 KiB
@@ -231,14 +236,7 @@ __global__ __launch_bounds__(64 * DL_WAVES) void draw_lists_weighted_kernel(uint
 extern "C" int cffm_draw_lists_weighted(uint64_t seed, int64_t list0, int32_t G, const int32_t* at, int32_t U, int32_t m,
                                         const uint32_t* cdf, const int32_t* cand, int32_t nf, int32_t* lists_out, int32_t* tuples_out,
                                         int32_t* target_out, void* stream) {
-    if (U < 1 || m < 1 || m > U - 1 || m > 1023 || G < 0 || list0 < 0 || list0 > INT64_MAX - (int64_t)G || nf < 0)
-        return CFFM_ERR_BAD_SHAPE;
-    const int64_t slots = (int64_t)G * (m + 1);                                    // < 2^41
-    if (slots >= (1ll << 31) || slots * (nf > 1 ? nf : 1) >= (1ll << 31)) return CFFM_ERR_BAD_SHAPE;
-    if ((cand == nullptr) != (tuples_out == nullptr)) return CFFM_ERR_BAD_SHAPE;
-    if (nf == 0 && cand) return CFFM_ERR_BAD_SHAPE;
-    if (!lists_out && !tuples_out) return CFFM_ERR_BAD_SHAPE;
-    if (!at || !target_out || !cdf) return CFFM_ERR_BAD_SHAPE;
+    if (U < 1 || !cdf || !draw_args_ok(list0, G, at, U, m, cand, nf, lists_out, tuples_out, target_out)) return CFFM_ERR_BAD_SHAPE;
     if (G == 0) return 0;
     const int W = (m + 1 + 3) & ~3;
     const size_t lds = (size_t)DL_WAVES * 2 * W * sizeof(uint32_t);                // at most 32 KiB

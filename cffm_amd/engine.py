@@ -324,6 +324,30 @@ class HipEngine(object):
             ids = ids.to(torch.int32).contiguous()
         return ids
 
+    def _cached(self, key, make):
+        """self._ws[key], made by make() on first use and kept."""
+        v = self._ws.get(key)
+        if v is None:
+            v = self._ws[key] = make()
+        return v
+
+    def _contexts(self, ctx):
+        """ctx as contiguous int32 [C, F]."""
+        ctx, F = self._ids(ctx), int(self.cfg.F)
+        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
+            raise ValueError('contexts must be [C, %d] feature ids' % F)
+        return ctx
+
+    def _fields(self, fields, who, block=None):
+        """`fields`, a column or several, as a list of 1 to F distinct ints of [0, F).  block: the piece size of an expand sweep,
+        refused in the same message where it is < 1."""
+        F = int(self.cfg.F)
+        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        nf = len(fields)
+        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields) or (block is not None and block < 1):
+            raise ValueError('%s: needs %s1 to %d distinct fields of [0, %d)' % (who, '' if block is None else 'block >= 1 and ', F, F))
+        return fields
+
     # ---- the two sess.run call shapes ---------------------------------------------------------------
     def predict(self, ids):
         """sess.run(self.out) (CFFM.py:596): int32 ids [B,F] on device -> fp32 [B] on device."""
@@ -374,32 +398,32 @@ class HipEngine(object):
         is swept in consecutive pieces of `block` rows (ragged last one): cffm_expand_candidates writes a piece's id rows,
         cffm_predict writes its outputs into the piece's slice of the result.  The ordinary workspace serves every piece, as in
         eval_sums; nothing synchronises."""
-        ctx, cand = self._ids(ctx), self._ids(cand.reshape(-1))
+        ctx, cand = self._contexts(ctx), self._ids(cand.reshape(-1))
         C, F = int(ctx.shape[0]), int(self.cfg.F)
-        N, block = int(cand.numel()), int(block)
-        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
-            raise ValueError('contexts must be [C, %d] feature ids' % F)
-        if N < 1 or block < 1 or not 0 <= int(field) < F:
+        N, block, field = int(cand.numel()), int(block), int(field)
+        if N < 1 or block < 1 or not 0 <= field < F:
             raise ValueError('score_candidates: needs a candidate, block >= 1 and 0 <= field < %d' % F)
-        scores = torch.empty((C, N), dtype=torch.float32, device=self.device)
-        key = ('cand_ids', block)
-        ids = self._ws.get(key)
-        if ids is None:
-            ids = torch.empty((block, F), dtype=torch.int32, device=self.device)
-            self._ws[key] = ids
+        expand = self.lib.cffm_expand_candidates
+        return self._piece_sweep(C, N, block, lambda s0, m, ids, st: expand(self._s, _ptr(ctx), C, field, _ptr(cand), N, s0, m, ids, st))
+
+    def _piece_sweep(self, n_ctx, N, block, expand):
+        """The sweep of score_candidates and score_candidate_tuples: the flattened [n_ctx * N] range in consecutive pieces of `block`
+        rows, expand(s0, m, ids, stream) - the caller's expand entry point - writing a piece's id rows into the one reused buffer and
+        cffm_predict its outputs into the piece's slice of the result -> fp32 [n_ctx, N] on the device."""
+        F = int(self.cfg.F)
+        scores = torch.empty((n_ctx, N), dtype=torch.float32, device=self.device)
+        ids = self._cached(('cand_ids', block), lambda: torch.empty((block, F), dtype=torch.int32, device=self.device))
         flat, st = scores.view(-1), self._stream()
-        for s0 in range(0, C * N, block):
-            m = min(block, C * N - s0)
+        for s0 in range(0, n_ctx * N, block):
+            m = min(block, n_ctx * N - s0)
             buf, _ = self.workspace(m)
-            hip.check(self.lib.cffm_expand_candidates(self._s, _ptr(ctx), C, int(field), _ptr(cand), N, s0, m, _ptr(ids), st))
+            hip.check(expand(s0, m, _ptr(ids), st))
             hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
         return scores
 
     def _cand_lists(self, ctx, cand, nf, who):
         """(ctx, cand, C, N, stride) of a candidate argument [N, nf] (one list, stride 0) or [C, N, nf] (a list per context)."""
-        ctx, F = self._ids(ctx), int(self.cfg.F)
-        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
-            raise ValueError('contexts must be [C, %d] feature ids' % F)
+        ctx = self._contexts(ctx)
         C = int(ctx.shape[0])
         if cand.dim() not in (2, 3) or int(cand.shape[-1]) != nf or (cand.dim() == 3 and int(cand.shape[0]) != C):
             raise ValueError('%s: candidates must be [N, %d] or [%d, N, %d]' % (who, nf, C, nf))
@@ -413,27 +437,14 @@ class HipEngine(object):
         for every context) or [C, N, nf] (a list per context) on the device, row (c, n) being context c with its ids at `fields`
         replaced together by candidate n -> fp32 [C, N] on the device.  Swept exactly as score_candidates is: one reused id buffer
         (cffm_expand_candidates_ex), cffm_predict into the piece's slice of the result, nothing synchronises."""
-        F, block = int(self.cfg.F), int(block)
-        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        block = int(block)
+        fields = self._fields(fields, 'score_candidate_tuples', block)
         nf = len(fields)
-        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields) or block < 1:
-            raise ValueError('score_candidate_tuples: needs block >= 1 and 1 to %d distinct fields of [0, %d)' % (F, F))
         ctx, cand, nctx, N, stride = self._cand_lists(ctx, cand, nf, 'score_candidate_tuples')
-        scores = torch.empty((nctx, N), dtype=torch.float32, device=self.device)
-        key = ('cand_ids', block)
-        ids = self._ws.get(key)
-        if ids is None:
-            ids = torch.empty((block, F), dtype=torch.int32, device=self.device)
-            self._ws[key] = ids
         host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
-        flat, st = scores.view(-1), self._stream()
-        for s0 in range(0, nctx * N, block):
-            m = min(block, nctx * N - s0)
-            buf, _ = self.workspace(m)
-            hip.check(self.lib.cffm_expand_candidates_ex(self._s, _ptr(ctx), nctx, C.addressof(host_fields), nf, _ptr(cand), stride, N,
-                                                         s0, m, _ptr(ids), st))
-            hip.check(self.lib.cffm_predict(self._s, self._t, _ptr(self.theta), _ptr(ids), m, _ptr(buf), _ptr(flat[s0:s0 + m]), st))
-        return scores
+        expand = self.lib.cffm_expand_candidates_ex
+        return self._piece_sweep(nctx, N, block, lambda s0, m, ids, st: expand(self._s, _ptr(ctx), nctx, C.addressof(host_fields), nf,
+                                                                               _ptr(cand), stride, N, s0, m, ids, st))
 
     def sweep_ok(self):
         """True where score_candidates_shared serves this engine's shape (cffm_sweep_ok, include/cffm_hip.h)."""
@@ -444,10 +455,8 @@ class HipEngine(object):
         same arguments, fp32 [C,N] on the device, equal to score_candidates to rounding (not bit for bit).  The per-context
         scratch is kept in self._ws; the ordinary workspace is not touched and nothing synchronises.  ValueError for a shape the
         sweep does not serve (sweep_ok())."""
-        ctx, cand = self._ids(ctx), self._ids(cand.reshape(-1))
+        ctx, cand = self._contexts(ctx), self._ids(cand.reshape(-1))
         F, N = int(self.cfg.F), int(cand.numel())
-        if ctx.dim() != 2 or int(ctx.shape[1]) != F:
-            raise ValueError('contexts must be [C, %d] feature ids' % F)
         if N < 1 or not 0 <= int(field) < F:
             raise ValueError('score_candidates_shared: needs a candidate and 0 <= field < %d' % F)
         C = int(ctx.shape[0])
@@ -502,11 +511,8 @@ class HipEngine(object):
         context) or [C, N, nf] (a list per context) on the device -> fp32 [C, N] on the device, equal to score_candidate_tuples to
         rounding.  The per-context scratch is kept in self._ws under a key of its own, grow-only; nothing synchronises.
         ValueError where (shape, nf) is not served (sweep_tuples_ok(nf))."""
-        F = int(self.cfg.F)
-        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
+        fields = self._fields(fields, 'score_candidate_tuples_shared')
         nf = len(fields)
-        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
-            raise ValueError('score_candidate_tuples_shared: needs 1 to %d distinct fields of [0, %d)' % (F, F))
         ctx, cand, nctx, N, stride = self._cand_lists(ctx, cand, nf, 'score_candidate_tuples_shared')
         if not self.sweep_tuples_ok(nf):
             raise ValueError('score_candidate_tuples_shared: the tuple sweep does not serve this shape for tuples of %d '
@@ -535,15 +541,15 @@ class HipEngine(object):
         for bit, NaN padded; count int32 [C] = min(k, N - skipped)).  skip: optional [C,N] mask, non-zero = leave out."""
         C, N, row_stride, skip, skip_stride = self._rank_args(scores, skip)
         k = int(k)
-        key = ('topk', C, N, k)
-        scratch = self._ws.get(key)
-        if scratch is None:
+        dev = self.device
+
+        def make():
             nbytes = int(self.lib.cffm_topk_scratch_bytes(C, N, k))
             if nbytes < 0:
                 raise ValueError('topk: needs N >= 1 and 1 <= k <= 1024 (N = %d, k = %d)' % (N, k))
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[key] = scratch
-        dev = self.device
+            return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+        scratch = self._cached(('topk', C, N, k), make)
         idx = torch.empty((C, k), dtype=torch.int32, device=dev)
         val = torch.empty((C, k), dtype=torch.float32, device=dev)
         count = torch.empty((C,), dtype=torch.int32, device=dev)
@@ -716,14 +722,18 @@ class HipEngine(object):
     def backward_dout(self, dout, B):
         """Backward from the caller's dL/dout (cffm_backward_dout): dout fp32 [B] on the device, used as given (no 1/B, no loss).
         The forward was forward(ids, y or None); the gradients are read as after backward(): export_grad(), row_grads(B)."""
+        self._backward_dout('backward_dout', self.lib.cffm_backward_dout, dout, B)
+
+    def _backward_dout(self, who, entry, dout, B):
+        """backward_dout and backward_dout_fused (who) around their entry points."""
         B = int(B)
         dout = dout.reshape(-1)
         if dout.dtype != torch.float32 or not dout.is_contiguous():
             dout = dout.to(torch.float32).contiguous()
         if int(dout.numel()) != B:
-            raise ValueError('backward_dout: dout must hold one value per example (%d, not %d)' % (B, int(dout.numel())))
+            raise ValueError('%s: dout must hold one value per example (%d, not %d)' % (who, B, int(dout.numel())))
         buf, _ = self.workspace(B)
-        hip.check(self.lib.cffm_backward_dout(self._s, _ptr(self.theta), _ptr(dout), B, _ptr(buf), _ptr(self.grad), self._stream()))
+        hip.check(entry(self._s, _ptr(self.theta), _ptr(dout), B, _ptr(buf), _ptr(self.grad), self._stream()))
 
     @staticmethod
     def _list_kind(kind):
@@ -756,47 +766,49 @@ class HipEngine(object):
             self._ws['list_loss'] = scratch
         return scratch
 
+    def _list_step_args(self, who, ctx, fields, cand, target, kind):
+        """What train_step_lists and train_step_lists_fused (who) open with: the optimizer, the loss, the kind, the fields and the
+        shapes checked -> (kind id, the fields as a host int32 array, nf, ctx, cand, target, G, Lg, stride).  Touches nothing."""
+        if self.cfg.optimizer != 'AdagradOptimizer':
+            raise ValueError('%s: the list step implements AdagradOptimizer, not %s' % (who, self.cfg.optimizer))
+        if self.cfg.loss_type == 'log_loss':
+            raise ValueError("%s: loss_type 'log_loss' leaves sigmoid(out) in the forward, not the score the list losses rank" % who)
+        kind_id = self._list_kind(kind)
+        fields = self._fields(fields, who)
+        nf = len(fields)
+        if cand.dim() != 3:
+            raise ValueError('%s: candidates must be [G, Lg, %d]' % (who, nf))
+        ctx, cand, G, Lg, stride = self._cand_lists(ctx, cand, nf, who)
+        target = self._ids(target.reshape(-1))
+        if Lg < 2 or int(target.numel()) != G:
+            raise ValueError('%s: needs lists of at least 2 candidates and one target per list' % who)
+        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        return kind_id, host_fields, nf, ctx, cand, target, G, Lg, stride
+
+    def _list_step_bufs(self, G, Lg):
+        """The buffers a list step of G lists of Lg keeps: (ids int32 [B, F] under ('list_ids', B); dout fp32 [B] and terms fp32 [G]
+        under ('list_out', G, Lg))."""
+        B, F, dev = G * Lg, int(self.cfg.F), self.device
+        ids = self._cached(('list_ids', B), lambda: torch.empty((B, F), dtype=torch.int32, device=dev))
+        dout, terms = self._cached(('list_out', G, Lg), lambda: (torch.empty(B, dtype=torch.float32, device=dev),
+                                                                  torch.empty(G, dtype=torch.float32, device=dev)))
+        return ids, dout, terms
+
     def train_step_lists(self, ctx, fields, cand, target, kind):
         """One Adagrad step on G ranked lists: ctx int32 [G, F] the contexts, cand int32 [G, Lg, nf] every list's candidate tuples
         for the columns `fields`, target int32 [G] the position of each list's positive, kind 'bpr' or 'softmax'.  The id rows
         (cffm_expand_candidates_ex), the forward without labels, the list loss on ws.out, the backward from its dL/dout
         (cffm_backward_dout: the stage launches), then the dense and the sparse Adagrad update.  Returns the loss as a device
         scalar (no host sync).  Adagrad only, and not loss_type='log_loss', whose forward leaves sigmoid(out) and not the score."""
-        if self.cfg.optimizer != 'AdagradOptimizer':
-            raise ValueError('train_step_lists: the list step implements AdagradOptimizer, not %s' % self.cfg.optimizer)
-        if self.cfg.loss_type == 'log_loss':
-            raise ValueError("train_step_lists: loss_type 'log_loss' leaves sigmoid(out) in the forward, not the score the list losses rank")
-        kind_id = self._list_kind(kind)
-        F = int(self.cfg.F)
-        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
-        nf = len(fields)
-        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
-            raise ValueError('train_step_lists: needs 1 to %d distinct fields of [0, %d)' % (F, F))
-        if cand.dim() != 3:
-            raise ValueError('train_step_lists: candidates must be [G, Lg, %d]' % nf)
-        ctx, cand, G, Lg, stride = self._cand_lists(ctx, cand, nf, 'train_step_lists')
-        target = self._ids(target.reshape(-1))
-        if Lg < 2 or int(target.numel()) != G:
-            raise ValueError('train_step_lists: needs lists of at least 2 candidates and one target per list')
+        kind_id, host_fields, nf, ctx, cand, target, G, Lg, stride = self._list_step_args('train_step_lists', ctx, fields, cand, target, kind)
         B = G * Lg
         if B == 0:
             return self.loss_buf
-        key = ('list_ids', B)
-        ids = self._ws.get(key)
-        if ids is None:
-            ids = torch.empty((B, F), dtype=torch.int32, device=self.device)
-            self._ws[key] = ids
-        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
+        ids, dout, terms = self._list_step_bufs(G, Lg)
         hip.check(self.lib.cffm_expand_candidates_ex(self._s, _ptr(ctx), G, C.addressof(host_fields), nf, _ptr(cand), stride, Lg,
                                                      0, B, _ptr(ids), self._stream()))
         self.forward(ids, None)
         buf, wl = self.workspace(B)
-        key = ('list_out', G, Lg)
-        out = self._ws.get(key)
-        if out is None:
-            out = (torch.empty(B, dtype=torch.float32, device=self.device), torch.empty(G, dtype=torch.float32, device=self.device))
-            self._ws[key] = out
-        dout, terms = out
         hip.check(self.lib.cffm_list_loss(kind_id, _ptr(buf) + int(wl.out), G, Lg, _ptr(target), _ptr(dout), _ptr(terms),
                                           _ptr(self.loss_buf), _ptr(self._list_scratch(G)), self._stream()))
         self.backward_dout(dout, B)
@@ -810,22 +822,28 @@ class HipEngine(object):
         the positive at[g] (int32 [G] on the device), m distinct others, the positive at a drawn place; cffm_amd.spec.draw_lists
         is the specification.  cand: int32 [U, nf] on the device, or None for the indices alone.  Returns (tuples int32
         [G, m + 1, nf] = cand[lists] or None, lists int32 [G, m + 1], target int32 [G]) on the device.  Nothing synchronises."""
+        return self._draw('draw_lists', self.lib.cffm_draw_lists, seed, list0, at, U, m, cand)
+
+    def _draw(self, who, entry, seed, list0, at, U, m, cand, cdf=None):
+        """draw_lists and draw_lists_weighted (who) around their entry points; the weighted one takes the cdf words after m.  m within
+        [1, min(U - 1, 1023)] leaves no U below 2 through."""
         seed, list0, U, m = int(seed) & 0xffffffffffffffff, int(list0), int(U), int(m)
         at = self._ids(at.reshape(-1))
         G, nf = int(at.numel()), 0
         if cand is not None:
             if cand.dim() != 2 or int(cand.shape[0]) != U or int(cand.shape[1]) < 1:
-                raise ValueError('draw_lists: cand must be [U = %d, nf >= 1]' % U)
+                raise ValueError('%s: cand must be [U = %d, nf >= 1]' % (who, U))
             cand, nf = self._ids(cand), int(cand.shape[1])
-        if U < 2 or not 1 <= m <= min(U - 1, 1023):
-            raise ValueError('draw_lists: needs 1 <= m <= min(U - 1, 1023) (U = %d, m = %d)' % (U, m))
+        if not 1 <= m <= min(U - 1, 1023):
+            raise ValueError('%s: needs 1 <= m <= min(U - 1, 1023) (U = %d, m = %d)' % (who, U, m))
         dev = self.device
         lists = torch.empty((G, m + 1), dtype=torch.int32, device=dev)
         target = torch.empty(G, dtype=torch.int32, device=dev)
         tuples = None if cand is None else torch.empty((G, m + 1, nf), dtype=torch.int32, device=dev)
         if G:
-            hip.check(self.lib.cffm_draw_lists(seed, list0, G, _ptr(at), U, m, _ptr(cand), nf, _ptr(lists), _ptr(tuples), _ptr(target),
-                                               self._stream()))
+            weights = () if cdf is None else (_ptr(cdf),)
+            hip.check(entry(seed, list0, G, _ptr(at), U, m, *weights, _ptr(cand), nf, _ptr(lists), _ptr(tuples), _ptr(target),
+                            self._stream()))
         return tuples, lists, target
 
     def draw_lists_weighted(self, seed, list0, at, cdf, m, cand=None):
@@ -835,26 +853,9 @@ class HipEngine(object):
         int32 [U, nf] on the device, or None for the indices alone.  Returns (tuples int32 [G, m + 1, nf] = cand[lists] or None,
         lists int32 [G, m + 1], target int32 [G]) on the device; a list that did not collect m negatives within the word cap (too
         skewed weights) and one whose at[g] is outside [0, U) come back as -1 / zeros / target -1.  Nothing synchronises."""
-        seed, list0, m = int(seed) & 0xffffffffffffffff, int(list0), int(m)
-        at = self._ids(at.reshape(-1))
         if cdf.dim() != 1 or cdf.dtype not in (torch.int32, torch.uint32) or cdf.device != at.device:
             raise ValueError('draw_lists_weighted: cdf must be an int32 / uint32 vector on the device (spec.weight_cdf)')
-        cdf = cdf.contiguous()
-        G, U, nf = int(at.numel()), int(cdf.numel()), 0
-        if cand is not None:
-            if cand.dim() != 2 or int(cand.shape[0]) != U or int(cand.shape[1]) < 1:
-                raise ValueError('draw_lists_weighted: cand must be [U = %d, nf >= 1]' % U)
-            cand, nf = self._ids(cand), int(cand.shape[1])
-        if U < 1 or not 1 <= m <= min(U - 1, 1023):
-            raise ValueError('draw_lists_weighted: needs 1 <= m <= min(U - 1, 1023) (U = %d, m = %d)' % (U, m))
-        dev = self.device
-        lists = torch.empty((G, m + 1), dtype=torch.int32, device=dev)
-        target = torch.empty(G, dtype=torch.int32, device=dev)
-        tuples = None if cand is None else torch.empty((G, m + 1, nf), dtype=torch.int32, device=dev)
-        if G:
-            hip.check(self.lib.cffm_draw_lists_weighted(seed, list0, G, _ptr(at), U, m, _ptr(cdf), _ptr(cand), nf, _ptr(lists),
-                                                        _ptr(tuples), _ptr(target), self._stream()))
-        return tuples, lists, target
+        return self._draw('draw_lists_weighted', self.lib.cffm_draw_lists_weighted, seed, list0, at, cdf.numel(), m, cand, cdf.contiguous())
 
     def list_step_ok(self, B):
         """True where train_step_lists_fused serves B = G * Lg rows of this engine's shape (cffm_list_step_ok; host only)."""
@@ -862,14 +863,7 @@ class HipEngine(object):
 
     def backward_dout_fused(self, dout, B):
         """backward_dout on the launches backward() takes where its fused top runs (cffm_backward_dout_fused); raises where it does not."""
-        B = int(B)
-        dout = dout.reshape(-1)
-        if dout.dtype != torch.float32 or not dout.is_contiguous():
-            dout = dout.to(torch.float32).contiguous()
-        if int(dout.numel()) != B:
-            raise ValueError('backward_dout_fused: dout must hold one value per example (%d, not %d)' % (B, int(dout.numel())))
-        buf, _ = self.workspace(B)
-        hip.check(self.lib.cffm_backward_dout_fused(self._s, _ptr(self.theta), _ptr(dout), B, _ptr(buf), _ptr(self.grad), self._stream()))
+        self._backward_dout('backward_dout_fused', self.lib.cffm_backward_dout_fused, dout, B)
 
     def train_step_lists_fused(self, ctx, fields, cand, target, kind):
         """train_step_lists through the fused top of the backward (cffm_train_step_lists, one library call): the id rows, the forward
@@ -880,42 +874,16 @@ class HipEngine(object):
         checks, return value and buffers (('list_ids', B), ('list_out', G, Lg), loss_buf) as train_step_lists.  Served where
         list_step_ok(G * Lg); elsewhere a ValueError names the shape and B, and nothing has been touched."""
         who = 'train_step_lists_fused'
-        if self.cfg.optimizer != 'AdagradOptimizer':
-            raise ValueError('%s: the list step implements AdagradOptimizer, not %s' % (who, self.cfg.optimizer))
-        if self.cfg.loss_type == 'log_loss':
-            raise ValueError("%s: loss_type 'log_loss' leaves sigmoid(out) in the forward, not the score the list losses rank" % who)
-        kind_id = self._list_kind(kind)
-        F = int(self.cfg.F)
-        fields = [int(f) for f in (fields if hasattr(fields, '__len__') else [fields])]
-        nf = len(fields)
-        if not 1 <= nf <= F or len(set(fields)) != nf or not all(0 <= f < F for f in fields):
-            raise ValueError('%s: needs 1 to %d distinct fields of [0, %d)' % (who, F, F))
-        if cand.dim() != 3:
-            raise ValueError('%s: candidates must be [G, Lg, %d]' % (who, nf))
-        ctx, cand, G, Lg, stride = self._cand_lists(ctx, cand, nf, who)
-        target = self._ids(target.reshape(-1))
-        if Lg < 2 or int(target.numel()) != G:
-            raise ValueError('%s: needs lists of at least 2 candidates and one target per list' % who)
+        kind_id, host_fields, nf, ctx, cand, target, G, Lg, stride = self._list_step_args(who, ctx, fields, cand, target, kind)
         B = G * Lg
         if B == 0:
             return self.loss_buf
         if not self.list_step_ok(B):
             raise ValueError('%s: the fused list step does not serve F=%d K=%d D=%d %s, lamda_bilinear=%g at B = %d x %d = %d rows '
-                             '(list_step_ok); train_step_lists does' % (who, F, self.cfg.K, self.cfg.D, self.cfg.activation,
+                             '(list_step_ok); train_step_lists does' % (who, int(self.cfg.F), self.cfg.K, self.cfg.D, self.cfg.activation,
                                                                        self.cfg.lamda_bilinear, G, Lg, B))
-        key = ('list_ids', B)
-        ids = self._ws.get(key)
-        if ids is None:
-            ids = torch.empty((B, F), dtype=torch.int32, device=self.device)
-            self._ws[key] = ids
+        ids, dout, terms = self._list_step_bufs(G, Lg)
         buf, _ = self.workspace(B)
-        key = ('list_out', G, Lg)
-        out = self._ws.get(key)
-        if out is None:
-            out = (torch.empty(B, dtype=torch.float32, device=self.device), torch.empty(G, dtype=torch.float32, device=self.device))
-            self._ws[key] = out
-        dout, terms = out
-        host_fields = (C.c_int32 * nf)(*fields)                  # read before the launch, like the shape
         hip.check(self.lib.cffm_train_step_lists(self._s, self._t, self._ta, _ptr(self.theta), _ptr(self.theta_acc), _ptr(self.grad),
                                                  _ptr(ctx), G, C.addressof(host_fields), nf, _ptr(cand), stride, Lg, _ptr(target),
                                                  kind_id, _ptr(ids), _ptr(dout), _ptr(terms), _ptr(buf), _ptr(self.loss_buf),
