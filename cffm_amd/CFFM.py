@@ -854,7 +854,7 @@ class CFFM(object):
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
     def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host',
-                      negative_weights=None, negative_power=0.75):
+                      negative_weights=None, negative_power=0.75, hard_pool=None):
         """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
         its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
         the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
@@ -882,11 +882,23 @@ class CFFM(object):
         replacement by rejection, cffm_amd.spec.draw_lists_weighted the specification.  These lists differ from the uniform device
         lists even for equal weights.  The BPR and softmax losses are used as they are: no logQ correction of the sampled softmax
         is applied.  Fewer than negatives + 1 positive weights, and weights so skewed that a list does not collect its negatives
-        under the word cap (checked after each epoch's draw, before its first step), raise ValueError.  Out of scope: hard-negative
-        (model-scored) draws, the multi-GPU list step, other optimizers."""
+        under the word cap (checked after each epoch's draw, before its first step), raise ValueError.
+        hard_pool (with sampler='device' only; a ValueError names both otherwise): None (default) trains on the drawn lists,
+        everything as without the keyword.  hard_pool=p, negatives < p <= min(U - 1, 1023) over the U distinct tuples, is dynamic
+        negative sampling: per epoch every positive draws a pool of p negatives instead of `negatives` (list e * P + j of the draw
+        above at m = p, the weighted draw under negative_weights, whose checks then speak of lists of p + 1), and every step first
+        scores its pools with the parameters as they stand before it (HipEngine.score_candidate_tuples, bit for bit predict) and
+        trains on the `negatives` best-scored members of each pool, hardest first, in the order of HipEngine.topk, around the
+        positive at a place drawn from (seed, e * P + j) (HipEngine.pick_hard; cffm_amd.spec.pick_hard is the specification) -
+        three launches ahead of the unchanged list step at the frappe shape, and the same lists under every lists_per_step only as
+        far as the parameters that score them are the same.  The losses are used as they are: no correction of the softmax for the
+        selection is applied.  Out of scope: the multi-GPU list step, other optimizers."""
         import torch
         from . import hip
         self._check_sampler('train_ranking()', sampler, negatives)
+        if hard_pool is not None and sampler != 'device':
+            raise ValueError("train_ranking(): hard_pool needs sampler='device', the only sampler that draws the pool (not sampler=%r)"
+                             % (sampler,))
         if step not in ('stages', 'fused', 'auto'):
             raise ValueError("train_ranking(): step must be 'stages', 'fused' or 'auto', not %r" % (step,))
         if self.optimizer_type != 'AdagradOptimizer':
@@ -917,9 +929,16 @@ class CFFM(object):
         per = int(self.batch_size // (m + 1) if lists_per_step is None else lists_per_step)
         if per < 1:
             raise ValueError('train_ranking(): lists_per_step must be >= 1 (batch_size %d holds no list of %d)' % (self.batch_size, m + 1))
+        drawn = m                                                              # negatives per drawn list: the pool under hard_pool
+        if hard_pool is not None:
+            drawn = int(hard_pool)
+            if not m < drawn <= min(U - 1, 1023):
+                raise ValueError('train_ranking(): hard_pool must be in (negatives, min(U - 1, 1023)] = (%d, %d]: a pool larger than '
+                                 'the negatives picked from it, drawn from the %d distinct tuples without the target, not %d'
+                                 % (m, min(U - 1, 1023), U, drawn))
         at_dev = self._positions(cand, ctx[:, colt].to(torch.int32))
         at = at_dev.cpu().numpy() if sampler == 'host' else None
-        cdf = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, m, U,
+        cdf = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, drawn, U,
                                  lambda: self._distinct([data], colt, counts=True))
         means = []
         for epoch in range(epochs):
@@ -929,7 +948,7 @@ class CFFM(object):
             if sampler == 'device':
                 permt = torch.from_numpy(perm).to(eng.device)
                 rows = ctx[permt]
-                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, m, cand, cdf, 'train_ranking()')
+                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, drawn, cand, cdf, 'train_ranking()')
             else:
                 lists, place = self._draw_lists(rng, at[perm], U, m)
                 rows = ctx[torch.from_numpy(perm).to(eng.device)]
@@ -940,7 +959,12 @@ class CFFM(object):
                 r1 = min(P, r0 + per)
                 fused = step == 'fused' or (step == 'auto' and eng.list_step_ok((r1 - r0) * (m + 1)))
                 run = eng.train_step_lists_fused if fused else eng.train_step_lists
-                step_loss = run(rows[r0:r1], cols, tuples[r0:r1].contiguous(), target[r0:r1], loss)
+                if hard_pool is None:
+                    step_tuples, step_target = tuples[r0:r1].contiguous(), target[r0:r1]
+                else:                                                          # the pool scored as the parameters stand now
+                    scores = eng.score_candidate_tuples(rows[r0:r1], cols, tuples[r0:r1])
+                    step_tuples, _, step_target = eng.pick_hard(seed, epoch * P + r0, scores, target[r0:r1], m, tuples=tuples[r0:r1])
+                step_loss = run(rows[r0:r1], cols, step_tuples, step_target, loss)
                 total += step_loss.double() * (r1 - r0)
             means.append(float(total.cpu()[0]) / P)
             self._info('Ranking epoch %d [%.1f s] %s loss over %d lists of %d: %.6f' % (epoch + 1, time() - t1, loss, P, m + 1, means[-1]))

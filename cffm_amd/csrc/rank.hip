@@ -17,6 +17,7 @@
 // the first level; 4096 rows of 4082 candidates are one workgroup per row.  Every barrier sits in a loop whose trip count is a kernel
 // argument (never under a per-lane condition).
 #include "internal.hpp"
+#include "rank_key.hpp"
 
 #define RANK_CHUNK 8192
 #define RANK_THREADS 1024
@@ -24,15 +25,6 @@
 #define RANK_COUNT_THREADS 256
 
 namespace {
-
-__device__ __forceinline__ unsigned long long rank_key64(unsigned u, unsigned pos) {
-    unsigned k32 = 0;                                             // NaN: below -inf (whose key32 is 0x007fffff)
-    if ((u & 0x7fffffffu) <= 0x7f800000u) {
-        if (u == 0x80000000u) u = 0;                              // -0 == +0
-        k32 = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((unsigned long long)k32 << 32) | (unsigned long long)(0xffffffffu - pos);
-}
 
 // one step of a bitonic network over 2 * pairs keys in LDS: keys i and i + stride, larger first where (i & size) == 0
 __device__ __forceinline__ void rank_cmpex(unsigned long long* lk, int tid, int pairs, int size, int stride) {

@@ -857,6 +857,48 @@ class HipEngine(object):
             raise ValueError('draw_lists_weighted: cdf must be an int32 / uint32 vector on the device (spec.weight_cdf)')
         return self._draw('draw_lists_weighted', self.lib.cffm_draw_lists_weighted, seed, list0, at, cdf.numel(), m, cand, cdf.contiguous())
 
+    def pick_hard(self, seed, list0, scores, target_pool, m, lists=None, tuples=None):
+        """cffm_pick_hard, the select step of dynamic negative sampling: from the scored pool of each of G lists (id list0 + g) the m
+        best-scored negatives, hardest first, in the order of topk (score descending, -0 == +0, NaN last, ties by position), around
+        the positive at a place drawn from (seed, id, m); cffm_amd.spec.pick_hard is the specification.  scores: fp32 [G, Lp] on the
+        device, the last dimension contiguous, the row stride passed through (elements beyond Lp are never read); target_pool: int32
+        [G], the pool position of each list's positive (the target of the draw that made the pool); lists: int32 [G, Lp] pool
+        indices and / or tuples: int32 [G, Lp, nf] pool tuples, one of them at least.  Returns (tuples int32 [G, m + 1, nf] or None,
+        lists int32 [G, m + 1] or None, target int32 [G]) on the device; a list whose target_pool lies outside [0, Lp) comes back as
+        zeros / -1 / target -1.  Nothing synchronises."""
+        who = 'pick_hard'
+        seed, list0, m = int(seed) & 0xffffffffffffffff, int(list0), int(m)
+        if scores.dim() != 2 or scores.dtype != torch.float32 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+            raise ValueError('%s: scores must be fp32 [G, Lp] with contiguous rows' % who)
+        G, Lp = int(scores.shape[0]), int(scores.shape[1])
+        row_stride = int(scores.stride(0)) if G > 1 else Lp
+        if row_stride < Lp:
+            raise ValueError('%s: the rows of scores overlap (row stride %d < Lp = %d)' % (who, row_stride, Lp))
+        if not 2 <= Lp <= 1024 or not 1 <= m <= Lp - 1:
+            raise ValueError('%s: needs 2 <= Lp <= 1024 and 1 <= m <= Lp - 1 (Lp = %d, m = %d)' % (who, Lp, m))
+        target_pool = self._ids(target_pool.reshape(-1))
+        if int(target_pool.numel()) != G:
+            raise ValueError('%s: one target_pool per row of the scores (%d, not %d)' % (who, G, int(target_pool.numel())))
+        if lists is None and tuples is None:
+            raise ValueError('%s: needs the pool as lists [G, Lp], as tuples [G, Lp, nf], or both' % who)
+        nf = 0
+        if lists is not None:
+            if tuple(lists.shape) != (G, Lp):
+                raise ValueError('%s: lists must be [G = %d, Lp = %d]' % (who, G, Lp))
+            lists = self._ids(lists)
+        if tuples is not None:
+            if tuples.dim() != 3 or tuple(tuples.shape[:2]) != (G, Lp) or int(tuples.shape[2]) < 1:
+                raise ValueError('%s: tuples must be [G = %d, Lp = %d, nf >= 1]' % (who, G, Lp))
+            tuples, nf = self._ids(tuples), int(tuples.shape[2])
+        dev = self.device
+        lists_out = None if lists is None else torch.empty((G, m + 1), dtype=torch.int32, device=dev)
+        tuples_out = None if tuples is None else torch.empty((G, m + 1, nf), dtype=torch.int32, device=dev)
+        target = torch.empty(G, dtype=torch.int32, device=dev)
+        if G:
+            hip.check(self.lib.cffm_pick_hard(seed, list0, G, _ptr(scores), row_stride, Lp, _ptr(target_pool), m, _ptr(lists), _ptr(tuples),
+                                              nf, _ptr(lists_out), _ptr(tuples_out), _ptr(target), self._stream()))
+        return tuples_out, lists_out, target
+
     def list_step_ok(self, B):
         """True where train_step_lists_fused serves B = G * Lg rows of this engine's shape (cffm_list_step_ok; host only)."""
         return bool(self.lib.cffm_list_step_ok(self._s, int(B)))

@@ -372,3 +372,50 @@ def draw_lists_weighted(seed, list0, at, cdf, m):
                 break
             todo, n = todo[~full], min(cap, 2 * n)
     return lists, place
+
+
+# ---- hard negatives picked from a scored pool BY LIST ID: the numpy twin (and the specification) of cffm_pick_hard ----------------
+HARD_TAG = 4                 # fourth counter word of the pick's place (the table draw: 0 and 1, the list draws: 2 and 3)
+HARD_MAX_LP = 1024           # pools of at most 1024 positions, the positive among them
+
+
+def pick_hard(seed, list0, scores, target_pool, m):
+    """The select step of dynamic negative sampling over G scored pools of Lp positions: scores float32 [G, Lp], target_pool [G] the
+    pool position of each list's positive (list g has the id list0 + g).  Returns (sel int64 [G, m + 1], place int64 [G]): sel holds
+    pool positions - the positive at place[g], around it the m best-scored of the Lp - 1 other positions, hardest first, the
+    negative of rank r at slot r + (r >= place) - and a list whose target lies outside [0, Lp) has a row of -1 and place -1.
+    The order is that of include/cffm_hip.h in prose: score descending as IEEE floats with -0 == +0, NaN below everything (-inf
+    included), equal scores (NaN among themselves too) to the smaller position.  Integer work on the float bits and one lexsort,
+    not the 64-bit key the kernel compares.  place = (w * (m + 1)) >> 32, w output word 0 of philox4x32_10(counter = (id lo, id hi,
+    0, HARD_TAG), key = (seed lo, seed hi)): a function of (seed, id, m) alone."""
+    s = np.asarray(scores)
+    if s.ndim != 2 or s.dtype != np.float32:
+        raise ValueError('pick_hard: scores must be float32 [G, Lp]')
+    t = np.asarray(target_pool).astype(np.int64).reshape(-1)
+    G, Lp, m = int(s.shape[0]), int(s.shape[1]), int(m)
+    if not 2 <= Lp <= HARD_MAX_LP or not 1 <= m <= Lp - 1 or t.shape[0] != G:
+        raise ValueError('pick_hard: needs 2 <= Lp <= %d, 1 <= m <= Lp - 1 and one target per list' % HARD_MAX_LP)
+    seed = int(seed) & 0xffffffffffffffff
+    sel = np.full((G, m + 1), -1, dtype=np.int64)
+    place = np.full(G, -1, dtype=np.int64)
+    live = np.nonzero((t >= 0) & (t < Lp))[0]
+    if live.shape[0] == 0:
+        return sel, place
+    b = s[live].view(np.uint32)
+    nan = (b & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    neg = (b >> np.uint32(31)).astype(np.int64)
+    mag = (b & np.uint32(0x7fffffff)).astype(np.int64)
+    val = np.where(nan, 0, np.where(neg == 1, -mag, mag))        # the floats' own order on their bits; -0 and +0 both give 0
+    pos = np.broadcast_to(np.arange(Lp, dtype=np.int64), val.shape)
+    own = pos == t[live][:, None]
+    # lexsort: the LAST key is the primary one.  The positive last of all; then NaN last; then score descending; then position
+    order = np.lexsort((pos, -val, nan, own), axis=-1)
+    ids = (np.uint64(int(list0)) + live.astype(np.uint64)).reshape(-1)
+    w = philox4x32_10((ids & np.uint64(0xffffffff), ids >> np.uint64(32), np.uint64(0), np.uint64(HARD_TAG)),
+                      (seed & 0xffffffff, seed >> 32))[0].astype(np.uint64)
+    pl = ((w * np.uint64(m + 1)) >> np.uint64(32)).astype(np.int64)
+    slot = np.arange(m + 1, dtype=np.int64)[None, :]
+    src = np.clip(slot - (slot > pl[:, None]), 0, m - 1)         # the rank held by a slot other than the place
+    sel[live] = np.where(slot == pl[:, None], t[live][:, None], np.take_along_axis(order[:, :m], src, axis=1))
+    place[live] = pl
+    return sel, place

@@ -630,6 +630,38 @@ int cffm_draw_lists_weighted(uint64_t seed, int64_t list0, int32_t G, const int3
                              const uint32_t *cdf, const int32_t *cand, int32_t nf,
                              int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
 
+/* ---- hard negatives picked from a scored pool, by list id ---------------------------------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes;
+ * cffm_draw_lists, cffm_draw_lists_weighted and cffm_topk keep their bits.
+ *
+ * cffm_pick_hard: from the scored pool of each of G lists, the m best-scored negatives around the positive at a drawn place - the
+ * select step of dynamic negative sampling.  List g has the id list0 + g.  scores: device fp32, scores[g * row_stride + p] the score
+ * of pool position p < Lp (the index is computed in 64 bits; elements at or beyond Lp are never read).  target_pool: device int32
+ * [G], t = target_pool[g] the pool position of the list's positive - the target_out of the draw that made the pool.  The negatives
+ * are the Lp - 1 positions other than t, ordered by THE ORDER of the candidate ranking above on (score, pool position): score
+ * descending, -0 == +0, NaN below -inf, equal scores to the smaller position (the 64-bit key defined there).  The m best are the
+ * list's negatives, hardest first.  The positive's place in the list is place = (w * (m + 1)) >> 32, w output word 0 of
+ * Philox4x32-10 at counter (id lo, id hi, 0, 4), key seed - the table draw holds 0 and 1 in that last counter word, the list draws
+ * 2 and 3 - and the negative of rank r goes to slot r + (r >= place).  With sel[g][slot] the chosen pool position:
+ *   lists_out   int32 [G][m + 1], lists_out[g][slot] = pool_lists[g][sel[g][slot]] with pool_lists device int32 [G][Lp]; NULL
+ *               together with pool_lists
+ *   tuples_out  int32 [G][m + 1][nf], tuples_out[g][slot][a] = pool_tuples[g][sel[g][slot]][a] with pool_tuples device int32
+ *               [G][Lp][nf]: the cand operand, at cand_ctx_stride = (m + 1) * nf, of cffm_expand_candidates_ex and
+ *               cffm_train_step_lists.  NULL together with pool_tuples (nf is then not used beyond the size check)
+ *   target_out  int32 [G] = place, the target of cffm_list_loss and cffm_rank_of
+ * A list whose t lies outside [0, Lp) (the draws mark a list without a target and an incomplete list so) gets target_out = -1, an
+ * index row of -1 and a tuple row of zeros; nothing of it is read, and nothing is read out of range.  A function of (seed, list id,
+ * scores) alone: the place of (seed, id, m), the chosen positions of the scores.  cffm_amd/spec.py pick_hard() is the
+ * specification; the match is exact.  Writes exactly G * (m + 1) indices, G * (m + 1) * nf tuple words and G targets: one launch,
+ * no scratch, no atomics, the same bits on every call and under every split of the lists into calls.
+ * CFFM_ERR_BAD_SHAPE, before any launch, for: Lp < 2; Lp > 1024; m < 1; m > Lp - 1; G < 0; list0 < 0; list0 + G beyond int64;
+ * row_stride < Lp; G * Lp * max(nf, 1) >= 2^31; nf < 0; nf == 0 with a non-NULL pool_tuples or tuples_out; exactly one of
+ * pool_tuples / tuples_out NULL; exactly one of pool_lists / lists_out NULL; both lists_out and tuples_out NULL; a NULL scores,
+ * target_pool or target_out.  G == 0 (with arguments that pass) returns 0 without a launch. */
+int cffm_pick_hard(uint64_t seed, int64_t list0, int32_t G, const float *scores, int64_t row_stride, int32_t Lp,
+                   const int32_t *target_pool, int32_t m, const int32_t *pool_lists, const int32_t *pool_tuples, int32_t nf,
+                   int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
