@@ -161,13 +161,20 @@ class CFFM(object):
         dev = int(os.environ.get('LOCAL_RANK', torch.cuda.current_device() if torch.cuda.is_available() else 0))
         if torch.cuda.is_available():
             torch.cuda.set_device(dev)
-        if os.environ.get('CFFM_TABLES', 'replicated') == 'sharded':
-            return self._build_sharded(dev)
-        self.engine = self._make_engine(dev)
+        sharded = os.environ.get('CFFM_TABLES', 'replicated') == 'sharded'
+        if sharded:
+            self._build_sharded(dev)                   # the engine over this rank's rows and, from two ranks up, its step
+        else:
+            self.engine = self._make_engine(dev)
         if self.pretrain_flag > 0:
             self.load(self.save_file)
-        self._setup_dist()
+        if not sharded:
+            self._setup_dist()
         return self.engine
+
+    def _refuse_uneven_batch(self):
+        if self.batch_size % self.world:
+            raise ValueError('--batch_size %d is not a multiple of the %d ranks' % (self.batch_size, self.world))
 
     engine_factory = None          # tests plug a CPU stand-in (the oracle) in here; the product path is HipEngine
 
@@ -217,8 +224,7 @@ class CFFM(object):
                 raise ValueError('CFFM_TABLES=sharded: --loss_type hybrid runs on one GPU only')
             if self.loss_type == 'square_loss' and self.lamda_bilinear > 0:
                 raise ValueError('CFFM_TABLES=sharded: --lamda > 0 (a regulariser over whole tables) runs on one GPU only')
-            if self.batch_size % self.world:
-                raise ValueError('--batch_size %d is not a multiple of the %d ranks' % (self.batch_size, self.world))
+            self._refuse_uneven_batch()
             if self.features_M < self.world:
                 raise ValueError('CFFM_TABLES=sharded: %d features over %d ranks leaves a rank without rows' % (self.features_M, self.world))
         cfg = copy.copy(self.config)
@@ -231,9 +237,6 @@ class CFFM(object):
                                     table_rows=(self.rank, self.world), device='cuda:%d' % dev)
         if self.world > 1:
             self._sh = ShardedStep(self.engine, M_global=self.features_M)
-        if self.pretrain_flag > 0:
-            self.load(self.save_file)
-        return self.engine
 
     def _setup_dist(self):
         """One process per GPU under torch.distributed.run (RANK / WORLD_SIZE / LOCAL_RANK in the environment), or a process
@@ -247,8 +250,7 @@ class CFFM(object):
         tables = os.environ.get('CFFM_TABLES', 'replicated')
         if tables != 'replicated':                     # 'sharded' went through _build_sharded
             raise ValueError("CFFM_TABLES=%r: the accepted values are 'replicated' (default) and 'sharded'" % (tables,))
-        if self.batch_size % self.world:
-            raise ValueError('--batch_size %d is not a multiple of the %d ranks' % (self.batch_size, self.world))
+        self._refuse_uneven_batch()
         from .dist import DataParallelStep
         self._dp = DataParallelStep(self.engine)
 
@@ -287,11 +289,28 @@ class CFFM(object):
         return arrays[0] if arrays is not None else data['X']
 
     # ---- training loop (CFFM.py:157-228) -------------------------------------------------------------
+    def _train_step(self):
+        """The step of train(), decided once per call: step(ids, y, starts, i) trains on batch i of an epoch's block starts, under
+        a process group on this rank's slice of it."""
+        per = self.batch_size // self.world
+
+        def part(t, starts, i):
+            lo = int(starts[i]) + self.rank * per
+            return t[lo:lo + per]
+
+        if self._sh is not None:
+            # this rank's slice of the batch, and of the NEXT one: its routing plan (and the read of the per-owner counts) is
+            # issued before this step's kernels
+            return lambda ids, y, starts, i: self._sh.train_step(part(ids, starts, i), part(y, starts, i),
+                                                                 next_ids=part(ids, starts, i + 1) if i + 1 < len(starts) else None)
+        run = self._dp.train_step if self._dp is not None else self.engine.train_step
+        return lambda ids, y, starts, i: run(part(ids, starts, i), part(y, starts, i))
+
     def train(self, data):
         import torch
         if self.engine is None:
             self.build_graph()
-        eng = self.engine
+        step = self._train_step()
         self._train_split = data.Train_data            # recommend() / evaluate_ranking() draw their default candidates from it
         self.calculate_parameters()
         if self.verbose > 0:
@@ -327,23 +346,8 @@ class CFFM(object):
                     dist.broadcast(st, src=0)
                     starts = st.cpu().numpy()
                 self.batch_starts.append(np.asarray(starts, dtype=np.int64))
-                per = self.batch_size // self.world
-                for i, start in enumerate(starts):
-                    start = int(start)
-                    if self._sh is not None:
-                        # this rank's slice of the batch, and of the NEXT one: its routing plan (and the read of the
-                        # per-owner counts) is issued before this step's kernels
-                        lo = start + self.rank * per
-                        nxt = None
-                        if i + 1 < len(starts):
-                            nlo = int(starts[i + 1]) + self.rank * per
-                            nxt = ids[nlo:nlo + per]
-                        self._sh.train_step(ids[lo:lo + per], y[lo:lo + per], next_ids=nxt)
-                    elif self._dp is not None:
-                        lo = start + self.rank * per
-                        self._dp.train_step(ids[lo:lo + per], y[lo:lo + per])
-                    else:
-                        eng.train_step(ids[start:start + self.batch_size], y[start:start + self.batch_size])
+                for i in range(len(starts)):
+                    step(ids, y, starts, i)
                 if torch.cuda.is_available():
                     torch.cuda.synchronize()
                 t2 = time()
@@ -395,18 +399,15 @@ class CFFM(object):
         num_example = int(ids.shape[0])
         if num_example == 0:
             raise ValueError('evaluate() needs at least one example')
+        # the forward is per example: every rank sweeps its contiguous share of the rows, the three sums are added up
+        r0, r1, _, block, n_blocks = self._share(num_example)
         if self._sh is not None:
             # row-sharded tables: a forward needs the owners of its rows, so every rank runs the SAME number of rounds of
             # collectives - what the largest share (rank 0's) needs; a rank whose rows have run out joins with empty blocks
-            r0, r1, block, n_blocks = self._share(num_example)
-            sums = self._all_reduce_sum(self._sh.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block, n_blocks))
-        elif self.world > 1:
-            # the forward is per example: every rank sweeps its contiguous share of the rows, the three sums are added up
-            r0, r1, _, _ = self._share(num_example)
-            sums = self._all_reduce_sum(self.engine.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block=max(int(self.batch_size), 8192)))
+            sums = self._sh.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block, n_blocks)
         else:
-            sums = self.engine.eval_sums(ids, y, lo, hi, block=max(int(self.batch_size), 8192))
-        ss_res, sy, syy = (float(v) for v in sums.cpu().numpy())
+            sums = self.engine.eval_sums(ids[r0:r1], y[r0:r1], lo, hi, block=block)
+        ss_res, sy, syy = (float(v) for v in self._all_reduce_sum(sums).cpu().numpy())
         if not math.isfinite(ss_res):
             # np.maximum/np.minimum propagate NaN and sklearn's mean_squared_error raises on it (CFFM.py:607-612): a
             # diverged model must not come back with a finite metric
@@ -417,11 +418,11 @@ class CFFM(object):
         return RMSE, R2
 
     def _share(self, num_example):
-        """This rank's contiguous share [r0, r1) of a split's rows, the block size of the sweep and the number of blocks the
-        LARGEST share takes (shares only get shorter with the rank, so that is rank 0's)."""
+        """This rank's contiguous share [r0, r1) of a split's rows, the size of the LARGEST share (shares only get shorter with the
+        rank, so that is rank 0's), the block size of the sweep and the number of blocks the largest share takes."""
         r0, r1, share = self._row_share(num_example)
         block = max(int(self.batch_size), 8192)
-        return r0, r1, block, -(-share // block)
+        return r0, r1, share, block, -(-share // block)
 
     def _row_share(self, n):
         """This rank's contiguous share [r0, r1) of n rows and the size of the largest share; all of them without a process group."""
@@ -432,12 +433,11 @@ class CFFM(object):
         """Raw (unclipped) predictions of a split as a host float64 array, in the split's current order."""
         import torch
         ids, _, _ = self._device_split(data)
+        n = int(ids.shape[0])
+        r0, r1, share, block, n_blocks = self._share(n)
         if self._sh is not None:
             # every rank predicts its share (in matched rounds, as evaluate() does) and gets the whole split back
             import torch.distributed as dist
-            n = int(ids.shape[0])
-            r0, r1, block, n_blocks = self._share(n)
-            share = -(-n // self.world)
             mine = None
             for b in range(n_blocks):
                 s0, s1 = min(r0 + b * block, r1), min(r0 + (b + 1) * block, r1)
@@ -450,8 +450,7 @@ class CFFM(object):
             full = mine.new_empty(share * self.world)
             dist.all_gather_into_tensor(full, mine)
             return full[:n].cpu().numpy().astype(np.float64)
-        block = max(int(self.batch_size), 8192)
-        outs = [self.engine.predict(ids[s:s + block]) for s in range(0, ids.shape[0], block)]
+        outs = [self.engine.predict(ids[s:s + block]) for s in range(0, n, block)]
         return torch.cat(outs).cpu().numpy().astype(np.float64) if outs else np.zeros((0,))
 
     # ---- candidate ranking: what a trained recommender is asked for ------------------------------------------------------
@@ -1018,13 +1017,12 @@ class CFFM(object):
     # A plain dict of tensors and scalars: loads with torch.load(weights_only=True), no pickled code.
     def save(self, save_file):
         import torch
+        from .dist import save_sharded, tensors_of as t
         if self._sh is not None:                       # row-sharded: one file per rank (cffm_amd.dist.save_sharded)
             import torch.distributed as dist
-            from .dist import save_sharded
             save_sharded(self.engine, save_file, self.rank, self.world, opt_step=int(getattr(self.engine, 'opt_step', 0)))
             dist.barrier()                             # on return every shard is on disk (a restore reads shard 0 on every rank)
             return
-        t = lambda d: None if d is None else {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in d.items()}
         cfg = {k: (v if isinstance(v, (int, float, str)) else float(v)) for k, v in self.config.__dict__.items()}
         torch.save({'format': 2, 'config': cfg, 'params': t(self.engine.export_params()),
                     'accumulators': t(self.engine.export_accumulators()),
@@ -1033,12 +1031,11 @@ class CFFM(object):
 
     def load(self, save_file):
         import torch
+        from .dist import arrays_of as n, load_sharded
         if self._sh is not None:                       # the shards a run at THIS world size wrote; dist.merge_shards for world 1
-            from .dist import load_sharded
             self.engine.opt_step = load_sharded(self.engine, save_file, self.rank, self.world)
             return
         blob = torch.load(save_file + '.pt', weights_only=True)
-        n = lambda d: None if d is None else {k: (v.numpy() if hasattr(v, 'numpy') else np.asarray(v)) for k, v in d.items()}
         saved = blob.get('config', {})
         for k in ('M', 'F', 'K', 'D'):
             if k in saved and int(saved[k]) != int(getattr(self.config, k)):

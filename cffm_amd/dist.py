@@ -1,7 +1,7 @@
 """Multi-GPU training step: batch-sharded data parallel, one process per GPU, torch.distributed
 (backend "nccl" = RCCL over xGMI on ROCm; "gloo" in the CPU tests).
 
-The reference is single-device only (no distributed code anywhere in /root/reference), so this is new
+The reference is single-device only (it has no distributed code anywhere), so this is new
 design.  Examples are independent in the forward pass; the only couplings are the loss normaliser (a mean
 over the GLOBAL batch, CFFM.py:493) and the parameter gradients:
 
@@ -17,7 +17,7 @@ over the GLOBAL batch, CFFM.py:493) and the parameter gradients:
        replicated (default while the tables fit one GPU):  ONE all-gather of packed (id, row gradients); every rank then
            runs the same sorted segment-sum + update (Adagrad, SGD or Momentum) over the Bg*F rows, so the replicas stay
            bit-identical;
-       row-sharded (``ShardedTables``, vocabulary beyond one GPU's HBM): ids all-to-all to the owner
+       row-sharded (``ShardedStep``, vocabulary beyond one GPU's HBM): the distinct ids of the batch all-to-all to the owner
            (row r lives on rank r % G), owners gather and send rows back, row gradients return by all-to-all and
            the owner applies the duplicates-summed-first update locally.
 
@@ -27,6 +27,8 @@ apply_sparse + the tensors named below); the CPU tests plug the oracle in there,
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from .spec import TABLES
 
 
 def sync_replicas(compute, group=None, tables=True, src=0):
@@ -180,71 +182,6 @@ class DataParallelStep(object):
         return len(stale)
 
 
-def shard_of(ids, world):
-    """Owner rank and local row of every id under the r -> (r % G, r // G) row sharding."""
-    return ids % world, ids // world
-
-
-def route_ids(ids_flat, world):
-    """Sort the lookups of one rank by owner: returns (perm, counts) with ids_flat[perm] grouped by owner
-    rank in rank order and counts[g] lookups going to rank g.  Pure index arithmetic (no collective)."""
-    owner = ids_flat % world
-    perm = torch.argsort(owner, stable=True)
-    counts = torch.bincount(owner, minlength=world)
-    return perm, counts
-
-
-class ShardedTables(object):
-    """Row-sharded embedding tables: row r of every table lives on rank r % G at local index r // G.
-    ``lookup`` and ``push_grads`` are the two exchange steps of a training step; both are all-to-all over
-    the lookups of the batch, so their volume scales with B*F, not with the vocabulary."""
-
-    def __init__(self, local_tables, group=None):
-        # local_tables: dict name -> tensor [M_local, dim] holding rows rank, rank+G, rank+2G, ...
-        self.t = local_tables
-        self.group = group
-        self.world = dist.get_world_size(group)
-        self.rank = dist.get_rank(group)
-        self._route = None
-
-    def _exchange_counts(self, counts):
-        recv = torch.empty_like(counts)
-        dist.all_to_all_single(recv, counts, group=self.group)
-        return recv
-
-    def lookup(self, ids_flat):
-        """ids_flat int64/int32 [n] global ids -> dict name -> [n, dim] rows, in the caller's order."""
-        world = self.world
-        perm, send_counts = route_ids(ids_flat.long(), world)
-        recv_counts = self._exchange_counts(send_counts)
-        sc, rc = send_counts.tolist(), recv_counts.tolist()
-        req = torch.empty(sum(rc), dtype=torch.long, device=ids_flat.device)
-        dist.all_to_all_single(req, ids_flat.long()[perm].contiguous(), rc, sc, group=self.group)
-        local_rows = req // world
-        out = {}
-        for name, tab in self.t.items():
-            rows = tab[local_rows].contiguous()
-            back = torch.empty((ids_flat.numel(),) + tuple(tab.shape[1:]), dtype=tab.dtype, device=tab.device)
-            dist.all_to_all_single(back, rows, sc, rc, group=self.group)
-            res = torch.empty_like(back)
-            res[perm] = back
-            out[name] = res
-        self._route = (perm, sc, rc, local_rows)
-        return out
-
-    def push_grads(self, row_grads):
-        """row_grads: dict name -> [n, dim] gradients in the order of the last lookup.  Returns
-        (local_rows [m], dict name -> [m, dim]) : what this rank's owner-side sparse update consumes."""
-        perm, sc, rc, local_rows = self._route
-        out = {}
-        for name, g in row_grads.items():
-            send = g[perm].contiguous()
-            recv = torch.empty((sum(rc),) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
-            dist.all_to_all_single(recv, send, rc, sc, group=self.group)
-            out[name] = recv
-        return local_rows, out
-
-
 def local_rows_count(M, rank, world):
     """Rows of an M-row table owned by ``rank`` under r -> (r % G, r // G)."""
     return (M - rank + world - 1) // world
@@ -253,7 +190,7 @@ def local_rows_count(M, rank, world):
 def shard_params(params, rank, world):
     """Global parameter dict -> this rank's view: the three tables keep rows rank, rank+G, ...; the rest is replicated."""
     out = dict(params)
-    for k in ('inner_embeddings', 'outer_embeddings', 'feature_bias'):
+    for k in TABLES:
         out[k] = params[k][rank::world].copy()
     return out
 
@@ -379,6 +316,25 @@ class ShardedStep(object):
             p.counts_host, p.event = both, None
         return p
 
+    def _lookup(self, plan):
+        """The exchange of a plan: ask the owners for the DISTINCT rows, by their local row index; the answer is one packed record
+        per row.  Returns (the records [#distinct, packed width] in distinct-id order, send counts, receive counts)."""
+        sc, rc = plan.counts()
+        asked = self._a2a(plan.send_rows[:sum(sc)], sc, rc)
+        return self._a2a(self.c.gather_packed(asked), rc, sc), sc, rc
+
+    def _forward(self, got, plan, y):
+        """The forward of the plan's rows on the received records; True where it consumed them where they lie."""
+        c = self.c
+        if got.shape[0] > 0 and hasattr(c, 'packed_ok') and c.packed_ok():
+            # wide shapes: the records are consumed where they lie (slot i reads record pos[i] in the kernel that fetches it, the
+            # product-path gather of the replicated tables with a record stride): nothing is staged into ws.Ei / ws.Eo
+            c.forward_packed(got, plan.pos, y, plan.B)
+            return True
+        c.stage_packed(got, plan.pos, plan.B)                            # duplicates re-expanded: ws.Ei / ws.Eo / ws.fb
+        c.forward_staged(y, plan.B)
+        return False
+
     def train_step(self, ids, y, next_ids=None):
         c = self.c
         plan, self._ahead = self._ahead, None
@@ -389,24 +345,15 @@ class ShardedStep(object):
         if next_ids is not None:
             self._ahead = self.plan(next_ids)         # before this step's kernels: its counts are on the host long before needed
         B, Bg = plan.B, plan.B * self.world
-        sc, rc = plan.counts()
-        u = sum(sc)
-        # 1) ask the owners for the DISTINCT rows, by their local row index; the answer is one packed record per row
-        asked = self._a2a(plan.send_rows[:u], sc, rc)
-        got = self._a2a(c.gather_packed(asked), rc, sc)                  # [u, K+D+4] in distinct-id order
-        if u > 0 and hasattr(c, 'packed_ok') and c.packed_ok():
-            # wide shapes: the records are consumed where they lie (slot i reads record pos[i] in the kernel that fetches it, the
-            # product-path gather of the replicated tables with a record stride): nothing is staged into ws.Ei / ws.Eo
-            c.forward_packed(got, plan.pos, y, B)
+        got, sc, rc = self._lookup(plan)
+        # local backward without 1/L, gradients keyed by the owner's local row, duplicates summed before they travel
+        if self._forward(got, plan, y):
             grad = c.backward_unscaled_packed(got, plan.pos, y, B, Bg)
         else:
-            c.stage_packed(got, plan.pos, B)                             # duplicates re-expanded: ws.Ei / ws.Eo / ws.fb
-            c.forward_staged(y, B)
-            # 2) local backward without 1/L, gradients keyed by the owner's local row, duplicates summed before they travel
             grad = c.backward_unscaled(plan.local_ids, y, B, Bg, pack=False)[0]
         dist.all_reduce(grad, op=dist.ReduceOp.SUM, group=self.group)
         rows = c.pack_rows_dedup(plan.local_ids, plan.order, plan.uniq, B)
-        recv = self._a2a(rows[:u], sc, rc)
+        recv = self._a2a(rows[:sum(sc)], sc, rc)
         return c.dp_apply(grad, recv, Bg)
 
     # ---- forward only: what evaluate() / predict_split() of a row-sharded model run ------------------------------------------
@@ -415,21 +362,12 @@ class ShardedStep(object):
         all-to-all back -> the forward on the received records (in place on the wide shapes, staged otherwise).  A collective
         call: every rank of the group calls it the same number of times, a rank with nothing to predict with an EMPTY batch
         ([0,F]) - it still answers the lookups of the others.  The plan prefetched for the next train step is left alone."""
-        c = self.c
         plan = self.plan(ids)
-        B = plan.B
-        sc, rc = plan.counts()
-        u = sum(sc)
-        asked = self._a2a(plan.send_rows[:u], sc, rc)
-        got = self._a2a(c.gather_packed(asked), rc, sc)                  # [u, K+D+4] in distinct-id order
-        if B == 0:
+        got = self._lookup(plan)[0]
+        if plan.B == 0:
             return got.new_empty(0)
-        if hasattr(c, 'packed_ok') and c.packed_ok():
-            c.forward_packed(got, plan.pos, None, B)
-        else:
-            c.stage_packed(got, plan.pos, B)
-            c.forward_staged(None, B)
-        return c.predictions(B)
+        self._forward(got, plan, None)
+        return self.c.predictions(plan.B)
 
     def eval_sums(self, ids, y, lo, hi, block, n_blocks):
         """evaluate()'s sweep over this rank's rows: blocks of ``block`` rows through predict() and the clip + float64 metric sums
@@ -452,19 +390,29 @@ class ShardedStep(object):
 # ---- checkpoint of a row-sharded model ("sharded-table aware") ----------------------------------------------
 # Every rank writes its own shard of the three tables and of their optimizer slots (local rows rank, rank + G, ...); the
 # replicated dense parameters (identical on every rank) are written by rank 0 only.  Plain tensors: weights_only loads.
+def tensors_of(d, keys=None):
+    """A dict of arrays as the dict of tensors a checkpoint holds: every entry, or those of `keys` that d has; None stays None."""
+    if d is None:
+        return None
+    return {k: torch.from_numpy(np.ascontiguousarray(d[k])) for k in (d if keys is None else keys) if k in d}
+
+
+def arrays_of(d):
+    """The reverse: a checkpoint's dict of tensors as arrays (None stays None)."""
+    return None if d is None else {k: (v.numpy() if hasattr(v, 'numpy') else np.asarray(v)) for k, v in d.items()}
+
+
 def save_sharded(engine, path, rank, world, opt_step=0):
-    t = lambda d, keys: {k: torch.from_numpy(d[k].copy()) for k in keys}
-    tables = ('inner_embeddings', 'outer_embeddings', 'feature_bias')
     params, accs = engine.export_params(), engine.export_accumulators()
     second = engine.export_second_moments() if hasattr(engine, 'export_second_moments') else None
     blob = {'format': 2, 'rank': int(rank), 'world': int(world), 'local_rows': int(params['inner_embeddings'].shape[0]),
-            'tables': t(params, tables), 'table_slots': t(accs, tables),
-            'table_slots2': t(second, tables) if second is not None else None, 'opt_step': int(opt_step)}
+            'tables': tensors_of(params, TABLES), 'table_slots': tensors_of(accs, TABLES),
+            'table_slots2': tensors_of(second, TABLES), 'opt_step': int(opt_step)}
     if rank == 0:
-        dense = [k for k in params if k not in tables]
-        blob['dense'] = t(params, dense)
-        blob['dense_slots'] = t(accs, [k for k in dense if k in accs])
-        blob['dense_slots2'] = t(second, [k for k in dense if k in second]) if second is not None else None
+        dense = [k for k in params if k not in TABLES]
+        blob['dense'] = tensors_of(params, dense)
+        blob['dense_slots'] = tensors_of(accs, dense)
+        blob['dense_slots2'] = tensors_of(second, dense)
     torch.save(blob, '%s.shard%d-of-%d.pt' % (path, rank, world))
 
 
@@ -475,14 +423,13 @@ def load_sharded(engine, path, rank, world):
     if own['world'] != world or own['rank'] != rank:
         raise ValueError('shard file written for rank %d of %d' % (own['rank'], own['world']))
     root = own if rank == 0 else torch.load('%s.shard0-of-%d.pt' % (path, world), weights_only=True)
-    n = lambda d: {k: v.numpy() for k, v in d.items()}
-    params, accs = n(root['dense']), n(root['dense_slots'])
-    params.update(n(own['tables']))
-    accs.update(n(own['table_slots']))
+    params, accs = arrays_of(root['dense']), arrays_of(root['dense_slots'])
+    params.update(arrays_of(own['tables']))
+    accs.update(arrays_of(own['table_slots']))
     second = None
     if own.get('table_slots2') is not None:
-        second = n(root['dense_slots2'])
-        second.update(n(own['table_slots2']))
+        second = arrays_of(root['dense_slots2'])
+        second.update(arrays_of(own['table_slots2']))
     if params['inner_embeddings'].shape[0] != engine.cfg.M:
         raise ValueError('shard has %d local rows, this engine owns %d' % (params['inner_embeddings'].shape[0], engine.cfg.M))
     for k, v in engine.export_params().items():          # untrained reference variables kept on the host only

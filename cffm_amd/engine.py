@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .spec import ADAGRAD_INIT_ACC, CFFMConfig, init_params, param_shapes
+from .spec import ADAGRAD_INIT_ACC, TABLES, CFFMConfig, init_params, param_shapes
 
 # theta member -> reference variable name (reshaped flat, row-major)
 _THETA_MEMBERS = [
@@ -88,6 +88,8 @@ class HipEngine(object):
         self._eval_scratch = None
         self._flat_dirty = False                      # dense-image route: the image is zero on entry, zero on exit
         self._host_only = {}
+        self.row_grad_width = 1 + cfg.K + cfg.D + 1   # floats of a row-gradient record (id bits | dEi | dEo | dfb)
+        self.packed_width = cfg.K + cfg.D + 4         # floats of a packed row (inner | outer | bias, 0, 0, 0)
         # params == 'device': the three tables are drawn ON the GPU with the reference's distributions (N(0, 0.1),
         # N(0, 0.01), exact zeros - CFFM.py:257-277); for vocabularies where a host-side draw + copy of M*(K+D) floats
         # would dominate start-up (10 M features: 5 GB).  Dense parameters still come from init_params(seed); the device
@@ -105,29 +107,24 @@ class HipEngine(object):
             params = init_params(cfg, seed=seed, tables=not device_tables)
         n = int(self.tl.n)
         dev = self.device
-        self.theta = torch.zeros(n, dtype=torch.float32, device=dev)
         # optimizer slots (CFFM.py:517-529): Adagrad accumulators start at 1e-8, Momentum accumulators / Adam m, v at 0
-        acc0 = ADAGRAD_INIT_ACC if cfg.optimizer == 'AdagradOptimizer' else 0.0
-        self.acc0 = acc0
-        self.theta_acc = torch.full((n,), acc0, dtype=torch.float32, device=dev)
+        self.acc0 = acc0 = ADAGRAD_INIT_ACC if cfg.optimizer == 'AdagradOptimizer' else 0.0
+        # ONE table of the state: a (theta, inner, outer, fbias) set of the parameters, one of the first slots and, for Adam, one of the
+        # second moments.  The named attributes alias these tensors; load, export and replicated_state walk self._sets.
+        sizes = ((n,), (cfg.M, cfg.K), (cfg.M, cfg.D), (cfg.M,))
+        self._sets = [tuple(torch.full(sz, fill, dtype=torch.float32, device=dev) for sz in sizes)
+                      for fill in (0.0, acc0) + ((0.0,) if cfg.optimizer == 'AdamOptimizer' else ())]
+        tabs = [hip.Tables(*(t.data_ptr() for t in st[1:])) for st in self._sets]
+        self.theta, self.inner, self.outer, self.fbias = self._sets[0]
+        self.theta_acc, self.inner_acc, self.outer_acc, self.fbias_acc = self._sets[1]
+        self.tables, self.tables_acc = tabs[:2]
+        self.theta_acc2 = self.tables_acc2 = None
+        if len(self._sets) > 2:                                      # second moment
+            self.theta_acc2, self.inner_acc2, self.outer_acc2, self.fbias_acc2 = self._sets[2]
+            self.tables_acc2 = tabs[2]
         self.grad = torch.zeros(n + 4, dtype=torch.float32, device=dev)[:n]      # +4: loss-sum slot of the DP step
         self._grad_full = self.grad._base if self.grad._base is not None else self.grad
-        M = cfg.M
-        self.inner = torch.zeros((M, cfg.K), dtype=torch.float32, device=dev)
-        self.outer = torch.zeros((M, cfg.D), dtype=torch.float32, device=dev)
-        self.fbias = torch.zeros((M,), dtype=torch.float32, device=dev)
-        self.inner_acc = torch.full_like(self.inner, acc0)
-        self.outer_acc = torch.full_like(self.outer, acc0)
-        self.fbias_acc = torch.full_like(self.fbias, acc0)
         self.opt_step = 0
-        self.theta_acc2 = self.tables_acc2 = None
-        if cfg.optimizer == 'AdamOptimizer':                         # second moment
-            self.theta_acc2 = torch.zeros_like(self.theta_acc)
-            self.inner_acc2, self.outer_acc2 = torch.zeros_like(self.inner), torch.zeros_like(self.outer)
-            self.fbias_acc2 = torch.zeros_like(self.fbias)
-            self.tables_acc2 = hip.Tables(self.inner_acc2.data_ptr(), self.outer_acc2.data_ptr(), self.fbias_acc2.data_ptr())
-        self.tables = hip.Tables(self.inner.data_ptr(), self.outer.data_ptr(), self.fbias.data_ptr())
-        self.tables_acc = hip.Tables(self.inner_acc.data_ptr(), self.outer_acc.data_ptr(), self.fbias_acc.data_ptr())
         self.loss_buf = torch.zeros(1, dtype=torch.float32, device=dev)
         # addresses of the small host structs (kept alive by self)
         self._s = C.addressof(self.shape)
@@ -152,14 +149,7 @@ class HipEngine(object):
         """Tensors that must be bit-identical on every rank of a multi-GPU job (cffm_amd.dist.sync_replicas): the dense
         parameters and their optimizer slots; with ``tables`` (data-parallel mode) also the three tables and their slots.
         In row-sharded mode the tables are per-rank shards and stay out."""
-        out = [self.theta, self.theta_acc]
-        if self.theta_acc2 is not None:
-            out.append(self.theta_acc2)
-        if tables:
-            out += [self.inner, self.outer, self.fbias, self.inner_acc, self.outer_acc, self.fbias_acc]
-            if self.theta_acc2 is not None:
-                out += [self.inner_acc2, self.outer_acc2, self.fbias_acc2]
-        return out
+        return [st[0] for st in self._sets] + ([t for st in self._sets for t in st[1:]] if tables else [])
 
     # ---- named parameters <-> device buffers -------------------------------------------------------
     def _members(self):
@@ -194,79 +184,63 @@ class HipEngine(object):
 
     def load_params(self, params, accs=None, accs2=None):
         shapes = param_shapes(self.cfg)
-        host = np.zeros(int(self.tl.n), dtype=np.float32)
-        for off, name in self._members():
-            v = self._pack(name, params[name])
-            host[off:off + v.size] = v
-        self.theta.copy_(torch.from_numpy(host))
-        if 'inner_embeddings' in params:                  # absent: tables initialised on the device (params='device')
-            self.inner.copy_(torch.from_numpy(np.asarray(params['inner_embeddings'], dtype=np.float32)))
-            self.outer.copy_(torch.from_numpy(np.asarray(params['outer_embeddings'], dtype=np.float32)))
-            self.fbias.copy_(torch.from_numpy(np.asarray(params['feature_bias'], dtype=np.float32).reshape(-1)))
-        trained = set(n for _, n in self._members()) | {'inner_embeddings', 'outer_embeddings', 'feature_bias'}
+        self._load_set(0, params, 'inner_embeddings' in params)  # absent: tables initialised on the device (params='device')
+        trained = set(n for _, n in self._members()) | set(TABLES)
         self._host_only = {k: np.array(params[k], dtype=np.float32) for k in shapes if k not in trained and k in params}
         if accs is not None:
-            ha = np.full(int(self.tl.n), self.acc0, dtype=np.float32)
-            for off, name in self._members():
-                v = self._pack(name, accs[name])
-                if name.startswith('outer_layer_conv_'):
-                    v = np.where(v == 0, np.float32(self.acc0), v)     # pads keep the initial accumulator
-                ha[off:off + v.size] = v
-            self.theta_acc.copy_(torch.from_numpy(ha))
-            self.inner_acc.copy_(torch.from_numpy(np.asarray(accs['inner_embeddings'], dtype=np.float32)))
-            self.outer_acc.copy_(torch.from_numpy(np.asarray(accs['outer_embeddings'], dtype=np.float32)))
-            self.fbias_acc.copy_(torch.from_numpy(np.asarray(accs['feature_bias'], dtype=np.float32).reshape(-1)))
+            self._load_set(1, accs)
         if accs2 is not None and self.theta_acc2 is not None:
-            h2 = np.zeros(int(self.tl.n), dtype=np.float32)
-            for off, name in self._members():
-                v = self._pack(name, accs2[name])
-                h2[off:off + v.size] = v
-            self.theta_acc2.copy_(torch.from_numpy(h2))
-            self.inner_acc2.copy_(torch.from_numpy(np.asarray(accs2['inner_embeddings'], dtype=np.float32)))
-            self.outer_acc2.copy_(torch.from_numpy(np.asarray(accs2['outer_embeddings'], dtype=np.float32)))
-            self.fbias_acc2.copy_(torch.from_numpy(np.asarray(accs2['feature_bias'], dtype=np.float32).reshape(-1)))
+            self._load_set(2, accs2)
 
-    def _export(self, flat, inner, outer, fbias):
+    def _load_set(self, s, values, tables=True):
+        """Set s of self._sets from reference variables by name: the dense members packed into the flat image, then the three tables.
+        What no member covers keeps the set's initial value: 0, and in the first slots (s == 1) the initial accumulator acc0."""
+        flat, fill = self._sets[s][0], np.float32(self.acc0 if s == 1 else 0.0)
+        host = np.full(int(self.tl.n), fill, dtype=np.float32)
+        for off, name in self._members():
+            v = self._pack(name, values[name])
+            if s == 1 and name.startswith('outer_layer_conv_'):
+                v = np.where(v == 0, fill, v)                          # pads keep the initial accumulator
+            host[off:off + v.size] = v
+        flat.copy_(torch.from_numpy(host))
+        if tables:
+            for t, k in zip(self._sets[s][1:], TABLES):
+                v = np.asarray(values[k], dtype=np.float32)
+                t.copy_(torch.from_numpy(v.reshape(-1) if t.dim() == 1 else v))
+
+    def _export(self, flat, *tables):
+        """The flat image by reference variable name; with (inner, outer, fbias) also the three tables."""
         shapes = param_shapes(self.cfg)
         host = flat.detach().cpu().numpy()
         out = {}
         for off, name in self._members():
             out[name] = self._unpack(name, host, off, shapes[name])
-        out['inner_embeddings'] = inner.detach().cpu().numpy().copy()
-        out['outer_embeddings'] = outer.detach().cpu().numpy().copy()
-        out['feature_bias'] = fbias.detach().cpu().numpy().reshape(-1, 1).copy()
+        for k, t in zip(TABLES, tables):
+            v = t.detach().cpu().numpy()
+            out[k] = (v.reshape(-1, 1) if k == 'feature_bias' else v).copy()
         return out
 
     def export_params_dense(self):
         """Every variable except the three tables (for vocabularies where a host copy of the tables is not wanted)."""
-        z = torch.zeros(1, device=self.device)
-        out = self._export(self.theta, z, z, z)
-        for k in ('inner_embeddings', 'outer_embeddings', 'feature_bias'):
-            out.pop(k)
+        out = self._export(self.theta)
         out.update({k: v.copy() for k, v in self._host_only.items()})
         return out
 
     def export_params(self):
-        out = self._export(self.theta, self.inner, self.outer, self.fbias)
+        out = self._export(*self._sets[0])
         out.update({k: v.copy() for k, v in self._host_only.items()})
         return out
 
     def export_accumulators(self):
-        return self._export(self.theta_acc, self.inner_acc, self.outer_acc, self.fbias_acc)
+        return self._export(*self._sets[1])
 
     def export_second_moments(self):
         """Adam's v slots (None for the other optimizers)."""
-        if self.theta_acc2 is None:
-            return None
-        return self._export(self.theta_acc2, self.inner_acc2, self.outer_acc2, self.fbias_acc2)
+        return self._export(*self._sets[2]) if self.theta_acc2 is not None else None
 
     def export_grad(self):
         """Dense-parameter gradients of the last backward, by reference variable name."""
-        z = torch.zeros(1, device=self.device)
-        g = self._export(self.grad, z, z, z)
-        for k in ('inner_embeddings', 'outer_embeddings', 'feature_bias'):
-            g.pop(k)
-        return g
+        return self._export(self.grad)
 
     # ---- workspace ---------------------------------------------------------------------------------
     def workspace(self, B):
@@ -324,6 +298,14 @@ class HipEngine(object):
             ids = ids.to(torch.int32).contiguous()
         return ids
 
+    @staticmethod
+    def _labels(y):
+        """y as contiguous float32 [B]."""
+        y = y.reshape(-1)
+        if y.dtype != torch.float32 or not y.is_contiguous():
+            y = y.to(torch.float32).contiguous()
+        return y
+
     def _cached(self, key, make):
         """self._ws[key], made by make() on first use and kept."""
         v = self._ws.get(key)
@@ -365,17 +347,12 @@ class HipEngine(object):
         """evaluate()'s sweep (CFFM.py:590-614) entirely on the device: ordered blocks of rows through cffm_predict, the
         clip to [lo, hi] and the float64 sums the two metrics need (cffm_eval_sums).  Returns a float64 device tensor
         [sum (y - p)^2, sum y, sum y^2]; nothing is copied to the host and nothing synchronises here."""
-        ids = self._ids(ids)
-        y = y.reshape(-1)
+        ids, y = self._ids(ids), self._labels(y)
         n = int(ids.shape[0])
-        if self._eval_scratch is None:
-            self._eval_scratch = torch.empty(int(self.lib.cffm_eval_scratch_bytes()), dtype=torch.uint8, device=self.device)
         sums = torch.zeros(3, dtype=torch.float64, device=self.device)
         for s0 in range(0, n, block):
             m = min(block, n - s0)
-            out = self.predict(ids[s0:s0 + m])
-            hip.check(self.lib.cffm_eval_sums(_ptr(out), _ptr(y[s0:s0 + m]), m, float(lo), float(hi),
-                                              _ptr(self._eval_scratch), _ptr(sums), self._stream()))
+            self.eval_sums_add(self.predict(ids[s0:s0 + m]), y[s0:s0 + m], lo, hi, sums)
         return sums
 
     def eval_sums_add(self, pred, y, lo, hi, sums):
@@ -384,11 +361,8 @@ class HipEngine(object):
         m = int(pred.shape[0])
         if self._eval_scratch is None:
             self._eval_scratch = torch.empty(int(self.lib.cffm_eval_scratch_bytes()), dtype=torch.uint8, device=self.device)
-        y = y.reshape(-1)
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.to(torch.float32).contiguous()
-        hip.check(self.lib.cffm_eval_sums(_ptr(pred), _ptr(y), m, float(lo), float(hi), _ptr(self._eval_scratch), _ptr(sums),
-                                          self._stream()))
+        hip.check(self.lib.cffm_eval_sums(_ptr(pred), _ptr(self._labels(y)), m, float(lo), float(hi), _ptr(self._eval_scratch),
+                                          _ptr(sums), self._stream()))
         return sums
 
     # ---- candidate ranking (csrc/rank.hip): scores of (context, candidate) pairs, top-k and rank-of-target on the device ----
@@ -577,10 +551,7 @@ class HipEngine(object):
     def train_step(self, ids, y):
         """sess.run((self.loss, self.optimizer)) (CFFM.py:200).  Returns the loss as a device scalar
         (no host sync)."""
-        ids = self._ids(ids)
-        y = y.reshape(-1)
-        if y.dtype != torch.float32 or not y.is_contiguous():
-            y = y.to(torch.float32).contiguous()
+        ids, y = self._ids(ids), self._labels(y)
         B = ids.shape[0]
         if B == 0:                                   # nothing to learn from: parameters and slots stay as they are
             return self.loss_buf
@@ -625,15 +596,15 @@ class HipEngine(object):
         to write them into; the call overwrites all of it, whatever it held)."""
         ids = self._ids(ids)
         n = int(ids.numel())
-        key = ('plan', n)
-        scratch = self._ws.get(key)
-        if scratch is None:
+        dev = self.device
+
+        def make():
             nbytes = int(self.lib.cffm_shard_plan_scratch_bytes(n))
             if nbytes < 0:
                 raise RuntimeError('cffm_shard_plan_scratch_bytes failed')
-            scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[key] = scratch
-        dev = self.device
+            return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+        scratch = self._cached(('plan', n), make)
         local_ids = torch.empty(ids.shape, dtype=torch.int32, device=dev)
         order, uniq, pos, send_rows = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
         if counts is None:
@@ -644,18 +615,17 @@ class HipEngine(object):
         return local_ids, order, uniq, pos, send_rows, counts
 
     def gather_packed(self, local_rows):
-        """Owner side of a row-sharded lookup: int32 [m] local rows -> [m, K+D+4] packed records
+        """Owner side of a row-sharded lookup: int32 [m] local rows -> [m, packed_width] packed records
         (inner | outer | bias, 0, 0, 0), ONE kernel (cffm_gather_packed)."""
         m = int(local_rows.numel())
-        Wp = self.cfg.K + self.cfg.D + 4
-        out = torch.empty((m, Wp), dtype=torch.float32, device=self.device)
+        out = torch.empty((m, self.packed_width), dtype=torch.float32, device=self.device)
         if m:
             rows = self._ids(local_rows.reshape(-1))
             hip.check(self.lib.cffm_gather_packed(self._s, self._t, _ptr(rows), m, _ptr(out), self._stream()))
         return out
 
     def stage_packed(self, packed, pos, B):
-        """Requester side: slot i of the batch takes record pos[i] of packed [n_records, K+D+4] -> ws.Ei / ws.Eo / ws.fb."""
+        """Requester side: slot i of the batch takes record pos[i] of packed [n_records, packed_width] -> ws.Ei / ws.Eo / ws.fb."""
         buf, _ = self.workspace(B)
         pos = self._ids(pos.reshape(-1)) if pos is not None else None
         hip.check(self.lib.cffm_stage_packed(self._s, _ptr(packed), _ptr(pos), int(packed.shape[0]), int(B), _ptr(buf),
@@ -666,7 +636,7 @@ class HipEngine(object):
         return bool(self.lib.cffm_gather_inner_fwd_ok(self._s))
 
     def forward_packed(self, packed, pos, y, B):
-        """Forward half of a row-sharded step straight from the received records [n_records, K+D+4]: slot i reads record pos[i]
+        """Forward half of a row-sharded step straight from the received records [n_records, packed_width]: slot i reads record pos[i]
         in the kernel that fetches it; ws.Ei / ws.Eo are never written (cffm_forward_packed)."""
         buf, _ = self.workspace(B)
         pos = self._ids(pos.reshape(-1))
@@ -699,18 +669,17 @@ class HipEngine(object):
         self.forward_staged(y, B)
 
     def pack_rows_dedup(self, local_ids, order, uniq, B):
-        """Row-gradient message with the duplicates of an id summed first (cffm_pack_rows_dedup): returns [B*F, 1+K+D+1]
+        """Row-gradient message with the duplicates of an id summed first (cffm_pack_rows_dedup): returns [B*F, row_grad_width]
         of which the first #distinct records are valid."""
         buf, _ = self.workspace(B)
-        W = 1 + self.cfg.K + self.cfg.D + 1
-        key = ('dedup', B)
-        out = self._ws.get(key)
-        if out is None:
-            out = torch.empty((B * self.cfg.F, W), dtype=torch.float32, device=self.device)
-            self._ws[key] = out
+        out = self._cached(('dedup', B), lambda: self._row_records(B))
         hip.check(self.lib.cffm_pack_rows_dedup(self._s, _ptr(self._ids(local_ids.reshape(-1))), _ptr(order), _ptr(uniq), int(B),
                                                 _ptr(buf), _ptr(out), self._stream()))
         return out
+
+    def _row_records(self, B):
+        """An uninitialised row-gradient message for a batch of B rows: [B*F, row_grad_width]."""
+        return torch.empty((B * self.cfg.F, self.row_grad_width), dtype=torch.float32, device=self.device)
 
     def backward(self, y, B, B_global=None):
         buf, _ = self.workspace(B)
@@ -935,17 +904,12 @@ class HipEngine(object):
     # ---- data-parallel halves with late loss normalisation (cffm_amd/dist.py) ----------------------------------
     def backward_unscaled(self, ids, y, B, B_global, pack=True):
         """Backward with dL/dout = (out - y) / B_global.  Returns (grad_full [n+4] with this rank's loss-term sum at
-        index n, rows [B*F, 1+K+D+1] = (id bits | dEi | dEo | dfb)) - the operands of ONE all-reduce and ONE
+        index n, rows [B*F, row_grad_width] = (id bits | dEi | dEo | dfb)) - the operands of ONE all-reduce and ONE
         all-gather.  pack=False leaves the row gradients in the workspace (rows is None): the row-sharded step packs
         them itself with the duplicates summed (pack_rows_dedup)."""
         ids = self._ids(ids)
         buf, _ = self.workspace(B)
-        W = 1 + self.cfg.K + self.cfg.D + 1
-        key = ('rows', B)
-        rows = self._ws.get(key) if pack else None
-        if rows is None and pack:
-            rows = torch.empty((B * self.cfg.F, W), dtype=torch.float32, device=self.device)
-            self._ws[key] = rows
+        rows = self._cached(('rows', B), lambda: self._row_records(B)) if pack else None
         hip.check(self.lib.cffm_backward_unscaled(self._s, _ptr(self.theta), _ptr(ids), _ptr(y), int(B),
                                                   int(B_global), _ptr(buf), _ptr(self._grad_full), _ptr(rows),
                                                   self._stream()))
@@ -953,24 +917,20 @@ class HipEngine(object):
 
     def dp_local(self, ids, y, B, B_global):
         """forward + backward_unscaled in one library call (the local half of a data-parallel step).  Returns
-        (grad_full, block): block is ONE flat buffer [B*F*(1+K+D+1) packed rows | B*F sorted 64-bit keys], the unit
+        (grad_full, block): block is ONE flat buffer [B*F*row_grad_width packed rows | B*F sorted 64-bit keys], the unit
         DataParallelStep all-gathers; cffm_dp_apply merges the per-rank sorted runs instead of sorting again."""
         ids = self._ids(ids)
         buf, _ = self.workspace(B)
-        W = 1 + self.cfg.K + self.cfg.D + 1
-        key = ('block', B)
-        block = self._ws.get(key)
-        if block is None:
-            block = torch.empty(B * self.cfg.F * (W + 2), dtype=torch.float32, device=self.device)
-            self._ws[key] = block
+        block = self._cached(('block', B), lambda: torch.empty(B * self.cfg.F * (self.row_grad_width + 2), dtype=torch.float32,
+                                                               device=self.device))
         hip.check(self.lib.cffm_dp_local(self._s, self._t, _ptr(self.theta), _ptr(ids), _ptr(y), int(B),
                                          int(B_global), _ptr(buf), _ptr(self._grad_full), _ptr(block), self._stream()))
         return self._grad_full, block
 
     def dp_apply(self, grad_full, rows_all, B_global, n_runs=0):
-        """n_runs = 0: rows_all [n_rows, 1+K+D+1] in any order (cffm_backward_unscaled rows).  n_runs > 0: the flat
+        """n_runs = 0: rows_all [n_rows, row_grad_width] in any order (cffm_backward_unscaled rows).  n_runs > 0: the flat
         concatenation of n_runs dp_local blocks."""
-        W = 1 + self.cfg.K + self.cfg.D + 1
+        W = self.row_grad_width
         # sorted runs: only where the single-launch forward left them, and while all ids fit the merge kernel's LDS
         runs_ok = n_runs > 0 and rows_all.dim() == 1 and (rows_all.numel() // (W + 2)) * 4 <= 150 * 1024 and \
             bool(self.lib.cffm_dp_runs_ok(self._s, int(rows_all.numel() // (W + 2) // n_runs // self.cfg.F)))
@@ -1004,11 +964,9 @@ class HipEngine(object):
     def dp_local_dense(self, ids, y, B, B_global):
         ids = self._ids(ids)
         buf, _ = self.workspace(B)
-        flat = self._ws.get('flat')
-        if flat is None:
-            flat = torch.zeros(int(self.lib.cffm_dp_dense_floats(self._s)), dtype=torch.float32, device=self.device)
-            self._ws['flat'] = flat
-        elif self._flat_dirty:
+        flat = self._cached('flat', lambda: torch.zeros(int(self.lib.cffm_dp_dense_floats(self._s)), dtype=torch.float32,
+                                                        device=self.device))
+        if self._flat_dirty:
             flat.zero_()                     # a step was abandoned between the two halves: the image contract is zero on entry
         self._flat_dirty = True
         hip.check(self.lib.cffm_dp_local_dense(self._s, self._t, _ptr(self.theta), _ptr(ids), _ptr(y),
@@ -1036,15 +994,6 @@ class HipEngine(object):
                                                _ptr(buf), int(B_ws), self._stream()))
 
     # ---- views the data-parallel step needs (cffm_amd/dist.py) ----------------------------------------
-    def loss_sum_local(self, B):
-        return self.ws_tensor(B, 'scalars', (16,))[0:1]
-
-    def set_loss_sum_global(self, B, s):
-        self.ws_tensor(B, 'scalars', (16,))[3:4].copy_(s)
-
-    def loss_value(self, B):
-        return self.ws_tensor(B, 'scalars', (16,))[1:2]
-
     def row_grads(self, B):
         F = self.cfg.F
         dEi = self.ws_tensor(B, 'dEi', (B, F, self.cfg.K)) if self.cfg.inner_conv else None

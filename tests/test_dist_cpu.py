@@ -326,44 +326,6 @@ def test_row_sharded_step_equals_single_process_step(world):
                 np.testing.assert_allclose(v, p[k], rtol=1e-10, atol=1e-12, err_msg='rank %d %s' % (rank, k))
 
 
-def _shard_worker(rank, world):
-    from cffm_amd.dist import ShardedTables
-    M, dim = 37, 5
-    full = torch.arange(M * dim, dtype=torch.float64).reshape(M, dim)
-    bias = torch.arange(M, dtype=torch.float64).reshape(M, 1) * 0.5
-    local = {'emb': full[rank::world].clone(), 'bias': bias[rank::world].clone()}
-    st = ShardedTables(local)
-    rng = np.random.default_rng(100 + rank)
-    ids = torch.from_numpy(rng.integers(0, M, size=23))
-    rows = st.lookup(ids)
-    assert torch.equal(rows['emb'], full[ids]) and torch.equal(rows['bias'], bias[ids])
-    grads = {'emb': torch.from_numpy(rng.standard_normal((23, dim))), 'bias': torch.from_numpy(rng.standard_normal((23, 1)))}
-    local_rows, recv = st.push_grads(grads)
-    dense = torch.zeros(M, dim, dtype=torch.float64)
-    dense.index_add_(0, ids, grads['emb'])
-    owned = torch.zeros_like(local['emb'])
-    owned.index_add_(0, local_rows, recv['emb'])
-    return dense.numpy(), owned.numpy()
-
-
-def test_row_sharded_lookup_and_gradient_routing():
-    res = _run(_shard_worker, 2)
-    total = res[0][0] + res[1][0]                 # what an unsharded table would accumulate over both ranks
-    for rank in (0, 1):
-        np.testing.assert_allclose(res[rank][1], total[rank::2], rtol=1e-12, atol=1e-12)
-
-
-def test_route_ids_is_a_stable_grouping():
-    from cffm_amd.dist import route_ids, shard_of
-    ids = torch.tensor([7, 2, 9, 4, 4, 1, 8])
-    perm, counts = route_ids(ids, 3)
-    owner = ids[perm] % 3
-    assert counts.tolist() == [1, 4, 2] and torch.equal(owner, torch.sort(owner)[0])
-    assert ids[perm].tolist() == [9, 7, 4, 4, 1, 2, 8]       # stable inside each owner group
-    o, l = shard_of(ids, 3)
-    assert torch.equal(o * 1 + l * 3, ids)
-
-
 # ---- round 3: replicas built from DIFFERENT seeds, content-matched plan prefetch, the CFFM class over a process group --------
 def _state_tensors(comp, tables):
     """replicated_state() of the oracle stand-ins: in-place torch views of the numpy parameters and accumulators."""
