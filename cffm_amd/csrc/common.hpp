@@ -359,11 +359,14 @@ __device__ __forceinline__ float act_relu_grad(float c, int act) {
     return c > 0.f ? act_grad_f(c, act) : 0.f;
 }
 
-// Workgroup barrier that orders LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier).  __syncthreads() also drains every
-// outstanding global load and store (vmcnt(0)): a phase that ends with a burst of global stores then pays their full
-// L2 round trip before the next phase may even issue its loads.  With this barrier the stores drain in the background
-// and loads issued before it stay in flight.  Only for barriers that protect LDS data: anything one thread passes to
-// another through GLOBAL memory still needs __syncthreads().
+// Workgroup barrier that orders LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier).  It was written on the understanding that
+// __syncthreads() also drains every outstanding global load and store (vmcnt(0)).  The generated code of this toolchain at gfx950
+// says otherwise: the __syncthreads() behind the head phase of bwd_top_kernel<3,3,false>, with that phase's global stores in
+// flight, is `s_waitcnt lgkmcnt(0)` and `s_barrier` and no vmcnt wait (a workgroup's wavefronts share one CU and its vector memory
+// path, so the workgroup-scope release needs none); the vmcnt(0) seen in front of other barriers comes from hipcc's counter tracking
+// across branches.  So do not expect a gain from swapping one for the other (profiles/bwd_top_head_waves.md).  The rule for choosing
+// stays: this barrier only where it protects LDS data; anything one thread passes to another through GLOBAL memory takes
+// __syncthreads(), whose fences are what the memory model asks for.
 __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
@@ -477,6 +480,11 @@ struct ParkFilter {
         }
     }
 };
+
+// A value whose only use sits under a lane condition is sunk into that branch by hipcc together with the load behind it, which is then
+// issued behind whatever the branch waits for - one more memory round trip.  pin(v) keeps v, and so its load and the wait for it, in
+// the straight-line code where pin is written.  It emits no instruction.
+__device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 
 // Elements tid, tid + NTH, .. < n of a run-time count: up to U loads of the thread are issued, then consumed in the same ascending
 // order; repeated for n > U * NTH.  Elements past n are predicated off (neither loaded nor consumed).  load(e) -> T, use(e, T).

@@ -2936,8 +2936,6 @@ struct BwdTopArgs {
 template <int NT, int ACT = -1, bool DOUT = false>
 __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float dh1s[CFFM_HEAD_UNITS];
-    __shared__ float dt1s[1024];
     __shared__ float red[4];
     const int bid = blockIdx.x;
 #ifdef CFFM_PHASE_TIMERS
@@ -2977,16 +2975,18 @@ __global__ __launch_bounds__(256, (NT <= 3 ? 3 : 1)) void bwd_top_kernel(BwdTopA
     HeadBwdState st;
     head_bwd_begin(a.hb, b, st);
     PHASE_MARKB(1, b);
+    // the single-example form of the head backward: three chains on wavefronts of their own and no barrier between here and the one in
+    // front of the first input gradient (head_body.hpp)
     if constexpr (DOUT) {
-        if (b < a.hb.B) head_bwd_example<ACT>(a.hb, b, st, b, a.ib.dout[b], dh1s, dt1s);
+        if (b < a.hb.B) head_bwd_example_one<ACT, NT>(a.hb, b, st, b, a.ib.dout[b]);
     } else {
     const float L = head_bwd_loss(a.hb, b == 0, red);
     PHASE_MARKB(2, b);
     if (b < a.hb.B)
-        head_bwd_example<ACT>(a.hb, b, st, b, head_dout(a.hb.loss, a.hb.out[b], a.hb.y[b], 1.f / (float)a.hb.Bg, L), dh1s, dt1s);
+        head_bwd_example_one<ACT, NT>(a.hb, b, st, b, head_dout(a.hb.loss, a.hb.out[b], a.hb.y[b], 1.f / (float)a.hb.Bg, L));
     }
     PHASE_MARKB(3, b);
-    head_bwd_end(a.hb, b, st);
+    head_bwd_end_one(a.hb, b, st);
     PHASE_MARKB(4, b);
     for (int t = 0; t < a.n_layers; ++t) {
         __syncthreads();                                     // dC of this layer (global, written above) is complete

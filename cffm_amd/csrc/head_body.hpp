@@ -427,3 +427,164 @@ __device__ __forceinline__ void head_bwd_end(const HeadBwdArgs& a, int slab, con
         a.s_linb[sob] = st.g_linb;
     }
 }
+
+// ---- single-example form (the fused top of the backward: one example per slab, 256 threads, Pp = 16 NT <= 64) -------------------
+// Once d = dL/dout is known the head backward is three chains that share nothing but d.  In the looping form above wavefront 0
+// carries all three one after the other, across three workgroup barriers; here each chain has wavefronts of its own, requests
+// everything it reads in one batch and passes its intermediate values inside the wavefront, so there is no barrier in this function:
+//   wavefront 0       (a) d -> dh -> dt1 -> dC_top, the only chain the input gradients wait for; keeps g_bias, g_d2w, g_d1b, g_d2b
+//   wavefronts 1, 2   (b) the dense(32) weight-gradient slab, each thread with its own d * beta_outer * d2_w[q]
+//   wavefront 3       (c) the attention / first-order branch; keeps g_linw, g_attb, g_linb
+// Every sum keeps its operands and their order (q ascending in the transposed dense(32), gI ascending in the attention sum) and every
+// slab element is stored as the looping form stores it for its first example: the results are the same bits.
+// The caller's next workgroup barrier (__syncthreads) is what publishes dC_top to the other wavefronts.
+template <int ACTC, int NT>
+__device__ __forceinline__ void head_bwd_example_one(const HeadBwdArgs& a, int slab, HeadBwdState& st, int b, float d) {
+    static_assert(NT >= 1 && NT <= 4, "dC_top is 4 Pp = 64 NT elements, NT per lane of wavefront 0; Pp <= 64 also means F <= 11");
+    constexpr int HU = CFFM_HEAD_UNITS, CB = 128, UB = 16, AW = 12;    // threads of chain (b), its t1 values per thread and batch
+    static_assert(CB % HU == 0, "a thread's q does not change from element to element");
+    const Geo& g = a.g;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int t1w = 2 * g.D - 2;
+    if (wave == 0) {
+        if (lane == 0) { a.dout[b] = d; st.g_bias += d; }
+        if (a.outer_conv) {
+            const float dd = d * g.beta_outer;
+            int off_top = 0;
+            for (int i = 0; i < g.live; ++i) off_top += g.D >> i;
+            const float* Ct = a.Ctop + (int64_t)b * (64 * NT);
+            // requests of the whole chain (lanes past an array's end read its last element again and drop it)
+            const float d2wv = a.d2_w[lane & (HU - 1)];
+            const float h1v = a.h1[(int64_t)b * HU + (lane & (HU - 1))];
+            float ct[NT];
+#pragma unroll
+            for (int u = 0; u < NT; ++u) ct[u] = Ct[lane + 64 * u];
+            float w[HU];                                             // this lane's row k = lane of the dense(32) kernel
+            {
+                const float* r = a.d1_w + min(lane, t1w - 1) * HU;
+#pragma unroll
+                for (int q = 0; q < HU; ++q) w[q] = r[q];
+            }
+            const float dhv = dd * d2wv;                               // dh[q] on lane q (and once more on lane q + 32)
+            st.g_d2w += h1v * dd;                                      // on every lane (head_bwd_end_one stores lanes 0 .. 31): under a
+            st.g_d1b += dhv;                                           // lane condition hipcc sinks the h1 load behind the wait for d2_w
+            if (lane == 0) st.g_d2b += dd;
+            float dtop[2] = {0.f, 0.f};                                // dt1[off_top], dt1[off_top + 1]: all of dt1 that dC_top needs
+            // One trip up to D = 32.  At D = 64 a lane carries a second k = lane + 64, whose row is fetched when its trip comes: holding
+            // both rows at once costs the Pp = 16 instances a wavefront per SIMD (81 registers against 79).
+            // (do-while: t1w >= 14, and behind a loop guard hipcc sinks the row's loads under the guard, behind the wait for d2_w)
+            int k0 = 0;
+            do {
+                if (k0 > 0) {
+                    const float* r = a.d1_w + min(k0 + lane, t1w - 1) * HU;
+#pragma unroll
+                    for (int q = 0; q < HU; ++q) w[q] = r[q];
+                }
+                float s = 0.f;
+#pragma unroll
+                for (int q = 0; q < HU; ++q)                           // q is uniform: dh[q] comes out of lane q by v_readlane
+                    s = fmaf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dhv), q)), w[q], s);   // spelled
+                                                                       // out: the fused multiply-add the looping form's loop compiles to
+                if (k0 + lane < t1w) a.dt1[(int64_t)b * t1w + k0 + lane] = s;
+#pragma unroll
+                for (int yy = 0; yy < 2; ++yy) {
+                    const int kk = off_top + yy - k0;                  // uniform
+                    if (kk >= 0 && kk < 64) dtop[yy] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s), kk));
+                }
+                k0 += 64;
+            } while (k0 < t1w);
+            // gradient wrt the top live conv output: only its sum pool feeds the head
+#pragma unroll
+            for (int u = 0; u < NT; ++u) {
+                const int e = lane + 64 * u, yy = e / (32 * NT);       // e / (2 Pp)
+                a.dCtop[(int64_t)b * (64 * NT) + e] = (yy ? dtop[1] : dtop[0]) * act_relu_grad(ct[u], ACTC >= 0 ? ACTC : g.act);
+            }
+        }
+    } else if (wave == 3) {
+        float* s_attW = a.s_attW + (int64_t)slab * a.stride_front;
+        // requests without a lane condition (lanes and columns past F read the last one again and drop it): one basic block, so that
+        // nothing waits between them
+        const int fl = min(lane, g.F - 1);
+        const float fbr = a.fb[(int64_t)b * g.F + fl];
+        const float fbv = lane < g.F ? fbr : 0.f;
+        if (g.linear_att) {
+            const float atr = a.att[(int64_t)b * g.F + fl], lwr = a.lin_w[fl];
+            float aw[AW], dzg[AW];                                     // the lane's row of att_W (F <= 11 < AW), requested with the rest
+#pragma unroll
+            for (int u = 0; u < AW; ++u) aw[u] = a.att_W[fl * g.F + min(u, g.F - 1)];
+            const float at = lane < g.F ? atr : 0.f;
+            const float lw = lane < g.F ? lwr : 0.f;
+            const float dg = lane < g.F ? d * lw : 0.f;
+            const float da = dg * fbv;
+            const float sda = wave_sum(da * at);
+            const float dz = at * (da - sda) / g.lamda_att;
+            float dfbv = dg * at;
+#pragma unroll
+            for (int u = 0; u < AW; ++u) dzg[u] = __shfl(dz, u, 64);
+#pragma unroll
+            for (int u = 0; u < AW; ++u) pin(aw[u]);                   // their only use is under the lane condition below
+            if (lane < g.F) {
+#pragma unroll
+                for (int u = 0; u < AW; ++u)
+                    if (u < g.F) dfbv = fmaf(dzg[u], aw[u], dfbv);    // spelled out: left to hipcc, the first term here became
+                                                                       // fma(dg, at, dzg[0] * aw[0]), one rounding elsewhere
+#pragma unroll
+                for (int u = 0; u < AW; ++u)
+                    if (u < g.F) s_attW[lane * g.F + u] = fbv * dzg[u];
+                a.dfb[(int64_t)b * g.F + lane] = dfbv;
+            }
+            st.g_linw += fbv * at * d;
+            st.g_attb += dz;
+            if (lane == 0) st.g_linb += d;
+        } else if (lane < g.F) {
+            a.dfb[(int64_t)b * g.F + lane] = d;
+        }
+    } else if (a.outer_conv) {
+        // dense(32) weight gradient, e = k * CFFM_HEAD_UNITS + q, over the 128 threads of wavefronts 1 and 2: a thread keeps its q while
+        // its k advances by 4 per element; its first UB values of t1 are requested with its d2_w[q], any further ones (D >= 64) in batches
+        float* s_d1w = a.s_d1w + (int64_t)slab * a.stride_back;
+        const float* t1b = a.t1 + (int64_t)b * t1w;
+        const int t = (int)threadIdx.x - 64, n = t1w * HU;
+        const float d2wv = a.d2_w[t & (HU - 1)];
+        float tv[UB];
+#pragma unroll
+        for (int u = 0; u < UB; ++u) tv[u] = t1b[min(t + CB * u, n - 1) / HU];
+        const float dd = d * g.beta_outer;
+        const float v = dd * d2wv;                                     // the same two multiplies as dh[q] of chain (a): the same bits
+        // every product first, pinned: a product formed under its store's condition takes its wait there, where the stores issued so
+        // far count as outstanding too, so that the later stores wait for the earlier ones to be acknowledged
+#pragma unroll
+        for (int u = 0; u < UB; ++u) { tv[u] *= v; pin(tv[u]); }
+#pragma unroll
+        for (int u = 0; u < UB; ++u)
+            if (t + CB * u < n) s_d1w[t + CB * u] = tv[u];
+        if (n > UB * CB)
+            loads_first<UB, CB, float>(t, n - UB * CB,
+                [&](int e) { return t1b[(e + UB * CB) / HU]; },
+                [&](int e, float tt) { s_d1w[e + UB * CB] = tt * v; });
+    }
+}
+
+// the slab's per-example sums, stored from the lanes head_bwd_example_one keeps them on
+__device__ __forceinline__ void head_bwd_end_one(const HeadBwdArgs& a, int slab, const HeadBwdState& st) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t sof = (int64_t)slab * a.stride_front, sob = (int64_t)slab * a.stride_back;
+    if (wave == 0) {
+        if (lane < CFFM_HEAD_UNITS) {
+            a.s_d2w[sob + lane] = st.g_d2w;
+            a.s_d1b[sob + lane] = st.g_d1b;
+        }
+        if (lane == 0) {
+            a.s_d2b[sob] = st.g_d2b;
+            a.s_bias[sof] = st.g_bias;
+        }
+    } else if (wave == 3) {
+        if (lane < a.g.F) {
+            a.s_linw[sob + lane] = st.g_linw;
+            a.s_attb[sof + lane] = st.g_attb;
+        }
+        if (lane == 0) a.s_linb[sob] = st.g_linb;
+    }
+}
