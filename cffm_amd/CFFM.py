@@ -716,14 +716,15 @@ class CFFM(object):
             raise ValueError("%s: sampler='device' draws lists of at most 1024: negatives must be <= 1023, not %d" % (who, int(negatives)))
 
     @staticmethod
-    def _negative_cdf(who, eng, negative_weights, negative_power, sampler, m, U, counts):
+    def _negative_cdf(who, eng, negative_weights, negative_power, sampler, m, U, counts, host=False):
         """The cdf words of HipEngine.draw_lists_weighted on the device (int32 storage of cffm_amd.spec.weight_cdf, built on the
         host once per call; U words cross the bus), or None for negative_weights=None.  counts: a callable that returns the
-        occurrence count of every distinct tuple as a device tensor [U] (for 'popularity'), or None where there is no data to count."""
+        occurrence count of every distinct tuple as a device tensor [U] (for 'popularity'), or None where there is no data to count.
+        host=True: (that, the same words as the host's uint32 array or None) - what cffm_amd.spec.logq_table reads."""
         import torch
         from .spec import weight_cdf
         if negative_weights is None:
-            return None
+            return (None, None) if host else None
         if sampler != 'device':
             raise ValueError("%s: negative_weights needs sampler='device', the only sampler that draws weighted lists (not %r)"
                              % (who, sampler))
@@ -748,14 +749,17 @@ class CFFM(object):
         if int((w > 0).sum()) < m + 1:
             raise ValueError('%s: negative_weights has %d positive weights; lists of %d need at least %d'
                              % (who, int((w > 0).sum()), m + 1, m + 1))
-        return torch.from_numpy(weight_cdf(w).view(np.int32)).to(eng.device)
+        words = weight_cdf(w)
+        dev = torch.from_numpy(words.view(np.int32)).to(eng.device)
+        return (dev, words) if host else dev
 
     @staticmethod
-    def _draw_lists_device(eng, seed, list0, at, U, m, cand, cdf=None, who=None):
+    def _draw_lists_device(eng, seed, list0, at, U, m, cand, cdf=None, who=None, with_lists=False):
         """HipEngine.draw_lists for the lists list0 .. list0 + len(at) - 1, in as many calls as the 2^31 element bound of one call
         asks for (a list is a function of its id, so the split does not show): (tuples int32 [G, m + 1, nf], target int32 [G]).
         With cdf (from _negative_cdf) the lists are those of HipEngine.draw_lists_weighted, and a list that came back incomplete
-        raises ValueError (one device reduction and one read per call of this function)."""
+        raises ValueError (one device reduction and one read per call of this function).  with_lists=True: (tuples, lists int32
+        [G, m + 1] the indices the draw wrote, target)."""
         import torch
         G = int(at.shape[0])
         per = max(1, ((1 << 31) - 1) // ((m + 1) * int(cand.shape[1])))
@@ -766,16 +770,16 @@ class CFFM(object):
             return eng.draw_lists_weighted(seed, g0, a, cdf, m, cand)
 
         if G <= per:
-            tuples, _, target = draw(list0, at)
+            tuples, lists, target = draw(list0, at)
         else:
             parts = [draw(list0 + g0, at[g0:g0 + per]) for g0 in range(0, G, per)]
-            tuples, target = torch.cat([p[0] for p in parts]), torch.cat([p[2] for p in parts])
+            tuples, lists, target = (torch.cat([p[i] for p in parts]) for i in range(3))
         if cdf is not None:
             short = int(((target < 0) & (at >= 0) & (at < U)).sum())
             if short:
                 raise ValueError('%s: negative_weights is too skewed for lists of %d under the word cap of the weighted draw: %d of %d '
                                  'lists did not collect their %d negatives (cffm_amd.spec.draw_weighted_cap)' % (who, m + 1, short, G, m))
-        return tuples, target
+        return (tuples, lists, target) if with_lists else (tuples, target)
 
     def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand',
                                 sampler='host', negative_weights=None, negative_power=0.75):
@@ -853,7 +857,7 @@ class CFFM(object):
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
     def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host',
-                      negative_weights=None, negative_power=0.75, hard_pool=None):
+                      negative_weights=None, negative_power=0.75, hard_pool=None, logq=False):
         """Train on what evaluate_ranking_tuples(negatives=m) measures: every row of `data` with a positive label becomes a list of
         its own tuple at `fields` and `negatives` distinct tuples drawn without it from the distinct tuples at `fields` of `data`,
         the positive at a drawn position (the rule of evaluate_ranking_tuples), and the model takes Adagrad steps on the list loss
@@ -879,8 +883,7 @@ class CFFM(object):
         distinct tuples (a zero weight is never drawn).  The cdf is built once per call on the host (cffm_amd.spec.weight_cdf; U
         words cross the bus) and list e * P + j is that of HipEngine.draw_lists_weighted(seed, ...): successive sampling without
         replacement by rejection, cffm_amd.spec.draw_lists_weighted the specification.  These lists differ from the uniform device
-        lists even for equal weights.  The BPR and softmax losses are used as they are: no logQ correction of the sampled softmax
-        is applied.  Fewer than negatives + 1 positive weights, and weights so skewed that a list does not collect its negatives
+        lists even for equal weights.  The BPR and softmax losses are used as they are unless logq=True (below).  Fewer than negatives + 1 positive weights, and weights so skewed that a list does not collect its negatives
         under the word cap (checked after each epoch's draw, before its first step), raise ValueError.
         hard_pool (with sampler='device' only; a ValueError names both otherwise): None (default) trains on the drawn lists,
         everything as without the keyword.  hard_pool=p, negatives < p <= min(U - 1, 1023) over the U distinct tuples, is dynamic
@@ -891,10 +894,30 @@ class CFFM(object):
         positive at a place drawn from (seed, e * P + j) (HipEngine.pick_hard; cffm_amd.spec.pick_hard is the specification) -
         three launches ahead of the unchanged list step at the frappe shape, and the same lists under every lists_per_step only as
         far as the parameters that score them are the same.  The losses are used as they are: no correction of the softmax for the
-        selection is applied.  Out of scope: the multi-GPU list step, other optimizers."""
+        selection is applied.
+        logq (default False: every call, launch and bit as without the keyword): True corrects the sampled softmax for the proposal q
+        the negatives were drawn from - the weights of negative_weights, or 1 / U for the uniform device draw.  The positive, in
+        every list with probability 1, takes no correction; a negative n of a list with positive t has log(m q_n / (1 - q_t))
+        subtracted from its score inside the loss (m = negatives), the importance weight of sum_{j != t} exp(s_j) under the draw's
+        own proposal q_j / (1 - q_t) - the with-replacement correction, meant for negatives far fewer than the distinct tuples.  The
+        table (cffm_amd.spec.logq_table, float32 [U, 2]) is built once per call on the host and U x 2 floats cross the bus; every
+        step hands its lists' indices and the table to the list step (HipEngine.train_step_lists[_fused](..., lists, corr): the same
+        launches), and the returned per-epoch loss is the mean corrected term.  Ranking (evaluate_ranking_tuples) is on raw scores
+        and does not change.  Needs sampler='device', loss='softmax' and hard_pool=None: a ValueError names the keyword at fault
+        (no agreed correction of pairwise BPR exists, and the selection bias of a hard pool is a different problem).
+        Out of scope: the multi-GPU list step, other optimizers."""
         import torch
         from . import hip
         self._check_sampler('train_ranking()', sampler, negatives)
+        if logq:
+            if sampler != 'device':
+                raise ValueError("train_ranking(): logq=True needs sampler='device', whose draws hand on the list indices and the "
+                                 "proposal (not sampler=%r)" % (sampler,))
+            if loss in hip.LIST_LOSS_IDS and loss != 'softmax':
+                raise ValueError("train_ranking(): logq=True corrects the sampled softmax: it needs loss='softmax', not loss=%r" % (loss,))
+            if hard_pool is not None:
+                raise ValueError('train_ranking(): logq=True needs hard_pool=None: the selection bias of a scored pool is not what '
+                                 'logQ corrects (hard_pool=%r)' % (hard_pool,))
         if hard_pool is not None and sampler != 'device':
             raise ValueError("train_ranking(): hard_pool needs sampler='device', the only sampler that draws the pool (not sampler=%r)"
                              % (sampler,))
@@ -937,8 +960,12 @@ class CFFM(object):
                                  % (m, min(U - 1, 1023), U, drawn))
         at_dev = self._positions(cand, ctx[:, colt].to(torch.int32))
         at = at_dev.cpu().numpy() if sampler == 'host' else None
-        cdf = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, drawn, U,
-                                 lambda: self._distinct([data], colt, counts=True))
+        cdf, cdf_host = self._negative_cdf('train_ranking()', eng, negative_weights, negative_power, sampler, drawn, U,
+                                           lambda: self._distinct([data], colt, counts=True), host=True)
+        corr = None
+        if logq:                                                               # once per call: U x 2 floats cross the bus
+            from .spec import logq_table
+            corr = torch.from_numpy(logq_table(cdf_host, m, U)).to(eng.device)
         means = []
         for epoch in range(epochs):
             t1 = time()
@@ -947,7 +974,8 @@ class CFFM(object):
             if sampler == 'device':
                 permt = torch.from_numpy(perm).to(eng.device)
                 rows = ctx[permt]
-                tuples, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, drawn, cand, cdf, 'train_ranking()')
+                tuples, lists, target = self._draw_lists_device(eng, seed, epoch * P, at_dev[permt], U, drawn, cand, cdf,
+                                                                'train_ranking()', with_lists=True)
             else:
                 lists, place = self._draw_lists(rng, at[perm], U, m)
                 rows = ctx[torch.from_numpy(perm).to(eng.device)]
@@ -963,7 +991,10 @@ class CFFM(object):
                 else:                                                          # the pool scored as the parameters stand now
                     scores = eng.score_candidate_tuples(rows[r0:r1], cols, tuples[r0:r1])
                     step_tuples, _, step_target = eng.pick_hard(seed, epoch * P + r0, scores, target[r0:r1], m, tuples=tuples[r0:r1])
-                step_loss = run(rows[r0:r1], cols, step_tuples, step_target, loss)
+                if logq:
+                    step_loss = run(rows[r0:r1], cols, step_tuples, step_target, loss, lists=lists[r0:r1], corr=corr)
+                else:
+                    step_loss = run(rows[r0:r1], cols, step_tuples, step_target, loss)
                 total += step_loss.double() * (r1 - r0)
             means.append(float(total.cpu()[0]) / P)
             self._info('Ranking epoch %d [%.1f s] %s loss over %d lists of %d: %.6f' % (epoch + 1, time() - t1, loss, P, m + 1, means[-1]))

@@ -448,20 +448,24 @@ extern "C" int cffm_list_step_ok(const cffm_shape_t* s, int32_t B) {
 
 // One Adagrad step on G ranked lists of Lg candidates in the launches of cffm_train_step at B = G * Lg (include/cffm_hip.h): id rows,
 // forward without labels, list loss on ws.out, backward from its dL/dout through the fused top, update.
-extern "C" int cffm_train_step_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
-                                     float* theta_acc, float* grad, const int32_t* ctx, int32_t G, const int32_t* fields, int32_t nf,
-                                     const int32_t* cand, int64_t cand_stride, int32_t Lg, const int32_t* target, int32_t kind,
-                                     int32_t* ids_out, float* dout, float* terms, void* ws, float* loss, void* scratch, void* stream) {
+// The corrected step (logq: cffm_train_step_lists_logq) differs in the loss call and in the refusals that belong to its three operands.
+static int train_step_lists_impl(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
+                                 float* theta_acc, float* grad, const int32_t* ctx, int32_t G, const int32_t* fields, int32_t nf,
+                                 const int32_t* cand, int64_t cand_stride, int32_t Lg, const int32_t* target, int32_t kind,
+                                 int32_t* ids_out, float* dout, float* terms, void* ws, float* loss, void* scratch, bool logq,
+                                 const int32_t* lists, const float* corr, int32_t U, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     int rc = check_shape(s);
     if (rc || G <= 0) return rc;
     if (Lg < 2 || (kind != CFFM_LIST_BPR && kind != CFFM_LIST_SOFTMAX)) return CFFM_ERR_BAD_SHAPE;
+    if (logq && kind == CFFM_LIST_BPR) return CFFM_ERR_UNSUPPORTED;
     const int64_t B64 = (int64_t)G * Lg;
     if (B64 > 0x7fffffff || !cffm_list_step_ok(s, (int32_t)B64)) return CFFM_ERR_UNSUPPORTED;
     const int32_t B = (int32_t)B64;
     if (!tab || !tab_acc || !theta || !theta_acc || !grad || !ctx || !fields || !cand || !target || !ids_out || !dout || !terms || !ws ||
         !loss || !scratch)
         return CFFM_ERR_BAD_SHAPE;
+    if (logq && (U < 1 || !lists || !corr || ((uintptr_t)corr & 7))) return CFFM_ERR_BAD_SHAPE;
     const StepCtx c(s, B, theta, ws);
     if ((rc = cffm_route_check(c))) return rc;       // what the forward and the backward ask first: here ahead of the expansion
     // the expansion checks fields / strides itself, before its launch, which is the first of the step
@@ -477,13 +481,34 @@ extern "C" int cffm_train_step_lists(const cffm_shape_t* s, const cffm_tables_t*
         rc = forward_impl(c, step_rows(tab, ids_out), nullptr, st, fo);
     }
     if (rc) return rc;
-    if ((rc = cffm_list_loss(kind, c.at<const float>(c.wl.out), G, Lg, target, dout, terms, loss, scratch, stream))) return rc;
+    const float* out = c.at<const float>(c.wl.out);
+    rc = logq ? cffm_list_loss_logq(kind, out, G, Lg, target, lists, corr, U, dout, terms, loss, scratch, stream)
+              : cffm_list_loss(kind, out, G, Lg, target, dout, terms, loss, scratch, stream);
+    if (rc) return rc;
     BwdOpts bo;
     bo.dout_fused = dout;
     bo.skip_reduce = true;                           // cffm_update_all reduces
     if (!keys_in_fwd) bo.rank_ids = ids_out;
     if ((rc = backward_impl(c, nullptr, (int64_t)B, grad, st, bo))) return rc;
     return cffm_update_all(c, tab, tab_acc, theta, theta_acc, grad, st);
+}
+
+extern "C" int cffm_train_step_lists(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
+                                     float* theta_acc, float* grad, const int32_t* ctx, int32_t G, const int32_t* fields, int32_t nf,
+                                     const int32_t* cand, int64_t cand_stride, int32_t Lg, const int32_t* target, int32_t kind,
+                                     int32_t* ids_out, float* dout, float* terms, void* ws, float* loss, void* scratch, void* stream) {
+    return train_step_lists_impl(s, tab, tab_acc, theta, theta_acc, grad, ctx, G, fields, nf, cand, cand_stride, Lg, target, kind, ids_out,
+                                 dout, terms, ws, loss, scratch, false, nullptr, nullptr, 0, stream);
+}
+
+// cffm_train_step_lists with the logQ-corrected softmax as its loss (include/cffm_hip.h): the same launches
+extern "C" int cffm_train_step_lists_logq(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_acc, float* theta,
+                                          float* theta_acc, float* grad, const int32_t* ctx, int32_t G, const int32_t* fields,
+                                          int32_t nf, const int32_t* cand, int64_t cand_stride, int32_t Lg, const int32_t* target,
+                                          int32_t kind, int32_t* ids_out, float* dout, float* terms, void* ws, float* loss,
+                                          void* scratch, const int32_t* lists, const float* corr, int32_t U, void* stream) {
+    return train_step_lists_impl(s, tab, tab_acc, theta, theta_acc, grad, ctx, G, fields, nf, cand, cand_stride, Lg, target, kind, ids_out,
+                                 dout, terms, ws, loss, scratch, true, lists, corr, U, stream);
 }
 
 extern "C" int cffm_train_step_opt(const cffm_shape_t* s, const cffm_tables_t* tab, const cffm_tables_t* tab_state1,

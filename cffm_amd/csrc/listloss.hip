@@ -5,6 +5,7 @@
 //   BPR       terms[g] = (1/m) sum_{n != t} softplus(s_n - s_t)        dout[n] = sigmoid(s_n - s_t) / (G m),  dout[t] = -sum_{n != t} dout[n]
 //   softmax   terms[g] = log sum_n exp(s_n - max) + max - s_t          dout[n] = (p_n - [n = t]) / G
 //   loss[0] = (1/G) sum_g terms[g]
+//   logQ      the softmax on z_n = s_n - (corr[i_n][0] - corr[i_t][1]) for n != t, z_t = s_t  (cffm_list_loss_logq, further down)
 //
 // One wavefront per list, walking it in strides of 64; lanes reduce by the xor butterfly (every lane ends with the same value).  The
 // loss is summed in two stages in list order - a workgroup's four terms in wave order, then the workgroups' partials by one
@@ -77,6 +78,80 @@ __global__ __launch_bounds__(64 * LL_WAVES) void list_loss_kernel(const float* _
     }
 }
 
+// The logQ-corrected softmax (include/cffm_hip.h): the softmax above on z_n = s_n - c_n, c_n = corr[i_n][0] - corr[i_t][1] for n != t and
+// c_t = 0, i_n = lists[g][n] an index into the table corr [U][2].  The same layout - one wavefront per list, the same order of every sum -
+// so an all-zero table gives the bits of list_loss_kernel<CFFM_LIST_SOFTMAX>: s - (0 - 0) is s, and a lane past the list adds what the
+// strided loops above never formed (-inf to the maximum, an exact zero to the sum).  Every loop runs ceil(Lg / 64) trips on every lane
+// and every branch is on a wave-uniform value; a lane past the end of the list loads the list's last element and its result is dropped
+// by a select (a store is predicated).  The first stride's z stays in a register over the three passes: a list of at most 64 gathers
+// its corrections once.
+__device__ __forceinline__ float ll_logq_z(const float* __restrict__ s, const int32_t* __restrict__ ix, const float2* __restrict__ corr,
+                                           int n, int t, float ct) {
+    const float2 cv = corr[ix[n]];                       // one 8-byte load; column 1 is used for the target alone
+    return s[n] - (n == t ? 0.f : cv.x - ct);
+}
+
+__global__ __launch_bounds__(64 * LL_WAVES) void list_loss_logq_kernel(const float* __restrict__ scores, int G, int Lg,
+                                                                       const int32_t* __restrict__ target,
+                                                                       const int32_t* __restrict__ lists,
+                                                                       const float2* __restrict__ corr, int U, float* __restrict__ dout,
+                                                                       float* __restrict__ terms, double* __restrict__ part) {
+    __shared__ float red[LL_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = blockIdx.x * LL_WAVES + wave;
+    float term = 0.f;                                    // a wavefront past the last list adds an exact zero to its workgroup's partial
+    if (g < G) {                                         // wave-uniform
+        const float* s = scores + (int64_t)g * Lg;
+        const int32_t* ix = lists + (int64_t)g * Lg;
+        float* d = dout + (int64_t)g * Lg;
+        const int t = __builtin_amdgcn_readfirstlane(target[g]);
+        bool ok = t >= 0 && t < Lg;
+        if (ok) {                                        // every index of the list, before the first gather
+            int bad = 0;
+            for (int b = 0; b < Lg; b += 64) {
+                const int i = ix[min(b + lane, Lg - 1)];
+                bad |= (i < 0 || i >= U) ? 1 : 0;
+            }
+            ok = __ballot(bad) == 0ull;
+        }
+        if (!ok) {                                       // defined: a zero row and a zero term, neither s nor corr is read
+            for (int b = 0; b < Lg; b += 64)
+                if (b + lane < Lg) d[b + lane] = 0.f;
+        } else {
+            const float ct = corr[ix[t]].y;              // wave-uniform
+            const float z0 = ll_logq_z(s, ix, corr, min(lane, Lg - 1), t, ct);
+            float mx = lane < Lg ? z0 : -INFINITY;       // fmaxf drops a NaN: it comes back through the sum
+            for (int b = 64; b < Lg; b += 64) {
+                const float z = ll_logq_z(s, ix, corr, min(b + lane, Lg - 1), t, ct);
+                mx = fmaxf(mx, b + lane < Lg ? z : -INFINITY);
+            }
+            mx = ll_wave_max(mx);
+            float se = lane < Lg ? expf(z0 - mx) : 0.f;
+            for (int b = 64; b < Lg; b += 64) {
+                const float z = ll_logq_z(s, ix, corr, min(b + lane, Lg - 1), t, ct);
+                se += b + lane < Lg ? expf(z - mx) : 0.f;
+            }
+            se = ll_wave_sum(se);
+            term = logf(se) + mx - s[t];                 // z_t = s_t: the positive takes no correction
+            const float inv_G = 1.f / (float)G;
+            if (lane < Lg) d[lane] = (expf(z0 - mx) / se - (lane == t ? 1.f : 0.f)) * inv_G;
+            for (int b = 64; b < Lg; b += 64) {
+                const int n = b + lane;
+                const float z = ll_logq_z(s, ix, corr, min(n, Lg - 1), t, ct);
+                if (n < Lg) d[n] = (expf(z - mx) / se - (n == t ? 1.f : 0.f)) * inv_G;
+            }
+        }
+        if (lane == 0) terms[g] = term;
+    }
+    if (lane == 0) red[wave] = term;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double p = 0.0;
+        for (int w = 0; w < LL_WAVES; ++w) p += (double)red[w];
+        part[blockIdx.x] = p;
+    }
+}
+
 // second stage: the n workgroup partials, strided over 1024 threads in index order, lanes by the xor butterfly, waves in wave order
 __global__ __launch_bounds__(1024) void list_loss_final_kernel(const double* __restrict__ part, int n, int G, float* __restrict__ loss) {
     __shared__ double red[16];
@@ -113,6 +188,25 @@ extern "C" int cffm_list_loss(int32_t kind, const float* scores, int32_t G, int3
     else
         hipLaunchKernelGGL(list_loss_kernel<CFFM_LIST_SOFTMAX>, dim3(nb), dim3(64 * LL_WAVES), 0, st, scores, G, Lg, target, dout, terms,
                            (double*)scratch);
+    CFFM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(list_loss_final_kernel, dim3(1), dim3(1024), 0, st, (const double*)scratch, nb, G, loss);
+    CFFM_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int cffm_list_loss_logq(int32_t kind, const float* scores, int32_t G, int32_t Lg, const int32_t* target, const int32_t* lists,
+                                   const float* corr, int32_t U, float* dout, float* terms, float* loss, void* scratch, void* stream) {
+    if (kind != CFFM_LIST_BPR && kind != CFFM_LIST_SOFTMAX) return CFFM_ERR_BAD_SHAPE;
+    if (kind == CFFM_LIST_BPR) return CFFM_ERR_UNSUPPORTED;              // no agreed correction of the pairwise loss
+    if (G < 0 || Lg < 2 || (int64_t)G * Lg >= (1ll << 31)) return CFFM_ERR_BAD_SHAPE;
+    if (U < 1) return CFFM_ERR_BAD_SHAPE;
+    if (G == 0) return 0;
+    if (!scores || !target || !lists || !corr || !dout || !terms || !loss || !scratch) return CFFM_ERR_BAD_SHAPE;
+    if ((uintptr_t)corr & 7) return CFFM_ERR_BAD_SHAPE;                  // a row of the table is one 8-byte load
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = (int)list_loss_blocks(G);
+    hipLaunchKernelGGL(list_loss_logq_kernel, dim3(nb), dim3(64 * LL_WAVES), 0, st, scores, G, Lg, target, lists, (const float2*)corr, U,
+                       dout, terms, (double*)scratch);
     CFFM_CHECK_LAUNCH();
     hipLaunchKernelGGL(list_loss_final_kernel, dim3(1), dim3(1024), 0, st, (const double*)scratch, nb, G, loss);
     CFFM_CHECK_LAUNCH();

@@ -71,6 +71,8 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_draw_lists);
     CFFM_BIND(cffm_draw_lists_weighted);
     CFFM_BIND(cffm_pick_hard);
+    CFFM_BIND(cffm_list_loss_logq);
+    CFFM_BIND(cffm_train_step_lists_logq);
     CFFM_BIND(cffm_dp_runs_ok);
     CFFM_BIND(cffm_dp_local);
     CFFM_BIND(cffm_dp_dense_floats);

@@ -710,10 +710,30 @@ class HipEngine(object):
             raise ValueError("list loss must be one of %s, not %r" % (sorted(hip.LIST_LOSS_IDS), kind))
         return hip.LIST_LOSS_IDS[kind]
 
-    def list_loss(self, scores, target, G, Lg, kind):
+    def _logq_args(self, who, kind, lists, corr, G, Lg):
+        """The operands of the logQ-corrected softmax, checked: lists int32 [G, Lg] and corr fp32 [U, 2] go together (a ValueError
+        names the missing one), kind 'bpr' with them is refused by name -> (lists, corr, U), or None where both are None."""
+        if lists is None and corr is None:
+            return None
+        if lists is None or corr is None:
+            raise ValueError('%s: lists and corr go together: %s is missing' % (who, 'lists' if lists is None else 'corr'))
+        if kind == 'bpr':
+            raise ValueError("%s: the logQ correction (lists, corr) is that of the sampled softmax; kind 'bpr' has none" % who)
+        if tuple(lists.shape) != (G, Lg):
+            raise ValueError('%s: lists must be int32 [G = %d, Lg = %d], not %s' % (who, G, Lg, tuple(lists.shape)))
+        if corr.dim() != 2 or int(corr.shape[1]) != 2 or int(corr.shape[0]) < 1 or corr.dtype != torch.float32 or \
+                not corr.is_contiguous() or corr.device != lists.device:
+            raise ValueError('%s: corr must be a contiguous fp32 [U, 2] on the device (cffm_amd.spec.logq_table)' % who)
+        return self._ids(lists), corr, int(corr.shape[0])
+
+    def list_loss(self, scores, target, G, Lg, kind, lists=None, corr=None):
         """cffm_list_loss over scores fp32 [G * Lg] (list g = rows g * Lg ..) with target int32 [G] the positives' positions, kind
-        'bpr' or 'softmax': (loss [1], dout [G * Lg], terms [G]) on the device, dout = d loss / d scores.  Nothing synchronises."""
-        kind, G, Lg = self._list_kind(kind), int(G), int(Lg)
+        'bpr' or 'softmax': (loss [1], dout [G * Lg], terms [G]) on the device, dout = d loss / d scores.  Nothing synchronises.
+        With lists int32 [G, Lg] (the candidates' indices into U distinct tuples) and corr fp32 [U, 2] (cffm_amd.spec.logq_table) the
+        softmax is logQ-corrected (cffm_list_loss_logq; cffm_amd.spec.list_loss_logq is its float64 twin); 'bpr' is then refused."""
+        kind_id, G, Lg = self._list_kind(kind), int(G), int(Lg)
+        logq = self._logq_args('list_loss', kind, lists, corr, G, Lg)
+        kind = kind_id
         scores, target = scores.reshape(-1), self._ids(target.reshape(-1))
         if scores.dtype != torch.float32 or not scores.is_contiguous():
             scores = scores.to(torch.float32).contiguous()
@@ -723,8 +743,13 @@ class HipEngine(object):
         dout = torch.empty(G * Lg, dtype=torch.float32, device=dev)
         terms = torch.empty(G, dtype=torch.float32, device=dev)
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        hip.check(self.lib.cffm_list_loss(kind, _ptr(scores), G, Lg, _ptr(target), _ptr(dout), _ptr(terms), _ptr(loss),
-                                          _ptr(self._list_scratch(G)), self._stream()))
+        if logq is None:
+            hip.check(self.lib.cffm_list_loss(kind, _ptr(scores), G, Lg, _ptr(target), _ptr(dout), _ptr(terms), _ptr(loss),
+                                              _ptr(self._list_scratch(G)), self._stream()))
+        else:
+            lists, corr, U = logq
+            hip.check(self.lib.cffm_list_loss_logq(kind, _ptr(scores), G, Lg, _ptr(target), _ptr(lists), _ptr(corr), U, _ptr(dout),
+                                                   _ptr(terms), _ptr(loss), _ptr(self._list_scratch(G)), self._stream()))
         return loss, dout, terms
 
     def _list_scratch(self, G):
@@ -763,13 +788,16 @@ class HipEngine(object):
                                                                   torch.empty(G, dtype=torch.float32, device=dev)))
         return ids, dout, terms
 
-    def train_step_lists(self, ctx, fields, cand, target, kind):
+    def train_step_lists(self, ctx, fields, cand, target, kind, lists=None, corr=None):
         """One Adagrad step on G ranked lists: ctx int32 [G, F] the contexts, cand int32 [G, Lg, nf] every list's candidate tuples
         for the columns `fields`, target int32 [G] the position of each list's positive, kind 'bpr' or 'softmax'.  The id rows
         (cffm_expand_candidates_ex), the forward without labels, the list loss on ws.out, the backward from its dL/dout
         (cffm_backward_dout: the stage launches), then the dense and the sparse Adagrad update.  Returns the loss as a device
-        scalar (no host sync).  Adagrad only, and not loss_type='log_loss', whose forward leaves sigmoid(out) and not the score."""
+        scalar (no host sync).  Adagrad only, and not loss_type='log_loss', whose forward leaves sigmoid(out) and not the score.
+        lists int32 [G, Lg] with corr fp32 [U, 2], together: the loss is the logQ-corrected softmax of list_loss (cffm_list_loss_logq
+        where cffm_list_loss stands above), every other launch as it is; kind 'bpr' with them is a ValueError before any launch."""
         kind_id, host_fields, nf, ctx, cand, target, G, Lg, stride = self._list_step_args('train_step_lists', ctx, fields, cand, target, kind)
+        logq = self._logq_args('train_step_lists', kind, lists, corr, G, Lg)
         B = G * Lg
         if B == 0:
             return self.loss_buf
@@ -778,8 +806,14 @@ class HipEngine(object):
                                                      0, B, _ptr(ids), self._stream()))
         self.forward(ids, None)
         buf, wl = self.workspace(B)
-        hip.check(self.lib.cffm_list_loss(kind_id, _ptr(buf) + int(wl.out), G, Lg, _ptr(target), _ptr(dout), _ptr(terms),
-                                          _ptr(self.loss_buf), _ptr(self._list_scratch(G)), self._stream()))
+        if logq is None:
+            hip.check(self.lib.cffm_list_loss(kind_id, _ptr(buf) + int(wl.out), G, Lg, _ptr(target), _ptr(dout), _ptr(terms),
+                                              _ptr(self.loss_buf), _ptr(self._list_scratch(G)), self._stream()))
+        else:
+            lists, corr, U = logq
+            hip.check(self.lib.cffm_list_loss_logq(kind_id, _ptr(buf) + int(wl.out), G, Lg, _ptr(target), _ptr(lists), _ptr(corr), U,
+                                                   _ptr(dout), _ptr(terms), _ptr(self.loss_buf), _ptr(self._list_scratch(G)),
+                                                   self._stream()))
         self.backward_dout(dout, B)
         self.apply_dense()
         dEi, dEo, dfb = self.row_grads(B)
@@ -876,16 +910,18 @@ class HipEngine(object):
         """backward_dout on the launches backward() takes where its fused top runs (cffm_backward_dout_fused); raises where it does not."""
         self._backward_dout('backward_dout_fused', self.lib.cffm_backward_dout_fused, dout, B)
 
-    def train_step_lists_fused(self, ctx, fields, cand, target, kind):
+    def train_step_lists_fused(self, ctx, fields, cand, target, kind, lists=None, corr=None):
         """train_step_lists through the fused top of the backward (cffm_train_step_lists, one library call): the id rows, the forward
         without labels, the list loss on ws.out, the backward from its dL/dout with the fused top placing the update's sort keys, and
         update_all.  Where the single-launch forward runs (cffm_fwd_all_ok: the frappe shape among them) these are the launches of
         train_step plus three, seven at the frappe shape; at D = 8 or 16, and at F = 11 with D = 32, the forward is the stage launches,
         a combination train_step itself does not run (it sorts and applies the rows separately there).  Same arguments,
         checks, return value and buffers (('list_ids', B), ('list_out', G, Lg), loss_buf) as train_step_lists.  Served where
-        list_step_ok(G * Lg); elsewhere a ValueError names the shape and B, and nothing has been touched."""
+        list_step_ok(G * Lg); elsewhere a ValueError names the shape and B, and nothing has been touched.  lists and corr as in
+        train_step_lists: the same launches with the logQ-corrected softmax as the loss (cffm_train_step_lists_logq)."""
         who = 'train_step_lists_fused'
         kind_id, host_fields, nf, ctx, cand, target, G, Lg, stride = self._list_step_args(who, ctx, fields, cand, target, kind)
+        logq = self._logq_args(who, kind, lists, corr, G, Lg)
         B = G * Lg
         if B == 0:
             return self.loss_buf
@@ -895,10 +931,14 @@ class HipEngine(object):
                                                                        self.cfg.lamda_bilinear, G, Lg, B))
         ids, dout, terms = self._list_step_bufs(G, Lg)
         buf, _ = self.workspace(B)
-        hip.check(self.lib.cffm_train_step_lists(self._s, self._t, self._ta, _ptr(self.theta), _ptr(self.theta_acc), _ptr(self.grad),
-                                                 _ptr(ctx), G, C.addressof(host_fields), nf, _ptr(cand), stride, Lg, _ptr(target),
-                                                 kind_id, _ptr(ids), _ptr(dout), _ptr(terms), _ptr(buf), _ptr(self.loss_buf),
-                                                 _ptr(self._list_scratch(G)), self._stream()))
+        args = (self._s, self._t, self._ta, _ptr(self.theta), _ptr(self.theta_acc), _ptr(self.grad), _ptr(ctx), G,
+                C.addressof(host_fields), nf, _ptr(cand), stride, Lg, _ptr(target), kind_id, _ptr(ids), _ptr(dout), _ptr(terms), _ptr(buf),
+                _ptr(self.loss_buf), _ptr(self._list_scratch(G)))
+        if logq is None:
+            hip.check(self.lib.cffm_train_step_lists(*args, self._stream()))
+        else:
+            lists, corr, U = logq
+            hip.check(self.lib.cffm_train_step_lists_logq(*args, _ptr(lists), _ptr(corr), U, self._stream()))
         return self.loss_buf
 
     # ---- data-parallel halves with late loss normalisation (cffm_amd/dist.py) ----------------------------------

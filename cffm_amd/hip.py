@@ -123,6 +123,9 @@ PROTOTYPES = {
                                            _P]),
     'cffm_pick_hard': (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
                                  _P]),
+    'cffm_list_loss_logq': (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    'cffm_train_step_lists_logq': (C.c_int, [_SH, _TB, _TB, _P, _P, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_int64, C.c_int32, _P,
+                                             C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P]),
     'cffm_backward_unscaled': (C.c_int, [_SH, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P]),
     'cffm_dp_apply': (C.c_int, [_SH, _TB, _TB, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P]),
     'cffm_dp_apply_opt': (C.c_int, [_SH, _TB, _TB, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P]),

@@ -419,3 +419,66 @@ def pick_hard(seed, list0, scores, target_pool, m):
     sel[live] = np.where(slot == pl[:, None], t[live][:, None], np.take_along_axis(order[:, :m], src, axis=1))
     place[live] = pl
     return sel, place
+
+
+# ---- logQ-corrected sampled softmax: the table and the float64 twin (and the specification) of cffm_list_loss_logq ----------------
+def logq_table(cdf, m, U=None):
+    """float32 [U, 2] for cffm_list_loss_logq: column 0 is log(m q_j), column 1 is log(1 - q_j), q the proposal the m negatives of a
+    list were drawn from.  cdf: the words of weight_cdf (int32 storage is reinterpreted), q_j = (cdf[j] - cdf[j - 1]) / T with
+    T = cdf[U - 1]; an index that is never drawn (q_j = 0) gets -inf in column 0, and column 1 is log1p(-q_j).  cdf=None with U is the
+    uniform proposal q = 1 / U.  Computed in float64 and rounded once."""
+    m = int(m)
+    if m < 1:
+        raise ValueError('logq_table: needs m >= 1 negatives')
+    if cdf is None:
+        if U is None or int(U) < 1:
+            raise ValueError('logq_table: the uniform table needs U >= 1')
+        q = np.full(int(U), 1.0 / int(U), dtype=np.float64)
+    else:
+        cdf = np.asarray(cdf)
+        if cdf.ndim != 1 or cdf.shape[0] < 1:
+            raise ValueError('logq_table: cdf must be a vector of U >= 1 words')
+        if U is not None and int(U) != cdf.shape[0]:
+            raise ValueError('logq_table: U = %d is not the length of the cdf (%d)' % (int(U), cdf.shape[0]))
+        words = cdf.astype(np.int64) & 0xffffffff
+        T = int(words[-1])
+        if T == 0:
+            raise ValueError('logq_table: the cdf has total T == 0: nothing can be drawn from it')
+        q = np.diff(words, prepend=0).astype(np.float64) / float(T)
+    with np.errstate(divide='ignore'):
+        return np.stack([np.log(m * q), np.log1p(-q)], axis=1).astype(np.float32)
+
+
+def list_loss_logq(scores, target, lists, corr):
+    """The logQ-corrected sampled softmax in float64: scores [G, Lg], target [G] the positives' places, lists [G, Lg] the candidates'
+    indices i_n into U distinct tuples, corr [U, 2] (logq_table).  With t = target[g]: c_n = corr[i_n, 0] - corr[i_t, 1] for n != t,
+    c_t = 0, z = s - c, terms[g] = logsumexp(z) - z_t, dout[g, n] = (softmax(z)_n - [n = t]) / G, loss = mean of the terms.  A target
+    outside [0, Lg), and any index outside [0, U) in a list with a valid target, gives a zero row and a zero term; a non-finite z
+    does what the arithmetic does (NaN term and row).  Returns (loss float, dout float64 [G, Lg], terms float64 [G])."""
+    s = np.asarray(scores, dtype=np.float64)
+    ix = np.asarray(lists).astype(np.int64)
+    c = np.asarray(corr, dtype=np.float64)
+    t = np.asarray(target).astype(np.int64).reshape(-1)
+    if s.ndim != 2 or ix.shape != s.shape or t.shape[0] != s.shape[0] or c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError('list_loss_logq: scores and lists [G, Lg], target [G], corr [U, 2]')
+    G, Lg = s.shape
+    U = c.shape[0]
+    dout, terms = np.zeros((G, Lg)), np.zeros(G)
+    for g in range(G):
+        tg = int(t[g])
+        if tg < 0 or tg >= Lg or (ix[g] < 0).any() or (ix[g] >= U).any():
+            continue
+        with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+            corr_g = c[ix[g], 0] - c[ix[g, tg], 1]
+            corr_g[tg] = 0.0
+            z = s[g] - corr_g
+            mx = np.max(z) if not np.isnan(z).any() else np.nan
+            e = np.exp(z - mx)
+            den = e.sum()
+            terms[g] = np.log(den) + mx - z[tg]
+            p = e / den
+            p[tg] -= 1.0
+            dout[g] = p / G
+            if np.isnan(terms[g]):
+                dout[g] = np.nan
+    return (float(terms.sum() / G) if G else 0.0), dout, terms

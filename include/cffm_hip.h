@@ -662,6 +662,42 @@ int cffm_pick_hard(uint64_t seed, int64_t list0, int32_t G, const float *scores,
                    const int32_t *target_pool, int32_t m, const int32_t *pool_lists, const int32_t *pool_tuples, int32_t nf,
                    int32_t *lists_out, int32_t *tuples_out, int32_t *target_out, void *stream);
 
+/* ---- logQ-corrected sampled softmax over drawn lists --------------------------------------------------
+ * Additive entry points: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes;
+ * cffm_list_loss and cffm_train_step_lists keep every launch and bit.
+ *
+ * cffm_list_loss_logq: cffm_list_loss(CFFM_LIST_SOFTMAX) on scores corrected for the proposal the negatives were drawn from.
+ * lists: device int32 [G][Lg], lists[g][n] = i_n the index of candidate n among U distinct tuples (lists_out of the draws);
+ * corr: device fp32 [U][2], 8-byte aligned, corr[j][0] = log(m q_j) and corr[j][1] = log(1 - q_j) with m = Lg - 1 and q the proposal
+ * (cffm_amd/spec.py logq_table() builds it, log m included: the kernel forms no transcendental for the correction).  With t = target[g]:
+ *   c_n = corr[i_n][0] - corr[i_t][1]  (n != t),   c_t = 0            z_n = s_n - c_n
+ *   terms[g] = log sum_n exp(z_n - max z) + max z - z_t               dout[n] = (softmax(z)_n - [n = t]) / G
+ *   loss[0] = (1/G) sum_g terms[g]
+ * The positive is in every list with probability 1 and takes no correction; a negative stands for 1 / (m q_n / (1 - q_t)) members of
+ * the catalogue without the target: importance sampling of sum_{j != t} exp(s_j) from q_j / (1 - q_t).  An all-zero table gives the
+ * bits of cffm_list_loss(CFFM_LIST_SOFTMAX).  Scratch, the two-stage fixed-order loss sum and what is written as cffm_list_loss: the
+ * same bits on every run, whatever scratch held.  A target[g] outside [0, Lg) gives a zero row and a zero term and nothing of the list
+ * is read; so does any lists[g][n] outside [0, U) in a list with a valid target (tested over the whole list before the first gather:
+ * corr is never read out of range).  Repeated indices in a list are allowed.  A non-finite z does what the arithmetic does: the list's
+ * term and row become NaN (a -inf correction of a negative among them), as a NaN score does in cffm_list_loss.
+ * Refusals, before any launch, in this order: CFFM_ERR_BAD_SHAPE for an unknown kind; CFFM_ERR_UNSUPPORTED for CFFM_LIST_BPR (no
+ * agreed correction of the pairwise loss exists); CFFM_ERR_BAD_SHAPE for G < 0, Lg < 2, G * Lg >= 2^31; CFFM_ERR_BAD_SHAPE for U < 1;
+ * G == 0 returns 0 without a launch; CFFM_ERR_BAD_SHAPE for a NULL pointer that would be read or written (scores, target, lists, corr,
+ * dout, terms, loss, scratch) and for a corr that is not 8-byte aligned. */
+int cffm_list_loss_logq(int32_t kind, const float *scores, int32_t G, int32_t Lg, const int32_t *target,
+                        const int32_t *lists, const float *corr, int32_t U,
+                        float *dout, float *terms, float *loss, void *scratch, void *stream);
+/* cffm_train_step_lists_logq: cffm_train_step_lists with its step 3 replaced by cffm_list_loss_logq(kind, ws.out, G, Lg, target, lists,
+ * corr, U, dout, terms, loss, scratch) - the same launches (seven at the frappe shape), the same served domain (cffm_list_step_ok).
+ * Every argument of cffm_train_step_lists in its order up to scratch, then lists, corr, U as above.  Refusals, all with nothing
+ * launched, in the order of cffm_train_step_lists with two more: CFFM_ERR_UNSUPPORTED for CFFM_LIST_BPR right after the kind check,
+ * and CFFM_ERR_BAD_SHAPE for U < 1, a NULL lists, a NULL corr or a corr that is not 8-byte aligned right after the NULL checks. */
+int cffm_train_step_lists_logq(const cffm_shape_t *s, const cffm_tables_t *tab, const cffm_tables_t *tab_acc, float *theta,
+                               float *theta_acc, float *grad, const int32_t *ctx, int32_t G, const int32_t *fields, int32_t nf,
+                               const int32_t *cand, int64_t cand_stride, int32_t Lg, const int32_t *target, int32_t kind,
+                               int32_t *ids_out, float *dout, float *terms, void *ws, float *loss, void *scratch,
+                               const int32_t *lists, const float *corr, int32_t U, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
