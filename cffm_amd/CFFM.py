@@ -522,7 +522,76 @@ class CFFM(object):
             raise ValueError('candidates must be a non-empty 1-D array of feature ids')
         return torch.from_numpy(np.ascontiguousarray(cand.astype(np.int32))).to(self.engine.device)
 
-    def recommend(self, contexts, field, candidates=None, k=10, skip=None, score_rows=1 << 22, sweep='expand'):
+    # ---- ranking without the items an owner has already seen -----------------------------------------------
+    def _seen_args(self, who, exclude, by, cols, refuse=()):
+        """exclude= / by= of the four ranking methods, checked before anything runs: None without them, else (the list of splits,
+        the owner column).  cols: the swept columns; refuse: (keyword, value, why) triples of keywords exclude does not go with."""
+        if exclude is None and by is None:
+            return None
+        if exclude is None:
+            raise ValueError('%s: by= names the owner column of exclude=, which is missing: pass exclude too' % who)
+        if by is None:
+            raise ValueError('%s: exclude= needs by=, the column whose id names the owner of a seen item: pass by too' % who)
+        for name, value, why in refuse:
+            if value:
+                raise ValueError('%s: exclude= does not go with %s: %s' % (who, name, why))
+        if isinstance(by, bool) or not isinstance(by, (int, np.integer)) or not 0 <= int(by) < self.num_field:
+            raise ValueError('%s: by=%r is not a column of [0, %d)' % (who, by, self.num_field))
+        if int(by) in cols:
+            raise ValueError('%s: by=%d is a swept column; the owner column must be one the candidates leave alone' % (who, int(by)))
+        splits = [exclude] if isinstance(exclude, dict) else list(exclude)
+        if not splits or not all(isinstance(d, dict) and 'X' in d and 'Y' in d for d in splits):
+            raise ValueError("%s: exclude must be a split {'X': ..., 'Y': ...} or a list of splits" % who)
+        return splits, int(by)
+
+    def _seen_relation(self, seen, cols, cand):
+        """The seen relation of a call as a CSR over candidate POSITIONS, built on the device once (cffm_amd.spec.seen_index is the
+        specification): (keys [R] the sorted distinct owners, off int32 [R + 1], pos int32 [nnz]).  Owner u has seen every entry of
+        cand - ids [N] for one swept column, tuples [N, nf] otherwise - that occurs at the swept columns of a row of the splits with
+        label > 0 and id u at the owner column, at EVERY position that holds it; a seen tuple cand lacks is dropped.  The one
+        device-to-host read is the number of pairs, for the int32 bound and the kernel's argument."""
+        import torch
+        splits, by = seen
+        rows = torch.cat([ids[y.reshape(-1) > 0] for ids, y, _ in (self._device_split(d) for d in splits)])
+        N = int(cand.shape[0])
+        what = rows[:, cols[0]] if cand.dim() == 1 else rows[:, cols]
+        first = self._positions(cand, what.to(cand.dtype))                      # the first position that holds the seen entry, N if none
+        here = first < N
+        owner, first = rows[:, by][here].long(), first[here]
+        # the list may repeat an entry: position n stands for the first position that holds cand[n], and a seen entry takes every
+        # position of its group
+        group, order = torch.sort(self._positions(cand, cand), stable=True)
+        lo = torch.searchsorted(group, first)
+        n_of = torch.searchsorted(group, first, right=True) - lo
+        start = torch.repeat_interleave(lo, n_of)
+        within = torch.arange(int(start.numel()), device=start.device) - torch.repeat_interleave(torch.cumsum(n_of, 0) - n_of, n_of)
+        keys, krow = torch.unique(torch.repeat_interleave(owner, n_of), return_inverse=True)
+        pairs = torch.unique(krow * N + order[start + within])                 # (CSR row, position), sorted, each once
+        nnz = int(pairs.numel())
+        if nnz >= 1 << 31:
+            raise ValueError('exclude: the seen relation holds %d (owner, position) pairs; the CSR indexes fewer than 2^31' % nnz)
+        R = int(keys.numel())
+        off = torch.searchsorted(torch.div(pairs, N, rounding_mode='floor'), torch.arange(R + 1, device=pairs.device)).to(torch.int32)
+        return keys, off, (pairs % N).to(torch.int32)
+
+    def _seen_masks(self, eng, seen, cols, cand, ctx, N, skip=None):
+        """mask(c0, c1) for the group loops of _topk_sweep and _rank_targets: the seen set of every context's owner as the uint8
+        [c1 - c0, N] skip mask of topk / rank_of, OR-ed with the rows of skip (uint8 [C, N] on the device, or None).  The CSR row of
+        EVERY context is looked up here, once, next to the relation build (keys is sorted and distinct: a searchsorted and a compare,
+        -1 for an owner that is not there); a group is then a slice of that vector and one HipEngine.seen_mask launch, and nothing in
+        the returned mask(c0, c1) synchronises with the host."""
+        import torch
+        keys, off, pos = self._seen_relation(seen, cols, cand)
+        owner = ctx[:, seen[1]].to(keys.dtype).contiguous()
+        R = int(keys.numel())
+        if R == 0:
+            row = torch.full((int(owner.shape[0]),), -1, dtype=torch.int32, device=owner.device)
+        else:
+            at = torch.searchsorted(keys, owner).clamp(max=R - 1)
+            row = torch.where(keys[at] == owner, at, torch.full_like(at, -1)).to(torch.int32)
+        return lambda c0, c1: eng.seen_mask(off, pos, row[c0:c1], N, skip=None if skip is None else skip[c0:c1])
+
+    def recommend(self, contexts, field, candidates=None, k=10, skip=None, score_rows=1 << 22, sweep='expand', exclude=None, by=None):
         """For every context row (contexts [C,F] feature ids), the k candidates that score highest when their id is put at column
         `field`.  candidates: 1-D feature ids (default: the sorted distinct ids in column `field` of the train split last passed
         to train()); skip: optional boolean [C,N] over candidate positions, True = leave out (e.g. items already seen).
@@ -530,15 +599,22 @@ class CFFM(object):
         (ids int32 [C,k] candidate feature ids, -1 padded; scores float32 [C,k] their raw predictions, NaN padded).  Local to
         the calling rank: no collective.  sweep: 'expand' (default) scores the expanded id rows with the ordinary forward;
         'shared' does the fixed-field work once per context (equal to rounding, not bit for bit; ValueError for a shape it does
-        not serve); 'auto' picks 'shared' where it is served and N >= SWEEP_MIN_N."""
+        not serve); 'auto' picks 'shared' where it is served and N >= SWEEP_MIN_N.
+        exclude / by (together, or a ValueError names the missing one; default None: every call as without them): exclude is a split
+        (the dict train() / evaluate() take) or a list of splits, by the column whose id names the owner of a seen item (the user
+        column; not `field`).  Every candidate that occurs at column `field` of a row of exclude with label > 0 and the context's
+        own id at column by is left out for that context, at every position of an explicit list that holds it, OR-ed with skip.
+        The relation goes to the device once as a CSR and the mask is made there per group of contexts (HipEngine.seen_mask)
+        instead of a dense host [C, N] array."""
         import torch
         eng = self._ranking_engine()
+        seen = self._seen_args('recommend()', exclude, by, [int(field)])
         if candidates is None and self._train_split is None:
             raise ValueError('recommend(): no train split yet (train() was not called) - pass candidates')
         if not 1 <= int(k) <= 1024:
             raise ValueError('recommend(): k must be in [1, 1024]')
         cand = self._candidates(candidates, field, [self._train_split])
-        pos, val = self._topk_sweep(eng, self._contexts(eng, contexts), int(field), cand, False, None, int(k), skip, score_rows, sweep)
+        pos, val = self._topk_sweep(eng, self._contexts(eng, contexts), int(field), cand, False, None, int(k), skip, score_rows, sweep, seen)
         cand64 = cand.long()
         ids = torch.where(pos >= 0, cand64[pos.clamp(min=0).long()], cand64.new_full((), -1)).to(torch.int32)
         return ids.cpu().numpy(), val.cpu().numpy()
@@ -551,10 +627,12 @@ class CFFM(object):
             raise ValueError('contexts must be [C, %d] feature ids' % self.num_field)
         return torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(eng.device)
 
-    def _topk_sweep(self, eng, ctx, fields, cand, per_context, counts, k, skip, score_rows, sweep):
+    def _topk_sweep(self, eng, ctx, fields, cand, per_context, counts, k, skip, score_rows, sweep, seen=None):
         """The top-k sweep of recommend and recommend_tuples over ctx and cand on the device (fields and cand as _scorer takes
         them), the contexts in groups of max(1, score_rows // N): (pos int32 [C, k] candidate positions, -1 padded; val float32
-        [C, k], NaN padded) on the device.  skip and counts are the caller's host arrays; counts is merged into the skip mask."""
+        [C, k], NaN padded) on the device.  skip and counts are the caller's host arrays; counts is merged into the skip mask.
+        seen: what _seen_args returned; with it the skip mask of a group is made on the device from the seen relation, that host
+        mask OR-ed in (_seen_masks)."""
         import torch
         C, N = int(ctx.shape[0]), int(cand.shape[1 if per_context else 0])
         if per_context and cand.shape[0] != C:
@@ -578,22 +656,32 @@ class CFFM(object):
         val_out = torch.empty((C, k), dtype=torch.float32, device=eng.device)
         group = max(1, int(score_rows) // N)
         score = self._scorer(eng, sweep, fields, N, per_context)
+        if seen is not None:
+            seen_of = self._seen_masks(eng, seen, [fields] if isinstance(fields, int) else fields, cand, ctx, N, mask)
         for c0 in range(0, C, group):
             c1 = min(C, c0 + group)
             scores = score(ctx[c0:c1], cand[c0:c1] if per_context else cand)
-            idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
+            if seen is not None:
+                idx, val, _ = eng.topk(scores, k, skip=seen_of(c0, c1))
+            else:
+                idx, val, _ = eng.topk(scores, k, skip=None if mask is None else mask[c0:c1])
             pos_out[c0:c1] = idx
             val_out[c0:c1] = val
         return pos_out, val_out
 
-    def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22, sweep='expand'):
+    def evaluate_ranking(self, data, field, k=10, candidates=None, score_rows=1 << 22, sweep='expand', exclude=None, by=None):
         """(HR@k, NDCG@k) of a split: for every row with label > 0 the context is the row and the target is the row's own id at
         column `field`, ranked among the candidates (default: the sorted distinct ids in column `field` over the train split and
         `data` together, so every target is a candidate).  Explicit candidates that lack a target raise ValueError.  The sweep
         stays on the device: scores, rank of the target, and the two sums and the count in float64; under a process group with
         replicated tables every rank takes a contiguous share of the positive rows and the sums are all-reduced.  sweep: as in
-        recommend()."""
+        recommend().
+        exclude / by (together; default None: every call as without them): as in recommend() - every positive row is ranked among
+        the candidates its own owner (the row's id at column by) has NOT got in exclude (label > 0), the filtered protocol of
+        full-ranking evaluations with exclude = the train split.  The target itself always stays: a pair that is in both splits is
+        still ranked (cffm_rank_of ignores the flag at the target).  Under a process group every rank builds the whole relation."""
         eng = self._ranking_engine()
+        seen = self._seen_args('evaluate_ranking()', exclude, by, [int(field)])
         ids, y, _ = self._device_split(data)
         cand = self._candidates(candidates, field, self._eval_splits(data))
         field, k = int(field), int(k)
@@ -610,13 +698,15 @@ class CFFM(object):
             raise ValueError('evaluate_ranking(): target id %d at field %d is not among the candidates'
                              % (int(tgt[missing][0]), field))
         r0, r1, _ = self._row_share(P)
+        seen_of = None if seen is None else self._seen_masks(eng, seen, [field], cand, ctx, N)
         return self._rank_targets('evaluate_ranking()', eng, self._scorer(eng, sweep, field, N), ctx, lambda c0, c1: cand, tpos, r0, r1,
-                                  N, k, score_rows)
+                                  N, k, score_rows, seen_of)
 
-    def _rank_targets(self, who, eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows):
+    def _rank_targets(self, who, eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows, seen_of=None):
         """(HR@k, NDCG@k) of the rows [r0, r1) of ctx, in groups of max(1, score_rows // N): score(ctx[c0:c1], cand_of(c0, c1)) and
         the rank of candidate tpos[c] in row c, the sums [hits, gains, rows, NaN flag] accumulated on the device in float64,
-        all-reduced and read once.  who names the calling method in the NaN error."""
+        all-reduced and read once.  who names the calling method in the NaN error.  seen_of: None, or _seen_masks' mask(c0, c1),
+        handed to rank_of as its skip (the flag at the target's own position is ignored there)."""
         import torch
         tpos = tpos.to(torch.int32)
         sums = torch.zeros(4, dtype=torch.float64, device=eng.device)
@@ -624,7 +714,10 @@ class CFFM(object):
         for c0 in range(r0, r1, group):
             c1 = min(r1, c0 + group)
             scores = score(ctx[c0:c1], cand_of(c0, c1))
-            rank = eng.rank_of(scores, tpos[c0:c1]).double()
+            if seen_of is None:
+                rank = eng.rank_of(scores, tpos[c0:c1]).double()
+            else:
+                rank = eng.rank_of(scores, tpos[c0:c1], skip=seen_of(c0, c1)).double()
             hit = rank < k
             sums[0] += hit.sum()
             sums[1] += torch.where(hit, 1.0 / torch.log2(rank + 2.0), torch.zeros_like(rank)).sum()
@@ -659,7 +752,7 @@ class CFFM(object):
         return np.ascontiguousarray(cand.astype(np.int32))
 
     def recommend_tuples(self, contexts, fields, candidates, per_context=False, counts=None, k=10, skip=None, score_rows=1 << 22,
-                         sweep='expand'):
+                         sweep='expand', exclude=None, by=None):
         """For every context row, the k candidates that score highest when their ids are put at the columns `fields` (an int or
         distinct columns) TOGETHER.  candidates: [N] / [N, nf] (one list for every context) or, with per_context, [C, N] /
         [C, N, nf] (a list per context); counts: optional [C] for per-context lists, list c holding counts[c] <= N candidates and
@@ -671,15 +764,19 @@ class CFFM(object):
         per context) for any nf >= 1, equal to 'expand' to rounding, ValueError naming 'tuples' where (shape, nf) is not served
         (nf <= 4; nf = 3 at F = 10, K = 32 is not).  Measured at the frappe shape, nf = 2: 0.60 of expand's time for one shared list,
         0.79 for lists of 100 per context (profiles/sweep_tuples.md, one box); 'auto' never picks it.  Local to the calling rank: no
-        collective."""
+        collective.
+        exclude / by: as in recommend(), the seen set of an owner being the tuples at `fields` of its rows of exclude with label > 0;
+        one shared list only - per_context=True with exclude raises ValueError (positions then differ per context)."""
         import torch
         eng = self._ranking_engine()
         cols = self._tuple_fields(fields)
+        seen = self._seen_args('recommend_tuples()', exclude, by, cols,
+                               [('per_context', per_context, 'candidate positions then differ per context; one shared list only')])
         if not 1 <= int(k) <= 1024:
             raise ValueError('recommend_tuples(): k must be in [1, 1024]')
         ctx = self._contexts(eng, contexts)
         cand = torch.from_numpy(self._tuple_array(candidates, len(cols), 2 if per_context else 1, 'candidates')).to(eng.device)
-        pos, val = self._topk_sweep(eng, ctx, cols, cand, per_context, counts, int(k), skip, score_rows, sweep)
+        pos, val = self._topk_sweep(eng, ctx, cols, cand, per_context, counts, int(k), skip, score_rows, sweep, seen)
         return pos.cpu().numpy(), val.cpu().numpy()
 
     @staticmethod
@@ -782,7 +879,7 @@ class CFFM(object):
         return (tuples, lists, target) if with_lists else (tuples, target)
 
     def evaluate_ranking_tuples(self, data, fields, k=10, candidates=None, negatives=None, seed=0, score_rows=1 << 22, sweep='expand',
-                                sampler='host', negative_weights=None, negative_power=0.75):
+                                sampler='host', negative_weights=None, negative_power=0.75, exclude=None, by=None):
         """(HR@k, NDCG@k) over the rows of `data` with a positive label, the target being the row's own tuple at `fields`.
         negatives=None: one shared list - by default the distinct tuples at `fields` over the train split and `data`, sorted
         (torch.unique(dim=0) on the device); explicit candidates [N] / [N, nf] that lack a target raise ValueError.  negatives=m:
@@ -804,11 +901,17 @@ class CFFM(object):
         ...) (cffm_amd.spec.draw_lists_weighted is the specification: successive sampling without replacement by rejection, list r
         a function of (seed, r) alone); they differ from the uniform device lists even for equal weights.  Fewer than m + 1
         positive weights, and weights so skewed that a list does not collect its m negatives under the word cap, raise ValueError.
-        Out of scope: hard-negative (model-scored) draws."""
+        exclude / by (negatives=None only; default None: every call as without them): as in evaluate_ranking(), the seen set of an
+        owner being the tuples at `fields` of its rows of exclude with label > 0.  With negatives=m a ValueError names exclude and
+        negatives: drawn lists that avoid seen items belong to the draw kernels.
+        Out of scope: hard-negative (model-scored) draws, seen-aware draws."""
         import torch
         self._check_sampler('evaluate_ranking_tuples()', sampler, negatives)
         eng = self._ranking_engine()
         cols = self._tuple_fields(fields)
+        seen = self._seen_args('evaluate_ranking_tuples()', exclude, by, cols,
+                               [('negatives=%r' % (negatives,), negatives is not None,
+                                 'lists drawn without the seen items are not implemented; exclude filters the shared list (negatives=None)')])
         ids, y, _ = self._device_split(data)
         k = int(k)
         if k < 1:
@@ -853,7 +956,8 @@ class CFFM(object):
                 tpos = torch.from_numpy(place).to(eng.device)
                 cand_of = lambda c0, c1: cand[lists[c0:c1]]
         score = self._scorer(eng, sweep, cols, N, negatives is not None)
-        return self._rank_targets('evaluate_ranking_tuples()', eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows)
+        seen_of = None if seen is None else self._seen_masks(eng, seen, cols, cand, ctx, N)
+        return self._rank_targets('evaluate_ranking_tuples()', eng, score, ctx, cand_of, tpos, r0, r1, N, k, score_rows, seen_of)
 
     # ---- training on ranked lists ----------------------------------------------------------------------------
     def train_ranking(self, data, fields, negatives=4, loss='bpr', epochs=1, lists_per_step=None, seed=0, step='stages', sampler='host',

@@ -99,6 +99,7 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_topk_scratch_bytes);
     CFFM_BIND(cffm_topk);
     CFFM_BIND(cffm_rank_of);
+    CFFM_BIND(cffm_seen_mask);
     CFFM_BIND(cffm_sweep_ok);
     CFFM_BIND(cffm_sweep_scratch_bytes);
     CFFM_BIND(cffm_score_sweep);

@@ -543,6 +543,32 @@ class HipEngine(object):
                                         self._stream()))
         return rank
 
+    def seen_mask(self, off, pos, row, N, skip=None):
+        """cffm_seen_mask: the skip mask of topk / rank_of from a sparse seen relation on the device - off int32 [R + 1] and pos int32
+        [nnz] the CSR of candidate positions (cffm_amd.spec.seen_index builds one), row int32 [C] the CSR row of every context
+        (outside [0, R): nothing seen) - OR-ed with skip, an optional [C, N] mask (non-zero = leave out).  Returns uint8 [C, N] on
+        the device, cffm_amd.spec.seen_mask bit for bit.  The buffer is kept per (C, N) and written again by the next call of that
+        shape: hand it to topk / rank_of before then.  Nothing synchronises."""
+        N = int(N)
+        if off.dim() != 1 or pos.dim() != 1 or row.dim() != 1 or int(off.numel()) < 1 or N < 1:
+            raise ValueError('seen_mask: needs off [R + 1], pos [nnz], row [C] and N >= 1')
+        off, pos, row = self._ids(off), self._ids(pos), self._ids(row)
+        C, R, nnz = int(row.numel()), int(off.numel()) - 1, int(pos.numel())
+        skip_stride = 0
+        if skip is not None:
+            if tuple(skip.shape) != (C, N):
+                raise ValueError('skip must be [C, N]: one row per entry of row')
+            if skip.dtype == torch.bool:
+                skip = skip.contiguous().view(torch.uint8)
+            elif skip.dtype != torch.uint8 or not skip.is_contiguous():
+                skip = (skip != 0).contiguous().view(torch.uint8)
+            skip_stride = N
+        mask = self._cached(('seen_mask', C, N), lambda: torch.empty((C, N), dtype=torch.uint8, device=self.device))
+        if C:
+            hip.check(self.lib.cffm_seen_mask(_ptr(off), _ptr(pos) if nnz else 0, R, nnz, _ptr(row), _ptr(skip), skip_stride, C, N,
+                                              _ptr(mask), N, self._stream()))
+        return mask
+
     def predictions(self, B):
         """The [B] outputs the last forward (forward / forward_staged / forward_packed) left in the workspace, as a tensor of
         their own."""

@@ -150,6 +150,7 @@ PROTOTYPES = {
     'cffm_topk_scratch_bytes': (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     'cffm_topk': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     'cffm_rank_of': (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    'cffm_seen_mask': (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     'cffm_sweep_ok': (C.c_int, [_SH]),
     'cffm_sweep_scratch_bytes': (C.c_int64, [_SH, C.c_int32]),
     'cffm_score_sweep': (C.c_int, [_SH, _TB, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P, _P]),

@@ -482,3 +482,55 @@ def list_loss_logq(scores, target, lists, corr):
             if np.isnan(terms[g]):
                 dout[g] = np.nan
     return (float(terms.sum() / G) if G else 0.0), dout, terms
+
+
+# ---- the skip mask of a ranking call from a sparse "seen" relation: the build and the numpy twin (and the specification) of
+# cffm_seen_mask ------------------------------------------------------------------------------------------------
+def seen_index(owner, cand_pos):
+    """The CSR of a seen relation from parallel arrays: pair i says that owner[i] has seen the candidate at position cand_pos[i].
+    Returns (keys int64 [R] the sorted distinct owners, off int32 [R + 1], pos int32 [nnz]): row r, pos[off[r]:off[r + 1]], holds the
+    positions of owner keys[r], ascending and distinct (a repeated pair counts once).  A context finds its row by looking its owner
+    up in keys; an owner that is not there has seen nothing."""
+    owner = np.asarray(owner).astype(np.int64).reshape(-1)
+    p = np.asarray(cand_pos).astype(np.int64).reshape(-1)
+    if owner.shape != p.shape:
+        raise ValueError('seen_index: one candidate position per owner')
+    if p.size and (p.min() < 0 or p.max() >= 2 ** 31):
+        raise ValueError('seen_index: candidate positions must lie in [0, 2^31)')
+    pairs = np.unique(np.stack([owner, p], axis=1), axis=0) if p.size else np.zeros((0, 2), dtype=np.int64)
+    if pairs.shape[0] >= 2 ** 31:
+        raise ValueError('seen_index: the relation must hold fewer than 2^31 pairs')
+    keys = np.unique(pairs[:, 0])
+    off = np.append(np.searchsorted(pairs[:, 0], keys, side='left'), pairs.shape[0])       # np.unique sorted the pairs by owner first
+    return keys, off.astype(np.int32), pairs[:, 1].astype(np.int32)
+
+
+def seen_mask(off, pos, row, N, skip_in=None, nnz=None):
+    """uint8 [C, N], the mask cffm_seen_mask writes: byte (c, n) is 1 where skip_in[c, n] != 0 or where n is an entry pos[j],
+    lo <= j < hi, of context c's CSR row r = row[c] - lo and hi being off[r] and off[r + 1] clamped into [0, nnz] - and 0 otherwise.
+    Malformed input as the kernel takes it: a row[c] outside [0, R) and a decreasing pair of offsets give no entries, entries of pos
+    outside [0, N) are ignored, entries may repeat and come in any order.  nnz: the number of entries of pos that belong to the
+    relation (default: all of pos); nothing at or beyond it is looked at."""
+    off = np.asarray(off).astype(np.int64).reshape(-1)
+    pos = np.asarray(pos).astype(np.int64).reshape(-1)
+    row = np.asarray(row).astype(np.int64).reshape(-1)
+    N, R = int(N), off.shape[0] - 1
+    nnz = pos.shape[0] if nnz is None else int(nnz)
+    if R < 0 or N < 1 or not 0 <= nnz <= pos.shape[0]:
+        raise ValueError('seen_mask: needs off [R + 1], N >= 1 and 0 <= nnz <= len(pos)')
+    C = row.shape[0]
+    if skip_in is None:
+        mask = np.zeros((C, N), dtype=np.uint8)
+    else:
+        skip_in = np.asarray(skip_in)
+        if skip_in.shape != (C, N):
+            raise ValueError('seen_mask: skip_in must be [%d, %d]' % (C, N))
+        mask = (skip_in != 0).astype(np.uint8)
+    for c in range(C):
+        r = int(row[c])
+        if not 0 <= r < R:
+            continue
+        lo, hi = (min(max(int(v), 0), nnz) for v in (off[r], off[r + 1]))
+        p = pos[lo:hi] if hi > lo else pos[:0]
+        mask[c, p[(p >= 0) & (p < N)]] = 1
+    return mask

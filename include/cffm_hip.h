@@ -698,6 +698,26 @@ int cffm_train_step_lists_logq(const cffm_shape_t *s, const cffm_tables_t *tab, 
                                int32_t *ids_out, float *dout, float *terms, void *ws, float *loss, void *scratch,
                                const int32_t *lists, const float *corr, int32_t U, void *stream);
 
+/* ---- the skip mask of a ranking call from a sparse "seen" relation (cffm_amd/csrc/seen.hip) ---------------
+ * Additive entry point: CFFM_ABI_VERSION stays 9.  No existing signature, struct, kernel body, default or refusal changes; the mask
+ * is consumed by the unchanged cffm_topk and cffm_rank_of as their `skip`.
+ *
+ * The relation is a CSR on the device: off int32 [R + 1] row offsets, pos int32 [nnz] candidate POSITIONS of the call, and per
+ * context the CSR row row[c] (int32 [C]).  cffm_seen_mask: for every c < C and n < N, mask_out[c * mask_stride + n] = 1 where
+ *   skip_in != NULL and skip_in[c * skip_in_stride + n] != 0, or
+ *   n == pos[j] for a j in [lo, hi), lo = min(max(off[r], 0), nnz), hi = min(max(off[r + 1], 0), nnz), r = row[c] in [0, R)
+ * and 0 otherwise.  Exactly C * N bytes are written, each once; the bytes [N, mask_stride) of a row are never touched, and what
+ * mask_out held before does not matter.  pos within a row may come in any order and may repeat; an entry outside [0, N) is ignored.
+ * A row[c] outside [0, R), off[r + 1] < off[r] and offsets outside [0, nnz] (clamped as above) give an empty or shortened seen set and
+ * never an out-of-range read: whatever the device arrays hold, the kernel reads only inside off[0..R], pos[0..nnz), row[0..C) and
+ * the first N bytes of the rows of skip_in.  skip_in and mask_out must not overlap anywhere (the kernel takes both as restrict-qualified;
+ * only the identical pointer is detected and refused, any other overlap is undefined).  No atomics; the same bytes on every run.  cffm_amd/spec.py seen_mask() is the numpy twin.
+ * CFFM_ERR_BAD_SHAPE, before any launch or HIP call, whatever C is, for: a NULL off, row or mask_out, a NULL pos with nnz != 0
+ * (skip_in may be NULL); N < 1, C < 0, R < 0 or nnz < 0; mask_stride < N; skip_in_stride < N with skip_in != NULL;
+ * skip_in == mask_out.  C == 0 (with arguments that pass) returns 0 without a launch. */
+int cffm_seen_mask(const int32_t *off, const int32_t *pos, int32_t R, int64_t nnz, const int32_t *row, const uint8_t *skip_in,
+                   int64_t skip_in_stride, int32_t C, int32_t N, uint8_t *mask_out, int64_t mask_stride, void *stream);
+
 /* ---- peak probes (bench.py prices the kernels against the data-sheet peaks AND these measured ones) ------------- */
 /* float4 streaming copy src -> dst (bytes % 16 == 0): 2*bytes of HBM traffic per launch */
 int cffm_probe_copy(const void *src, void *dst, int64_t bytes, void *stream);
