@@ -102,3 +102,34 @@ extern "C" int cffm_probe_mfma_bf16(float* out, int32_t iters, int64_t* flops, v
     if (flops) *flops = (int64_t)blocks * 4 * iters * 8 * (2ll * 16 * 16 * 32);
     return 0;
 }
+
+// ONE v_mfma_f32_16x16x32_bf16 per problem, operands and accumulator given by the caller: how the instruction adds its 32 exact
+// products into an fp32 C is read off the device (oracle/mfma_model.py holds the emulation, tests/test_gpu_mfma_model.py the
+// operand sets).  Problem p: A [16][32] and B [32][16] as bf16 bit patterns, C and D [16][16] fp32.  One wavefront per problem in
+// the operand layout of mfma_bf16 (conv.hip): lane (r = lane & 15, kk = lane >> 4) holds row r of A and column r of B at
+// k = 8 kk .. 8 kk + 7, and rows 4 kk .. 4 kk + 3 of column r of C / D.
+__global__ __launch_bounds__(64) void probe_mfma_bf16_once_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ B,
+                                                                  const float* __restrict__ Cin, float* __restrict__ D, int n) {
+    const int64_t p = blockIdx.x;
+    if (p >= n) return;
+    const int lane = threadIdx.x, r = lane & 15, kk = lane >> 4;
+    const probe_u32x4 av = *reinterpret_cast<const probe_u32x4*>(A + p * 512 + r * 32 + 8 * kk);
+    const uint16_t* bp = B + p * 512 + (8 * kk) * 16 + r;
+    unsigned bw[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) bw[t] = (unsigned)bp[(2 * t) * 16] | ((unsigned)bp[(2 * t + 1) * 16] << 16);
+    const probe_u32x4 bv = {bw[0], bw[1], bw[2], bw[3]};
+    const float* cp = Cin + p * 256 + (4 * kk) * 16 + r;
+    const f32x4 c = {cp[0], cp[16], cp[32], cp[48]};
+    const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(probe_bf16x8, av), __builtin_bit_cast(probe_bf16x8, bv),
+                                                            c, 0, 0, 0);
+    float* dp = D + p * 256 + (4 * kk) * 16 + r;
+    dp[0] = d[0]; dp[16] = d[1]; dp[32] = d[2]; dp[48] = d[3];
+}
+extern "C" int cffm_probe_mfma_bf16_once(const uint16_t* A, const uint16_t* B, const float* C, float* D, int32_t n, void* stream) {
+    if (n < 0 || (n > 0 && (!A || !B || !C || !D)) || ((uintptr_t)A & 15)) return CFFM_ERR_BAD_SHAPE;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(probe_mfma_bf16_once_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, A, B, C, D, (int)n);
+    CFFM_CHECK_LAUNCH();
+    return 0;
+}

@@ -113,4 +113,5 @@ PYBIND11_MODULE(_cffm_pybind, m) {
     CFFM_BIND(cffm_probe_read);
     CFFM_BIND(cffm_probe_mfma);
     CFFM_BIND(cffm_probe_mfma_bf16);
+    CFFM_BIND(cffm_probe_mfma_bf16_once);
 }

@@ -727,6 +727,11 @@ int cffm_probe_read(const void *src, void *sink, int64_t bytes, void *stream);
 int cffm_probe_mfma(float *out, int32_t iters, int64_t *flops, void *stream);
 /* the same on the bf16 pipe (v_mfma_f32_16x16x32_bf16): the denominator of the bf16x3 conv loops */
 int cffm_probe_mfma_bf16(float *out, int32_t iters, int64_t *flops, void *stream);
+/* exactly ONE v_mfma_f32_16x16x32_bf16 per problem, D = A B + C on the caller's operands (one wavefront each): n problems of
+ * A [16][32] and B [32][16] as bf16 bit patterns (A 16-byte aligned), C and D [16][16] fp32, all row-major on the device.
+ * What the accumulate of the bf16x3 conv loops rounds to is read from this (oracle/mfma_model.py).  n == 0 returns 0 without a
+ * launch; CFFM_ERR_BAD_SHAPE for n < 0 or a NULL / misaligned pointer with n > 0. */
+int cffm_probe_mfma_bf16_once(const uint16_t *A, const uint16_t *B, const float *C, float *D, int32_t n, void *stream);
 
 /* The same step for the other optimizers of CFFM.py:517-529 (s->optimizer): state1 = Momentum accumulators / Adam m,
  * state2 = Adam v (NULL otherwise), step = 1-based Adam time step.  Adagrad routes to cffm_train_step(state1). */

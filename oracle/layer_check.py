@@ -259,7 +259,10 @@ def stats(got, ref, S, bias_mask=None):
     if r.numel() > 2 ** 24:                       # torch.quantile's limit: a strided subsample
         r = r[::int(math.ceil(r.numel() / 2 ** 24))]
     p999 = float(torch.quantile(r, 0.999)) / U if r.numel() else 0.0
-    return {'beta': beta, 'sigma_beta': sigma, 'n_beta': n_b, 'p999_u': p999, 'max_u': float(r.max()) / U if r.numel() else 0.0, 'n': int(err.numel())}
+    # the signed offset alpha = mean(err) / mean(S) over the same elements: a report field (a constant one-sided loss per accumulate
+    # shows here on a symmetric tensor, where it cannot show in the slope), no tier reads it
+    alpha = float(err[m].sum()) / float(S[m].sum()) if n_b and float(S[m].sum()) > 0 else 0.0
+    return {'beta': beta, 'alpha': alpha, 'sigma_beta': sigma, 'n_beta': n_b, 'p999_u': p999, 'max_u': float(r.max()) / U if r.numel() else 0.0, 'n': int(err.numel())}
 
 
 def _record(name, ratio):
